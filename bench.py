@@ -1,7 +1,13 @@
 """Benchmark of the hot path at BASELINE.json configs[1]: 480x854, 60 000 splats, synthetic data.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1 without a launcher: bench.py re-executes itself under torch.distributed.run, one rank per GPU)
+
+A plain run takes the two measurements below and prints the line; everything else the line can carry (the
+window timed again --repeats times, the event-instrumented stage pass and the roofline blocks built on it,
+the two mid-clip windows, the co-resident clip table, the drop-in levels, the CPU baseline) runs only with
+--full.  --dump-outputs DIR writes what the last timed step computed (rank 0's render, the splats'
+projections and the activated splat parameters after the step, its loss terms) as DIR/<name>.npy.
 
 Two measurements per rank, both with the inputs resident in HBM and bracketed by a barrier and a
 device synchronisation:
@@ -208,12 +214,13 @@ CLIP_WINDOW_FRAME, CAM_I0, JOINT_I0 = 30, 60, 120
 STAGE_SHARE = {"first_frame": 500 / 27050.0, "camera": 59 * 150 / 27050.0, "joint": 59 * 300 / 27050.0}
 
 
-def measure_window(eng, stepper, saved, args, barrier, lib, units=True):
+def measure_window(eng, stepper, saved, args, barrier, lib, units=True, capture=None):
     """Time the pinned window the stepper stands at the start of: W warm-up steps, then EXACTLY K steps between two barriers
     (-> elapsed: what ms_per_step is quoted on), then the same K steps ``args.repeats`` times more, each between barriers of
     its own (-> repeats: a 4 ms region on a box whose minutes differ by 5 % says little alone), then once more with the
     library's HIP events around every stage (-> stage_ms) and the pair count of every iteration read (-> K).  K > 20 timed
-    steps replay the same 20 iterations: the state is put back after every 20."""
+    steps replay the same 20 iterations: the state is put back after every 20.  ``capture``: called right after the K timed
+    steps, before anything else runs (-> outputs: what the last timed step computed)."""
     import gc
 
     def run_window(n):
@@ -245,6 +252,7 @@ def measure_window(eng, stepper, saved, args, barrier, lib, units=True):
         elapsed = time.perf_counter() - t0
         # iterations of the timed region that stepped nothing because a tile outgrew its reserved region (FitEngine.settle_overflow)
         void_iterations = int(eng.overflow[1].item()) - void0
+        outputs = capture() if capture is not None else None
         reps = []
         for _ in range(max(0, args.repeats)):
             eng.restore_state(saved)
@@ -280,7 +288,8 @@ def measure_window(eng, stepper, saved, args, barrier, lib, units=True):
     ks = k_dev[:n_k].cpu().tolist()
     out = {"elapsed": elapsed, "ms_per_step": elapsed / args.steps * 1e3, "timed_region_s": elapsed, "stage_ms": stage_ms,
            "K_list": ks, "K_mean": sum(ks) / len(ks),          # mean over the window's iterations: what the kernels' average durations belong to
-           "void_iterations": void_iterations, "reserved_on": bool(eng._reserved_flag()), "splats": int(eng.N)}
+           "void_iterations": void_iterations, "reserved_on": bool(eng._reserved_flag()), "splats": int(eng.N),
+           "outputs": outputs}
     if reps:
         r = sorted(reps)
         out["repeats"] = {"n": len(r), "median": r[len(r) // 2], "min": r[0], "max": r[-1], "steps_each": args.steps,
@@ -294,6 +303,42 @@ def measure_window(eng, stepper, saved, args, barrier, lib, units=True):
         except Exception as e:
             out["work"] = {"error": f"{type(e).__name__}: {e}"}
     return out
+
+
+DUMP_BUDGET = 60 * 10 ** 6          # --dump-outputs: bytes of array data in all (the limit is 64 MB, .npy headers included)
+
+
+def step_outputs(stepper, tr):
+    """What a caller of the stepper holds after its last step, copied on the device before anything else runs: the render
+    (rgb + depth map, 4 x H x W), the rendered splats' projections and depths, the splats the step's Adam wrote as the trainer
+    hands them out (``get_attribute``: activated, so a saturated colour is 1, not its raw logit +inf), and the step's loss
+    terms.  The inputs are the same in every run; the outputs agree to a tolerance, not bit for bit: the
+    backward blend sums a tile's waves with atomics, and Adam turns the last bits of a near-zero gradient into a whole step."""
+    out = {"render": stepper.last_render.clone(), "uv": stepper.uv.clone(), "depth": stepper.depth.clone()}
+    out.update({k: tr.get_attribute(k).clone() for k in ("xyz", "scale", "rotate", "opacity", "rgb")})
+    out["loss"] = torch.stack([t.double() for t in tr.engine.loss_terms()])     # (rgb term, depth term)
+    return out
+
+
+def write_outputs(path, arrays, budget=DUMP_BUDGET):
+    """--dump-outputs: every array as ``path/<name>.npy``, float64 where it is float64 and float32 otherwise.  Over ``budget``
+    bytes in all (only --size runs far above the default get there), every array keeps the same share of its elements: a
+    fixed, seeded sample, flattened, so that two runs or two builds dump the same indices."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[name] = np.ascontiguousarray(a if a.dtype == np.float64 else a.astype(np.float32))
+    total = sum(a.nbytes for a in host.values())
+    frac = min(1.0, budget / max(total, 1))
+    for name, a in host.items():
+        if frac < 1.0:
+            flat = a.reshape(-1)
+            idx = np.sort(np.random.default_rng(0).choice(flat.size, max(1, int(flat.size * frac)), replace=False))
+            a = flat[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(host)
 
 
 def window_report(m, name, kernels, N, P):
@@ -589,8 +634,16 @@ def main():
     ap.add_argument("--only-window", choices=("first_frame", "camera", "joint"), default=None,
                     help="profiling runs (tools/profile_round.sh): nothing but this pinned window -- no clip fit, no secondary "
                          "tables -- so that the LAST launches of every kernel in a rocprofv3 trace are the window's")
-    ap.add_argument("--repeats", type=int, default=10,
-                    help="time every pinned window this many times more (ms_per_step_repeats: median / min / max)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="time every pinned window this many times more (ms_per_step_repeats: median / min / max); "
+                         "default 10 with --full, 0 without")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the repeats, the event-instrumented stage pass and the roofline "
+                         "blocks, the mid-clip windows, the co-resident clip table, the drop-in levels, the CPU baseline "
+                         "(each still subject to its --no-* flag).  Without it a run does the clip fit and the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0; float32 / float64, at most "
+                         "64 MB in all)")
     ap.add_argument("--no-drop-in-levels", action="store_true",
                     help="skip the secondary table of what the three levels of the drop-in cost (five operators / fused "
                          "render operator / fused fit iteration)")
@@ -602,6 +655,10 @@ def main():
                          "trainer.py:573-582); 0 = none")
     args = ap.parse_args()
 
+    if args.repeats is None:
+        args.repeats = 10 if args.full else 0
+    if not args.full:
+        args.no_stage_pass = args.no_clip_windows = args.no_coresident = args.no_drop_in_levels = args.no_cpu_baseline = True
     if args.only_window:
         args.no_clip = args.no_coresident = args.no_drop_in_levels = args.no_cpu_baseline = True
     global H, W, N_SPLATS
@@ -684,7 +741,11 @@ def main():
     eng = tr.engine
     # the pinned window: iterations [STEP_I0, STEP_I0 + STEP_WINDOW) of this fit, whatever --steps / --warmup are
     stepper.run(STEP_I0)
-    m1 = measure_window(eng, stepper, eng.save_state(), args, barrier, lib)
+    dump = args.dump_outputs and rank == 0
+    m1 = measure_window(eng, stepper, eng.save_state(), args, barrier, lib, units=args.full,
+                        capture=(lambda: step_outputs(stepper, tr)) if dump else None)
+    if dump:
+        write_outputs(args.dump_outputs, m1.pop("outputs"))
     elapsed, kern_all, K, ks = m1["elapsed"], m1["stage_ms"], m1["K_mean"], m1["K_list"]
     void_iterations, reserved_on = m1["void_iterations"], m1["reserved_on"]
     kern = {k: kern_all[k] for k in ("blend_fwd", "loss", "blend_bwd") if k in kern_all}

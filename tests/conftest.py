@@ -44,7 +44,7 @@ _SAMPLED = {
 # ... and tests that launch bench.py as processes of their own or report a wall-clock figure
 _LAST = {
     "test_bench_collectives_over_rccl_with_one_rank", "test_bench_with_two_ranks_on_this_box",
-    "test_operator_cost_is_reported_not_asserted",
+    "test_operator_cost_is_reported_not_asserted", "test_plain_bench_run_times_the_steps_and_dumps_the_last_one",
 }
 
 

@@ -524,7 +524,7 @@ def test_bench_with_two_ranks_on_this_box():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--clip-frames", "2", "--steps", "4", "--warmup", "2",
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--clip-frames", "2", "--steps", "4", "--warmup", "2", "--full",
            "--no-cpu-baseline", "--no-coresident", "--clips-per-gpu", "1"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
@@ -563,7 +563,7 @@ def test_bench_collectives_over_rccl_with_one_rank():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29631", "bench.py", "--gpus", "1", "--collective", "--clip-frames", "2", "--steps", "4", "--warmup", "2",
-           "--no-cpu-baseline", "--no-coresident"]
+           "--full", "--no-cpu-baseline", "--no-coresident"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
@@ -575,6 +575,44 @@ def test_bench_collectives_over_rccl_with_one_rank():
     assert c["frames_per_rank"] == 2 and len(c["rank_wall_s"]) == 1 and c["rank_wall_s"][0] > 0.0
     assert abs(d["value"] - 2 / c["wall_s"]) < 1e-6 * d["value"]
     assert d["roofline"] and 0 < d["roofline"]["frac"] < 1
+
+
+def test_plain_bench_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """``bench.py`` without --full: the clip fit behind ``value`` and exactly --steps timed steps behind ``ms_per_step``,
+    none of the secondary measurements; --dump-outputs writes what the last timed step computed as float32 / float64 .npy
+    files, 64 MB at most in all."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "outputs"
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--clip-frames", "2", "--steps", "7", "--warmup", "2",
+           "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"].startswith("GFlow fit_video frames/sec") and d["unit"] == "frames/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["steps"] == 7 and d["warmup"] == 2
+    assert d["ms_per_step"] > 0 and abs(d["ms_per_step"] - d["timed_region_s"] / 7 * 1e3) < 1e-9 * d["ms_per_step"]
+    assert abs(d["value"] - 2 / d["clip_fit"]["wall_s"]) < 1e-6 * d["value"]
+    assert d["roofline"] is None and d["stage_ms"] == {} and d["ms_per_step_repeats"] is None
+    assert d["step_window_camera"] is None and d["step_window_clip"] is None and d["config"]["step_window"]["work"] is None
+    assert not {"cpu_baseline", "drop_in_levels", "clips_per_gpu"} & set(d)
+    names = ("render", "uv", "depth", "xyz", "scale", "rotate", "opacity", "rgb", "loss")
+    assert sorted(os.listdir(out)) == sorted(n + ".npy" for n in names)
+    assert sum(os.path.getsize(out / (n + ".npy")) for n in names) <= 64 * 10 ** 6
+    a = {n: np.load(out / (n + ".npy")) for n in names}
+    assert a["render"].shape == (4, 480, 854) and a["loss"].shape == (2,) and a["loss"].dtype == np.float64
+    widths = dict(uv=2, depth=1, xyz=3, scale=3, rotate=4, opacity=1, rgb=3)
+    for n, w in widths.items():
+        assert a[n].dtype == np.float32 and a[n].shape == (60000, w), (n, a[n].shape)
+    for n in names:
+        assert np.isfinite(a[n]).all(), n
+    # the splats as get_attribute hands them out: colours and opacities in [0, 1], unit quaternions, non-negative scales
+    assert 0 <= a["rgb"].min() and a["rgb"].max() <= 1 and 0 <= a["opacity"].min() and a["opacity"].max() <= 1
+    assert np.allclose(np.linalg.norm(a["rotate"], axis=1), 1, atol=1e-4) and a["scale"].min() >= 0
 
 
 def test_fit_clip_renders_the_trajectories_of_every_frame():

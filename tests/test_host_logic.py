@@ -447,3 +447,27 @@ def test_bench_window_report_and_clip_iteration_model():
     assert abs(cm["windows_weighted_ms_per_iteration"] - want) < 1e-9
     assert abs(cm["clip_fit_ms_per_iteration"] - 5.9 / 27050 * 1e3) < 1e-9 and 0 < cm["unexplained_frac"] < 0.2
     assert bench.clip_iteration_model(local, None, None) is None
+
+
+def test_bench_write_outputs_keeps_the_types_the_budget_and_the_same_sample(tmp_path):
+    """bench.py --dump-outputs: float64 stays float64, everything else is written as float32; under the budget every array is
+    written whole, over it every array keeps the same seeded share of its elements -- the same indices in every run."""
+    import bench
+    arrays = {"img": torch.arange(1200, dtype=torch.float32).reshape(3, 20, 20), "loss": torch.tensor([0.25, 0.5], dtype=torch.float64),
+              "count": torch.arange(300, dtype=torch.int32)}
+    assert bench.write_outputs(str(tmp_path / "whole"), arrays) == ["count", "img", "loss"]
+    got = {k: np.load(tmp_path / "whole" / (k + ".npy")) for k in arrays}
+    assert got["img"].dtype == np.float32 and np.array_equal(got["img"], arrays["img"].numpy())
+    assert got["loss"].dtype == np.float64 and np.array_equal(got["loss"], [0.25, 0.5])
+    assert got["count"].dtype == np.float32 and np.array_equal(got["count"], np.arange(300))
+    budget = 2000
+    for run in ("a", "b"):
+        bench.write_outputs(str(tmp_path / run), arrays, budget=budget)
+    a = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in arrays}
+    b = {k: np.load(tmp_path / "b" / (k + ".npy")) for k in arrays}
+    assert sum(v.nbytes for v in a.values()) <= budget
+    for k in arrays:
+        assert np.array_equal(a[k], b[k]), k
+        # a sample of the flattened array, in index order
+        flat = arrays[k].reshape(-1).double().numpy()
+        assert 0 < a[k].size < flat.size and np.all(np.diff(a[k]) > 0) and np.isin(a[k], flat).all(), k

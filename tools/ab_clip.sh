@@ -8,7 +8,7 @@ for r in $(seq 1 $R); do
   done
 done
 for v in $A $B; do
-  env $VAR=$v python bench.py --no-clip --no-cpu-baseline --steps 100 --warmup 10 2>/dev/null | python -c "
+  env $VAR=$v python bench.py --full --no-clip --no-cpu-baseline --steps 100 --warmup 10 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); st=d['stage_ms']; print('$VAR=$v bench step %.4f ms  fwd %.1f bwd %.1f us' % (d['ms_per_step'], 1e3*st['blend_fwd'], 1e3*st['blend_bwd']))"
 done

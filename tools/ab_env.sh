@@ -4,7 +4,7 @@
 VAR=$1; A=$2; B=$3; R=${4:-3}; shift 4
 for r in $(seq 1 $R); do
   for v in $A $B; do
-    env $VAR=$v python bench.py --no-clip --no-cpu-baseline --steps 200 --warmup 20 "$@" 2>/dev/null | python -c "
+    env $VAR=$v python bench.py --full --no-clip --no-cpu-baseline --steps 200 --warmup 20 "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 st=d['stage_ms']

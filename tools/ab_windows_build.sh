@@ -7,7 +7,7 @@ WIN=${WIN:-joint}
 for r in 1 2 3; do
   for c in "$@"; do
     make -C gflow_amd/csrc clean >/dev/null; make -C gflow_amd/csrc CONSTS="$c" -j16 2>&1 | grep -E " error"
-    python bench.py --only-window $WIN --steps 20 --warmup 5 2>/dev/null | python -c "
+    python bench.py --full --only-window $WIN --steps 20 --warmup 5 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 w=d['step_window_clip'] if '$WIN'=='joint' else d['step_window_camera']

@@ -5,7 +5,7 @@ WIN=${WIN:-joint}
 VAR=$1; shift
 for r in 1 2 3; do
   for v in "$@"; do
-    env $VAR=$v python bench.py --only-window $WIN --steps 20 --warmup 5 2>/dev/null | python -c "
+    env $VAR=$v python bench.py --full --only-window $WIN --steps 20 --warmup 5 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 w=d['step_window_clip'] if '$WIN'=='joint' else d['step_window_camera']

@@ -22,7 +22,7 @@ export TMPDIR=/tmp
 # <7>): 98 % of the metric's iterations are of the last two kinds.
 cd /tmp
 for WIN in first_frame camera joint; do
-  BENCH="python $ROOT/bench.py --steps 20 --warmup 5 --no-stage-pass --repeats 0 --only-window $WIN"
+  BENCH="python $ROOT/bench.py --full --steps 20 --warmup 5 --no-stage-pass --repeats 0 --only-window $WIN"
   mkdir -p "$OUT/$WIN"
   rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$WIN/trace" -o r -- $BENCH > "$OUT/$WIN/bench_trace.log" 2>&1
   rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/$WIN/fetch" -o r -- $BENCH > "$OUT/$WIN/bench_fetch.log" 2>&1

@@ -2,7 +2,7 @@
 # SQ counters of bench.py's window (last 40 launches of every kernel)   gpurun -- bash tools/quick_pmc.sh tag [ENV=VAL ...]
 TAG=$1; shift
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/qp_$TAG; mkdir -p $OUT; export TMPDIR=/tmp; cd /tmp
-env "$@" rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_INSTS_SALU GRBM_GUI_ACTIVE --output-format csv -d $OUT -o r -- python $ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-stage-pass --no-clip > $OUT/log 2>&1
+env "$@" rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_INSTS_SALU GRBM_GUI_ACTIVE --output-format csv -d $OUT -o r -- python $ROOT/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-stage-pass --no-clip > $OUT/log 2>&1
 cd $ROOT
 python - $OUT "${FILTER:-blend}" <<'PY'
 import csv, glob, sys, os

@@ -3,7 +3,7 @@
 #   gpurun -- bash tools/quick_trace.sh tag [ENV=VAL ...]
 TAG=$1; shift
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/qt_$TAG; mkdir -p $OUT; export TMPDIR=/tmp; cd /tmp
-env "$@" rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o r -- python $ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-stage-pass --no-clip > $OUT/log 2>&1
+env "$@" rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o r -- python $ROOT/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-stage-pass --no-clip > $OUT/log 2>&1
 cd $ROOT
 python - $OUT <<'PY'
 import csv, glob, sys, os

@@ -1,6 +1,6 @@
 set -u
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/plm; mkdir -p $OUT; export TMPDIR=/tmp
-BENCH="python $ROOT/bench.py --steps 30 --warmup 10 --no-cpu-baseline --no-stage-pass --no-clip"
+BENCH="python $ROOT/bench.py --full --steps 30 --warmup 10 --no-cpu-baseline --no-stage-pass --no-clip"
 cd /tmp
 rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_LDS SQ_WAVES GRBM_GUI_ACTIVE --output-format csv -d $OUT/sq -o r -- $BENCH > $OUT/sq.log 2>&1
 rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_SALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_LDS SQ_INST_CYCLES_SALU SQ_LDS_IDX_ACTIVE --output-format csv -d $OUT/sq2 -o r -- $BENCH > $OUT/sq2.log 2>&1

@@ -4,7 +4,7 @@ WRITE_SIZE passes; FETCH_SIZE doubled, the gfx950 correction of MI355X_MICROARCH
 
 Every figure is an average over the launches of ONE of bench.py's three PINNED WINDOWS (first_frame / camera / joint: one
 directory of passes each, bench.py --only-window) -- the last WINDOW_LAUNCHES dispatches of each kernel: with the driver's
-flags (--steps 20 --warmup 5 --no-stage-pass --repeats 0) bench.py runs up to the window, 27 warm-up steps, and then the
+flags (--full --steps 20 --warmup 5 --no-stage-pass --repeats 0) bench.py runs up to the window, 27 warm-up steps, and then the
 window twice (the timed pass and the pass that reads the pair counts) --, so the counters belong to the workload the bench
 line is timed on.  The whole-run --stats table is kept beside it.
 
@@ -189,7 +189,7 @@ def main():
     clip = {k: v for k, v in kernel_stats(os.path.join(root, "clip")).items() if k in STAGE_OF or "blend" in k}
     print(json.dumps({
         "tag": os.path.basename(os.path.normpath(root)),
-        "command": "python bench.py --steps 20 --warmup 5 --no-stage-pass --repeats 0 --only-window <first_frame|camera|joint>  "
+        "command": "python bench.py --full --steps 20 --warmup 5 --no-stage-pass --repeats 0 --only-window <first_frame|camera|joint>  "
                    "(the driver's flags; one pinned window per set of passes)",
         "method": "rocprofv3 --kernel-trace --stats; --pmc FETCH_SIZE; --pmc WRITE_SIZE; --pmc SQ_* (separate runs); "
                   "FETCH_SIZE x2 (gfx950 counts 128-B requests as 64 B), both counters in KB; every figure averaged over "
