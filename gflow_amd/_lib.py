@@ -23,7 +23,7 @@ _lib = None
 
 c_void_p, c_int, c_float, c_size_t, c_int64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_int64
 
-MIN_VERSION = 304          # GFL_VERSION of the include/gflow_hip.h this binding mirrors (overflow[4], sort-order trailer, gfl_constants_n)
+MIN_VERSION = 305          # GFL_VERSION of the include/gflow_hip.h this binding mirrors (gfl_fit_state.flags, gfl_scan_f64)
 
 # name -> (restype, argtypes); mirrors include/gflow_hip.h one to one
 _P = c_void_p
@@ -79,6 +79,8 @@ SIGNATURES = {
     "gfl_selftest_cov2d": (c_int, [_P, _P, c_int, _P, _P, _P]),
     "gfl_selftest_block_mask": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P]),
     "gfl_concave_hull": (c_int, [_P, c_int, ctypes.c_double, ctypes.c_double, _P, c_int]),
+    "gfl_scan_f64_workspace_bytes": (c_size_t, [c_int]),
+    "gfl_scan_f64": (c_int, [_P, c_int, _P, _P, c_size_t, _P]),
     "gfl_abi_sizes": (c_int, [_P, _P]),
     "gfl_profile_enable": (c_int, [ctypes.c_uint]),
     "gfl_profile_read": (c_int, [_P, _P, c_int]),
@@ -142,6 +144,26 @@ def need_device(*tensors):
 
 def scratch(nbytes, device):
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
+
+
+def scan_f64(x):
+    """Inclusive scan of a 1-D tensor as float64 on the device (gfl_scan_f64): what torch.cumsum(x.double(), 0) computes,
+    summed in an order fixed by the length alone -- the same bits on every call.  The deterministic mode's CDFs."""
+    need_device(x)
+    x = x.reshape(-1).double().contiguous()
+    out = torch.empty_like(x)
+    n = x.numel()
+    if n:
+        lib = load()
+        ws = scratch(lib.gfl_scan_f64_workspace_bytes(n), x.device)
+        check(lib.gfl_scan_f64(ptr(x), n, ptr(out), ptr(ws), ws.numel(), stream()), "scan_f64")
+    return out
+
+
+def resolve_deterministic(deterministic):
+    """The deterministic mode a call runs in: ``deterministic`` if given, else torch's own switch
+    (torch.use_deterministic_algorithms)."""
+    return torch.are_deterministic_algorithms_enabled() if deterministic is None else bool(deterministic)
 
 
 # ---------------------------------------------------------------------------- CU-masked streams

@@ -137,6 +137,7 @@ static FitWs carve(const gfl_fit_state* st) {
     w.sched.cap_q = (int)(((size_t)SCHED_MAX_QUEUES * sched_queue_capacity((int)T, 64)) / w.sched.nq);
     w.sched.split_min = 0;
     w.sched.xcd = 1;         // XCD-local bands + LPT in rounds wherever the grid allows it (sched_xcd_usable, next_sched_ok)
+    w.sched.det = (st->flags & GFL_FIT_DETERMINISTIC) ? 1 : 0;     // ties of the tile order by tile index (gfl_sched.hpp)
     w.sched_fwd = w.sched;
     w.sched_fwd.work = (int32_t*)p;
     p += up256(4 * T * sizeof(int32_t));
@@ -211,6 +212,7 @@ static NextSched next_sched_reserving(const gfl_fit_state* st, const FitWs& w, i
 static int fit_check(const gfl_fit_state* st, const gfl_fit_hyper* hp) {
     if (!st || !hp) return GFL_ERR_INVALID;
     if (st->N < 0 || st->N > st->cap || st->W <= 0 || st->H <= 0 || st->K_cap < 0) return GFL_ERR_INVALID;
+    if (st->flags & ~GFL_FIT_DETERMINISTIC) return GFL_ERR_INVALID;
     if (!st->params || !st->rec || !st->pose || !st->intr || !st->extr || !st->render || !st->final_T ||
         !st->n_contrib || !st->tile_offsets || !st->ids || !st->tile_range || !st->overflow || !st->workspace)
         return GFL_ERR_INVALID;
@@ -412,6 +414,20 @@ int gfl_fit_snapshot_stage(const gfl_fit_state* src, const gfl_fit_state* dst, g
 
 int gfl_render_fwd(const gfl_fit_state* st, const gfl_fit_hyper* hp, gfl_stream_t stream) {
     if (st && st->foot_flags) return GFL_ERR_INVALID;
+    if (st && (st->flags & GFL_FIT_DETERMINISTIC)) {
+        // The tile weights are the work the blend launches counted in the state's LAST call -- for a pooled operator engine
+        // (gflow_amd/render.py), whatever it rendered before.  A render must be a function of its inputs: the feedback is
+        // dropped and this call schedules by its own list lengths (three small memsets).
+        const int rc = fit_check(st, hp);
+        if (rc) return rc;
+        const int T = ((st->W + GFL_TILE - 1) / GFL_TILE) * ((st->H + GFL_TILE - 1) / GFL_TILE);
+        const FitWs w = carve(st);
+        hipStream_t s = (hipStream_t)stream;
+        if (check(hipMemsetAsync(w.sched.work, 0, 4 * (size_t)T * sizeof(int32_t), s)) ||
+            check(hipMemsetAsync(w.sched_fwd.work, 0, 4 * (size_t)T * sizeof(int32_t), s)) ||
+            check(hipMemsetAsync(w.sched_valid, 0, sizeof(int32_t), s)))
+            return GFL_ERR_HIP;
+    }
     return fit_forward_impl(st, hp, stream, 1);
 }
 

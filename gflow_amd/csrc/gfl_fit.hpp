@@ -200,6 +200,8 @@ constexpr int FB = 256;   // staged splats per batch (forward)
 constexpr int FBL = GFL_FWD_LONG_BATCH;   // ... of the long-tile walk (512: forward inside a clip fit 56.6 against 52.7 us, round 4)
 constexpr int FBB = 192;  // backward: 18.6 KB of LDS per workgroup -> 8 workgroups per CU (the tile queues of
                           // gfl_sched.hpp assume that all workgroups of a blend launch are resident)
+constexpr int FBB_DET = 64;   // ... in the deterministic mode (GFL_FIT_DETERMINISTIC): one row of sums per 8x8 block, four rows
+                              // per staged splat -- 64 x (48 + 4 + 4 x 48 + 1) B = 15.7 KB, still eight workgroups per CU
 
 // "every lane of the workgroup says yes" with ONE barrier and no dependence on the block's shape (HIP's __syncthreads_and reads
 // blockDim / threadIdx.y for a flat thread id: loop-invariant values the forward blend then carried through its tile loop --

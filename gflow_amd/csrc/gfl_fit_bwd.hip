@@ -103,11 +103,17 @@ __device__ void loss_tail(const LossTail& t) {
     }
 }
 
+// DET (GFL_FIT_DETERMINISTIC): the four waves do not add their sums into one row with LDS float atomics, in whatever order they
+// arrive; each leaves its sums in a row of its own 8x8 block with plain stores (one lane per component and splat: the
+// reduce-scatter hands each component to one lane) and the tile folds the four rows in block order, ((b0 + b1) + b2) + b3.
+// Rows by BLOCK, not by wave or SIMD: which wave walks which block depends on where the dispatcher put the waves (plan_ok).
+// Fewer splats per batch (FBB_DET) keep the four rows inside the LDS that eight resident workgroups per CU leave.
+//
 // SUMS: how many of the ten per-pair sums somebody reads.  10: the first frame.  7: later frames, whose colours are frozen
 // (freeze_rgb, trainer.py:537-540) -- the three colour sums are neither formed nor reduced (18 VALU ops in the wave
 // reduce-scatter instead of 27 per unit).  6: the camera-only stage (freeze_all_splats) -- every splat gradient is zeroed
 // afterwards, and the pose gradient needs only the five moments and the depth feature's gradient (16 ops).
-template <int SUMS>
+template <int SUMS, bool DET = false>
 __global__ void __launch_bounds__(256, 8) fused_blend_bwd_kernel(const float* __restrict__ rec,
                                                               const int32_t* __restrict__ ids,
                                                               const int32_t* __restrict__ tile_range, float bg, int W,
@@ -132,10 +138,13 @@ __global__ void __launch_bounds__(256, 8) fused_blend_bwd_kernel(const float* __
     // now the stores of this kernel, which is bound by instruction issue and does not wait for them.  A row carries the number
     // of the forward it belongs to (FitWs.stamp) in its eleventh float: pairs nobody walks -- behind the tile's deepest
     // contributor -- need no zero row.
-    __shared__ RecLDS recs[FBB];
-    __shared__ int32_t s_gid[FBB];
-    __shared__ float acc[FBB][REC];
-    __shared__ unsigned char s_mask[FBB];
+    constexpr int NB = DET ? FBB_DET : FBB;          // splats staged per batch
+    constexpr int NACC = DET ? 4 : 1;                // rows of sums per staged splat
+    static_assert(!DET || NACC * NB * REC == 3 * 4 * 256, "the deterministic rows are cleared with three float4 per lane");
+    __shared__ RecLDS recs[NB];
+    __shared__ int32_t s_gid[NB];
+    __shared__ float acc[NACC][NB][REC];
+    __shared__ unsigned char s_mask[NB];
     __shared__ int32_t s_max_last;
     __shared__ int32_t s_ticket;
     __shared__ int32_t s_simd[4];
@@ -212,8 +221,8 @@ __global__ void __launch_bounds__(256, 8) fused_blend_bwd_kernel(const float* __
     const int hi = last_part ? depth_n : min((item.part + 1) * seg, depth_n);
 
     const int stamp = *stamp_ptr;
-    for (int r0 = 0; r0 < hi - lo; r0 += FBB) {
-        const int pos_t = tid < FBB ? hi - 1 - r0 - tid : -1;          // slot tid <-> list position pos_t
+    for (int r0 = 0; r0 < hi - lo; r0 += NB) {
+        const int pos_t = tid < NB ? hi - 1 - r0 - tid : -1;           // slot tid <-> list position pos_t
         __syncthreads();
         if (pos_t >= lo) {
             const int g = ids[start + pos_t];
@@ -223,12 +232,15 @@ __global__ void __launch_bounds__(256, 8) fused_blend_bwd_kernel(const float* __
             s_gid[tid] = g;
             s_mask[tid] = (unsigned char)block_mask(p0, p1, p2.z, tx * GFL_TILE, ty * GFL_TILE);
         }
-        if (tid < FBB) {
-            float4* az = reinterpret_cast<float4*>(&acc[tid][0]);
+        if constexpr (DET) {
+            float4* az = reinterpret_cast<float4*>(&acc[0][0][0]);
+            az[tid] = zero4; az[tid + 256] = zero4; az[tid + 512] = zero4;
+        } else if (tid < NB) {
+            float4* az = reinterpret_cast<float4*>(&acc[0][tid][0]);
             az[0] = zero4; az[1] = zero4; az[2] = zero4;
         }
         __syncthreads();
-        const int cnt = min(FBB, hi - lo - r0);
+        const int cnt = min(NB, hi - lo - r0);
         for (int c0 = 0; c0 < cnt; c0 += 64) {
             const int slot = c0 + lane;
             const int spos = hi - 1 - r0 - slot;
@@ -277,7 +289,11 @@ __global__ void __launch_bounds__(256, 8) fused_blend_bwd_kernel(const float* __
                 } else {
                     mine = wave_reduce_scatter10(v, lane);
                 }
-                if (comp >= 0) atomicAdd(&acc[j][comp], mine);
+                if constexpr (DET) {
+                    if (comp >= 0) acc[blk][j][comp] = mine;
+                } else {
+                    if (comp >= 0) atomicAdd(&acc[0][j][comp], mine);
+                }
             }
         }
         __syncthreads();
@@ -295,10 +311,25 @@ __global__ void __launch_bounds__(256, 8) fused_blend_bwd_kernel(const float* __
                 row = off >= 0 ? wide_base + off + j : -1;
             }
             if (row >= 0) {
-                const float4* a4 = reinterpret_cast<const float4*>(&acc[tid][0]);
                 float4* o = reinterpret_cast<float4*>(pair_grad + (size_t)row * PG);
-                o[0] = a4[0]; o[1] = a4[1];
-                o[2] = make_float4(a4[2].x, a4[2].y, __int_as_float(stamp), 0.f);
+                if constexpr (DET) {
+                    float4 s[3];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        const float4 b0 = reinterpret_cast<const float4*>(&acc[0][tid][0])[k];
+                        const float4 b1 = reinterpret_cast<const float4*>(&acc[1][tid][0])[k];
+                        const float4 b2 = reinterpret_cast<const float4*>(&acc[2][tid][0])[k];
+                        const float4 b3 = reinterpret_cast<const float4*>(&acc[3][tid][0])[k];
+                        s[k] = make_float4(((b0.x + b1.x) + b2.x) + b3.x, ((b0.y + b1.y) + b2.y) + b3.y,
+                                           ((b0.z + b1.z) + b2.z) + b3.z, ((b0.w + b1.w) + b2.w) + b3.w);
+                    }
+                    o[0] = s[0]; o[1] = s[1];
+                    o[2] = make_float4(s[2].x, s[2].y, __int_as_float(stamp), 0.f);
+                } else {
+                    const float4* a4 = reinterpret_cast<const float4*>(&acc[0][tid][0]);
+                    o[0] = a4[0]; o[1] = a4[1];
+                    o[2] = make_float4(a4[2].x, a4[2].y, __int_as_float(stamp), 0.f);
+                }
             }
         }
     }
@@ -321,10 +352,13 @@ __global__ void __launch_bounds__(256, 8) fused_blend_bwd_kernel(const float* __
   }
 }
 
-// ---- launcher (gfl_fit.hpp).  sums: 10 / 7 / 6 (see the kernel)
+// ---- launcher (gfl_fit.hpp).  sums: 10 / 7 / 6 (see the kernel); the deterministic instantiations with the state's flag
 void launch_blend_bwd(const gfl_fit_state* st, float bg, int gx, int gy, int grid, int sums, const float* d_out, const TileQueue& q,
                       const FitWs& w, const LossTail& lt, hipStream_t s) {
     auto kern = sums == 6 ? fused_blend_bwd_kernel<6> : (sums == 7 ? fused_blend_bwd_kernel<7> : fused_blend_bwd_kernel<10>);
+    if (st->flags & GFL_FIT_DETERMINISTIC)
+        kern = sums == 6 ? fused_blend_bwd_kernel<6, true>
+                         : (sums == 7 ? fused_blend_bwd_kernel<7, true> : fused_blend_bwd_kernel<10, true>);
     kern<<<grid, 256, 0, s>>>(st->rec, st->ids, st->tile_range, bg, st->W, st->H, gx, st->final_T, st->n_contrib, d_out, w.pair_grad,
                               q, w.sched.work, w.ckpt, st->render, lt, gy, w.wide_off, w.wide_base, w.stamp);
 }

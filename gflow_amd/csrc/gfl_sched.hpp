@@ -29,8 +29,12 @@
 //             T and S = sum_c g_c (out_c - C_c)).
 // The 8 workgroups resident on a CU pull from that CU's queue (first pull = slot number, later
 // pulls through a per-queue counter that only those 8 contend for).
-// The schedule decides WHERE a tile is processed, never what is computed: results do not depend on
-// it, and a dispatcher that places workgroups differently only loses the balance.
+// The schedule decides WHERE a tile is processed, and -- through the first tiles of the queues, which are split -- how the
+// heaviest tiles are walked: segments from checkpoints (backward) and tree-order products on four CUs (forward) change the
+// last bits of T, the render and the gradients of those tiles.  In the default mode the tiles of one quantised weight are
+// ordered by LDS-atomic arrival, so a tie at the first round's cutoff can change results from run to run; the
+// deterministic mode (Sched.det, GFL_FIT_DETERMINISTIC) orders them by tile index (sched_stable_position).  Everything
+// else the rounds decide -- which queue, which SIMD walks which block -- moves whole tiles between CUs and changes nothing.
 #pragma once
 
 namespace gfl {
@@ -51,6 +55,7 @@ struct Sched {
     int cap_q;           // capacity of one queue
     int split_min;       // forward schedule: a first tile with a longer list is walked on four CUs; 0: never
     int xcd;             // 1: XCD-local bands + snake deal (schedule_tiles_xcd) instead of the batched LPT
+    int det;             // 1: tiles of equal quantised weight in tile order (GFL_FIT_DETERMINISTIC)
 };
 
 __host__ __device__ inline int sched_queue_capacity(int T, int nq) { return 2 * ((T + nq - 1) / nq) + 8; }
@@ -147,6 +152,37 @@ __device__ __forceinline__ int sched_scan_bins(int32_t* bins, int32_t* wsum) {
     return tot;
 }
 
+// Deterministic mode: the counting sort's positions with ties in tile order, one chunk of BLOCK tiles at a time.  bins[]
+// holds the running start of every bin (SCHED_BINS bins, 10-bit keys); tile t = c * BLOCK + threadIdx.x of chunk c gets its
+// bin's start + the tiles of its bin with a lower index (returned; -1 for t >= T), and bins[] is advanced past the chunk.
+// The lanes of a wave with the same key find each other with one ballot per key bit, and the waves take their turns in
+// wave order (a barrier each).  key_of(t) is called for t < T only.  Chunks in ascending order; whole workgroup.
+template <int BLOCK, typename KeyFn>
+__device__ __forceinline__ int sched_stable_position(int c, int T, int32_t* bins, KeyFn key_of) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int t = c * BLOCK + (int)threadIdx.x;
+    const bool valid = t < T;
+    const int key = valid ? key_of(t) : 0;
+    unsigned long long peers = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < 10; ++b) {
+        const unsigned long long ones = __ballot((key >> b) & 1);
+        peers &= ((key >> b) & 1) ? ones : ~ones;
+    }
+    const int below = __popcll(peers & ((1ull << lane) - 1ull));
+    const bool last = (peers >> lane) == 1ull;                       // the highest lane of its key
+    int pos = -1;
+    for (int w = 0; w < BLOCK / 64; ++w) {
+        if (wave == w && valid) {
+            const int base = bins[key];
+            pos = base + below;
+            if (last) bins[key] = base + below + 1;
+        }
+        __syncthreads();
+    }
+    return pos;
+}
+
 // static LDS of the scheduling workgroup, declared ONCE in the kernel that calls either scheduler
 struct SchedLds {
     int32_t bins[SCHED_BINS];
@@ -215,9 +251,16 @@ __device__ void schedule_tiles(const int32_t* __restrict__ tile_counts, int T, c
         bins[2 * tid + 1] = excl + a;
     }
     __syncthreads();
-    for (int t = tid; t < T; t += SCHED_BLOCK) {
-        const int pos = atomicAdd(&bins[SCHED_BINS - 1 - (w16[t] >> shift)], 1);
-        ord16[pos] = (unsigned short)t;
+    if (sc.det) {
+        for (int c = 0; c * SCHED_BLOCK < T; ++c) {                    // (uniform)
+            const int pos = sched_stable_position<SCHED_BLOCK>(c, T, bins, [&](int t) { return SCHED_BINS - 1 - (w16[t] >> shift); });
+            if (pos >= 0) ord16[pos] = (unsigned short)(c * SCHED_BLOCK + tid);
+        }
+    } else {
+        for (int t = tid; t < T; t += SCHED_BLOCK) {
+            const int pos = atomicAdd(&bins[SCHED_BINS - 1 - (w16[t] >> shift)], 1);
+            ord16[pos] = (unsigned short)t;
+        }
     }
     __syncthreads();
     // (Round 3 measured two ways of tightening the CU balance further, both rejected.  A shared pool of the lightest tiles --
@@ -408,16 +451,30 @@ __device__ void schedule_tiles_xcd(const int32_t* __restrict__ tile_counts, int 
     constexpr int MAXPER = SCHED_PLAN_TILES / BLOCK;
     int my_pos[MAXPER];
     __syncthreads();
+    if (sc.det) {
+        // ties in tile order; tile k * BLOCK + tid is this thread's k-th here (not the contiguous run above)
 #pragma unroll
-    for (int k = 0; k < MAXPER; ++k) {
-        const int t = t_lo + k;
-        if (k < per && t < t_hi) my_pos[k] = atomicAdd(&bins[(int)ord16[t] * 128 + 127 - (w16[t] >> shift)], 1);
-    }
-    __syncthreads();
+        for (int k = 0; k < MAXPER; ++k)
+            if (k * BLOCK < T)                                         // (uniform)
+                my_pos[k] = sched_stable_position<BLOCK>(k, T, bins,
+                                                         [&](int t) { return (int)ord16[t] * 128 + 127 - (w16[t] >> shift); });
 #pragma unroll
-    for (int k = 0; k < MAXPER; ++k) {
-        const int t = t_lo + k;
-        if (k < per && t < t_hi) ord16[my_pos[k]] = (unsigned short)t;
+        for (int k = 0; k < MAXPER; ++k) {
+            const int t = k * BLOCK + tid;
+            if (t < T) ord16[my_pos[k]] = (unsigned short)t;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < MAXPER; ++k) {
+            const int t = t_lo + k;
+            if (k < per && t < t_hi) my_pos[k] = atomicAdd(&bins[(int)ord16[t] * 128 + 127 - (w16[t] >> shift)], 1);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < MAXPER; ++k) {
+            const int t = t_lo + k;
+            if (k < per && t < t_hi) ord16[my_pos[k]] = (unsigned short)t;
+        }
     }
     __syncthreads();
     // ---- deal, band by band: LPT in rounds.  Thread x * NQG + j owns queue q = j * 8 + x, so the NQG queues of a band sit

@@ -190,7 +190,7 @@ def stage_kwargs(c, frames, i, stage):
 
 
 def fit_clip(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, log=None, load_extr=True, keep=None,
-             async_snapshots=None):
+             async_snapshots=None, deterministic=None):
     """Fit one clip; returns the metrics dict of this clip (PSNR summed over its frames; with ``cfg["traj_num"]`` > 0 also
     ``"traj"``: the per-frame trajectory images and seed projections, host arrays -- what the reference's frame loop collects in
     ``frames_sequence_traj / frames_sequence_traj_upon / sequence_traj``).
@@ -198,10 +198,16 @@ def fit_clip(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, 
     (``extr``, read from the sequence's camera files) load it before they are fitted
     (fit_video.py:115-116, :252-253).  ``keep``: a dict that receives the trainer (``keep["trainer"]``) and the
     per-frame PSNR as device scalars (``keep["psnr"]``) -- for tests and tools; with ``cfg["traj_num"]`` also the per-frame
-    trajectory images and seed projections as they left for the host (``keep["traj"]``)."""
+    trajectory images and seed projections as they left for the host (``keep["traj"]``).
+    ``deterministic``: the same frames, cfg and seed give the same metrics, parameters and trajectory outputs bit for bit
+    (SimpleGaussian(deterministic=)); None follows torch.are_deterministic_algorithms_enabled().  Needs
+    ``fused=True``."""
+    if deterministic and not fused:
+        raise ValueError("fit_clip(deterministic=True) needs fused=True: the operator path's alpha_blending backward has no "
+                         "deterministic implementation")
     dev_ = torch.device(device)
     g = fit_clip_steps(frames, device, cfg=cfg, seed=seed, snapshot_interval=snapshot_interval, fused=fused, log=log,
-                       load_extr=load_extr, chunk=None, keep=keep,
+                       load_extr=load_extr, chunk=None, keep=keep, deterministic=deterministic,
                        **({} if async_snapshots is None else {"async_snapshots": async_snapshots}))
 
     def drive():
@@ -228,7 +234,7 @@ def fit_clip(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, 
 
 
 def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, log=None, load_extr=True, chunk=None,
-                   async_snapshots=True, keep=None, cu_count=0):
+                   async_snapshots=True, keep=None, cu_count=0, deterministic=None):
     """fit_clip as a generator: yields after every ``chunk`` iterations of a stage (None: never) and returns the metrics
     dict.  The caller owns the stream the work is enqueued on (fit_clips_concurrent gives every clip its own)."""
     from .trainer import SimpleGaussian
@@ -238,7 +244,7 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
         frames = upload_clip(frames, device)         # (bench.py uploads before its clock starts: "inputs resident in HBM")
     f0 = frames[0]
     tr = SimpleGaussian(f0["image"], f0["depth"], num_points=c["num_points"], background=c["background"],
-                        device=device, seed=seed, fused=fused)
+                        device=device, seed=seed, fused=fused, deterministic=deterministic)
     tr.async_snapshots = bool(async_snapshots)       # (trainer.py: snapshots composed beside the next iterations, or behind theirs)
     tr.cu_count = int(cu_count)                      # (the caller's stream is CU-masked: fit_clips_concurrent(partition=True))
     tr.load_camera(focal=f0["focal"], pp=f0["pp"])
@@ -354,7 +360,8 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
 NUMERIC_KEYS = ("psnr_sum", "frames", "iterations", "rasterisations", "clips", "splats_final", "void_iterations")
 
 
-def fit_clips_concurrent(clips, device, cfg=None, seeds=None, snapshot_interval=0, chunk=32, partition=False):
+def fit_clips_concurrent(clips, device, cfg=None, seeds=None, snapshot_interval=0, chunk=32, partition=False,
+                         deterministic=None):
     """Fit several clips AT THE SAME TIME on ONE device, in one host thread: every clip has its own trainer, engine and
     STREAM, and the clips take turns enqueueing ``chunk`` iterations each (fit_clip_steps), so their graph launches
     interleave on the device.  One fit leaves the chip partly idle -- its kernels are a chain of dependent launches,
@@ -368,7 +375,9 @@ def fit_clips_concurrent(clips, device, cfg=None, seeds=None, snapshot_interval=
     ``partition``: every clip's stream is CU-MASKED to its own share of every XCD (_lib.cu_partition: 256 CUs / n, each share
     spanning all eight XCDs and their L2s) and its engines size their persistent blend grids and tile queues for that share
     (gfl_fit_state.cu_count) -- the clips then run SIDE BY SIDE instead of taking turns on every CU.  Results do not depend
-    on it (the schedule never enters a result).  Measured in bench.py's ``clips_per_gpu`` table."""
+    on it (the schedule never enters a result).  Measured in bench.py's ``clips_per_gpu`` table.
+    ``deterministic`` (None: torch's switch): every clip's result is bit for bit that of fit_clip(..., deterministic=True)
+    with the same seed -- without ``partition``, which changes the number of tile queues (include/gflow_hip.h)."""
     n = len(clips)
     seeds = list(range(n)) if seeds is None else seeds
     dev = torch.device(device)
@@ -387,7 +396,7 @@ def fit_clips_concurrent(clips, device, cfg=None, seeds=None, snapshot_interval=
     # (a lone fit takes its snapshots on a side stream; several fits already fill each other's gaps, and a side stream + shadow
     #  engine per clip cost them more than they give)
     gens = [fit_clip_steps(clips[i], dev, cfg, seed=seeds[i], snapshot_interval=snapshot_interval, chunk=chunk,
-                           async_snapshots=n == 1, cu_count=shares[i][1] if shares else 0)
+                           async_snapshots=n == 1, cu_count=shares[i][1] if shares else 0, deterministic=deterministic)
             for i in range(n)]
     results = [None] * n
     live = list(range(n))
@@ -423,7 +432,10 @@ def main(argv=None):
                     help="path of a prepared sequence folder (images + the reference's sibling folders, "
                          "gflow_amd/io.py); may be given several times, one clip each; default: synthetic clips")
     ap.add_argument("--resize", type=int, default=None, help="shorter image side after loading a --sequence")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="bit-identical results for identical inputs (the library's deterministic mode, INTEGRATION.md)")
     args = ap.parse_args(argv)
+    det = True if args.deterministic else None
     from . import synthetic as S
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -475,10 +487,10 @@ def main(argv=None):
         group = order[g0:g0 + c]
         if len(group) == 1:
             ci = group[0]
-            res = [fit_clip(clips[ci], dev, cfg, seed=ci,
+            res = [fit_clip(clips[ci], dev, cfg, seed=ci, deterministic=det,
                             log=(lambda s, ci=ci: print(f"[rank {rank} clip {ci}] {s}")) if args.verbose else None)]
         else:
-            res = fit_clips_concurrent([clips[ci] for ci in group], dev, cfg, seeds=group)
+            res = fit_clips_concurrent([clips[ci] for ci in group], dev, cfg, seeds=group, deterministic=det)
         for m in res:
             for k in METRIC_NAMES:
                 local[k] += m[k]

@@ -32,7 +32,9 @@ class FitState(ctypes.Structure):          # mirrors gfl_fit_state
                 ("render", _P), ("final_T", _P), ("n_contrib", _P),
                 ("d_render", _P), ("err_px", _P), ("sums", _P),
                 ("tile_offsets", _P), ("ids", _P), ("tile_range", _P), ("overflow", _P),
-                ("workspace", _P), ("workspace_bytes", ctypes.c_size_t), ("cu_count", _I), ("reserved_", _I)]
+                ("workspace", _P), ("workspace_bytes", ctypes.c_size_t), ("cu_count", _I), ("flags", _I)]
+
+GFL_FIT_DETERMINISTIC = 1                  # gfl_fit_state.flags (include/gflow_hip.h)
 
 
 class FitHyper(ctypes.Structure):          # mirrors gfl_fit_hyper
@@ -83,11 +85,14 @@ def set_profile(mask):
 
 
 class FitEngine:
-    def __init__(self, W, H, capacity, device, K_cap=None, bg=0.0, cu_count=0):
+    def __init__(self, W, H, capacity, device, K_cap=None, bg=0.0, cu_count=0, deterministic=False):
         """``cu_count``: compute units the stream this engine is driven on may use (a CU-masked stream, _lib.masked_stream;
-        0 = the whole device): the persistent blend grids and their tile queues are sized for it (gfl_fit_state.cu_count)."""
+        0 = the whole device): the persistent blend grids and their tile queues are sized for it (gfl_fit_state.cu_count).
+        ``deterministic``: every launch on this engine reduces in a fixed order -- bit-identical results for identical
+        inputs (GFL_FIT_DETERMINISTIC, include/gflow_hip.h); may be changed between calls (``self.deterministic``)."""
         self.lib = L.load()
         self.cu_count = int(cu_count)
+        self._deterministic = bool(deterministic)
         _declare(self.lib)
         self.dev = torch.device(device)
         if self.dev.type != "cuda":
@@ -310,12 +315,24 @@ class FitEngine:
                 setattr(s, name, None if t is None else t.data_ptr())
             s.workspace_bytes = self.workspace.numel()
             s.cu_count = self.cu_count
+            s.flags = GFL_FIT_DETERMINISTIC if self._deterministic else 0
             if self.gt_rgb is not None and self.foot_flags is None:
                 # SSIM statistics of the (masked) target, once per set_targets (gfl_fit_prepare_targets)
                 L.check(self.lib.gfl_fit_prepare_targets(ctypes.byref(s), L.stream()), "fit prepare targets")
                 s.gt_cached = 1
             self._state = s
         return self._state
+
+    @property
+    def deterministic(self):
+        return self._deterministic
+
+    @deterministic.setter
+    def deterministic(self, on):
+        # (the state word is part of the graph key: iteration() re-captures its graphs after a change)
+        self._deterministic = bool(on)
+        if getattr(self, "_state", None) is not None:
+            self._state.flags = GFL_FIT_DETERMINISTIC if self._deterministic else 0
 
     # -------------------------------------------------------------------- calls
     def snapshot_ring(self, rows):

@@ -12,6 +12,8 @@ Gradients provided (the ones the reference consumes):
 project_point -> xyz, extr; compute_cov3d -> scale, rotate;
 ewa_project -> xyz, cov3d, extr; alpha_blending -> uv, conic, opacity, feature.
 """
+import warnings
+
 import torch
 
 from . import _lib as L
@@ -208,6 +210,15 @@ class _Blend(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_out):
+        if torch.are_deterministic_algorithms_enabled():
+            # (per-splat gradients are added with global float atomics, in arrival order: torch's contract for such an op)
+            msg = ("gflow_amd.msplat.alpha_blending backward does not have a deterministic implementation, but you set "
+                   "'torch.use_deterministic_algorithms(True)'.  The fused operator (gflow_amd.render.render) and the fused "
+                   "fit (fit_clip(fused=True)) have one.")
+            if torch.is_deterministic_algorithms_warn_only_enabled():
+                warnings.warn(msg)
+            else:
+                raise RuntimeError(msg)
         lib = L.load()
         uv, conic, opacity, feature, ids, tile_range, final_T, n_contrib = ctx.saved_tensors
         bg, W, H = ctx.meta

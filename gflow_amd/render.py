@@ -43,6 +43,8 @@ def _checkout(W, H, n, dev):
     eng.ensure_capacity(n)
     if getattr(eng, "pad2", None) is None or eng.pad2.shape[0] < eng.cap:
         eng.pad2 = torch.zeros(eng.cap, 2, dtype=torch.float32, device=eng.dev)
+    # the deterministic mode follows torch's switch at the time of the forward (the backward reads the same state word)
+    eng.deterministic = torch.are_deterministic_algorithms_enabled()
     eng.busy = True
     eng.owner = object()
     return eng, eng.owner
@@ -147,7 +149,9 @@ def render(gaussians, camera, bg=0.0):
     scale (N,3), rotate (N,4, unit, wxyz), opacity (N,1), rgb (N,3); camera: dict with intr (4,), extr (3,4),
     W, H.  Returns dict(rgb (3,H,W), depth_map (1,H,W), uv (N,2), depth (N,1)) -- what
     render_multiple(input_group, ["rgb", "uv", "depth", "depth_map"]) returns (render.py:6-108), with gradients to
-    the five attributes and to extr."""
+    the five attributes and to extr.
+    Under torch.use_deterministic_algorithms(True) the call runs in the library's deterministic mode (GFL_FIT_DETERMINISTIC,
+    include/gflow_hip.h): forward and backward give bit-identical results for identical inputs."""
     L.need_device(gaussians["xyz"])
     rgb, depth_map, uv, depth = _FusedRender.apply(
         gaussians["xyz"], gaussians["scale"], gaussians["rotate"], gaussians["opacity"], gaussians["rgb"],

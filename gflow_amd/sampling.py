@@ -62,16 +62,28 @@ def texture_probability_device(gt_image):
     return mag / mag.sum()
 
 
-def complex_texture_sampling_device(gt_image, gt_depth, num_points, generator=None):
+def cdf_device(weights, deterministic=False):
+    """Inclusive CDF of the flattened weights as float64 on the device: torch.cumsum, or -- deterministic mode -- the library's
+    scan (gfl_scan_f64: a fold order fixed by the length, the same bits on every call; torch classes its cumsum on the
+    device as nondeterministic and refuses it under torch.use_deterministic_algorithms)."""
+    flat = weights.flatten().double()
+    if deterministic:
+        from . import _lib
+        return _lib.scan_f64(flat)
+    return torch.cumsum(flat, 0)
+
+
+def complex_texture_sampling_device(gt_image, gt_depth, num_points, generator=None, deterministic=False):
     """complex_texture_sampling without the host round trip (the image goes to the host, 410 000 probabilities through
     np.random.choice and five arrays back: ~25 ms per clip on the fit's critical path): the same distribution, drawn
     by inverse-CDF lookup on the device.  gt_image (H,W,3), gt_depth (H,W,1) on the device.  Returns DEVICE tensors
     xys (n,2) int64 (x, y), depths (n,1), scales_norm (n,) float64, rgbs (n,3) float32.  (No ``mask`` / ``drop_to``:
-    those make the count data dependent; callers that pass them use the host version.)"""
+    those make the count data dependent; callers that pass them use the host version.)  ``deterministic``: the CDF from
+    cdf_device's deterministic scan."""
     H, W = gt_image.shape[:2]
     prob = texture_probability_device(gt_image)
     flat = prob.flatten()
-    cdf = torch.cumsum(flat, 0)
+    cdf = cdf_device(flat, deterministic)
     u = torch.rand(num_points, generator=generator, device=gt_image.device, dtype=torch.float64) * cdf[-1]
     pts = torch.searchsorted(cdf, u, right=True).clamp_(max=flat.numel() - 1)
     ys, xs = pts // W, pts % W

@@ -28,6 +28,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _lib as L
 from . import geometry, losses, msplat
 from . import render as render_mod
 from .optim import Adam, LinearLR
@@ -209,11 +210,18 @@ def _within(uv, W, H):
 
 class SimpleGaussian:
     def __init__(self, gt_image, gt_depth=None, gt_flow=None, num_points=100000, background="black",
-                 device=None, log_dir=None, seed=None, fused=True):
+                 device=None, log_dir=None, seed=None, fused=True, deterministic=None):
         """``fused=True`` (default) runs each iteration as one call into the native library
         (gflow_amd/fused.py); ``fused=False`` composes the msplat-compatible autograd operators
-        the way the reference does (slower, same results)."""
+        the way the reference does (slower, same results).
+        ``deterministic``: bit-identical fits for identical inputs and seed (the library's deterministic mode,
+        include/gflow_hip.h: GFL_FIT_DETERMINISTIC, and deterministic CDFs for the initial and the densification draws);
+        None follows torch.are_deterministic_algorithms_enabled().  Fused path only."""
         self.fused = bool(fused)
+        self.deterministic = L.resolve_deterministic(deterministic)
+        if self.deterministic and not self.fused and deterministic is not None:
+            raise ValueError("SimpleGaussian(deterministic=True) needs fused=True: the operator path's alpha_blending "
+                             "backward has no deterministic implementation")
         self.async_snapshots = True      # snapshots composed on a side stream from a copy of the forward's state (make_stepper)
         self.exact_snapshots = True      # iterations whose forward is looked at are never void or behind (make_stepper: one_iteration)
         self.cu_count = 0                # compute units the stream this trainer is driven on may use (0: the device): FitEngine(cu_count=)
@@ -313,7 +321,8 @@ class SimpleGaussian:
             from .sampling import complex_texture_sampling_device
             img = gt_image.to(self.device)
             self.gt_depth = gt_depth.float().to(self.device)
-            xys, depths, scales, rgbs = complex_texture_sampling_device(img, self.gt_depth, num_points, generator=self.gen)
+            xys, depths, scales, rgbs = complex_texture_sampling_device(img, self.gt_depth, num_points, generator=self.gen,
+                                                                        deterministic=self.deterministic)
             n = xys.shape[0]
             xys, depths = xys.float(), depths.float()
             scales = (scales * (depths / depths.min()).squeeze(1).double()).float()
@@ -556,7 +565,7 @@ class SimpleGaussian:
         from .fused import FitEngine
         if self.engine is None:
             self.engine = FitEngine(self.W, self.H, max(8 * int(self.num_points), 2 * n, 65536), self.device, bg=self.bg,
-                                    cu_count=self.cu_count)
+                                    cu_count=self.cu_count, deterministic=self.deterministic)
         self.engine.ensure_capacity(n)
         return self.engine
 
@@ -1035,7 +1044,7 @@ class SimpleGaussian:
             else:
                 self._snap_stream = torch.cuda.Stream(device=dev)
             aux = self._snap_aux = FitEngine(self.W, self.H, max(eng.cap, n), dev, K_cap=eng.K_cap, bg=self.bg,
-                                                  cu_count=self.cu_count)
+                                                  cu_count=self.cu_count, deterministic=self.deterministic)
             self._snap_done = None
         side = self._snap_stream
         if self._snap_done is not None:
@@ -1062,7 +1071,7 @@ class SimpleGaussian:
         aux = getattr(self, "_aux", None)
         if aux is None or aux.cap < n:
             aux = self._aux = FitEngine(self.W, self.H, max(eng.cap, n), self.device, bg=self.bg,
-                                    cu_count=self.cu_count)
+                                    cu_count=self.cu_count, deterministic=self.deterministic)
         aux.set_count(n)
         aux.pose.copy_(eng.pose)
         aux.intr.copy_(eng.intr)
@@ -1084,7 +1093,7 @@ class SimpleGaussian:
         aux = getattr(self, "_aux", None)
         if aux is None or aux.cap < n:
             aux = self._aux = FitEngine(self.W, self.H, max(eng.cap, n), self.device, bg=self.bg,
-                                    cu_count=self.cu_count)
+                                    cu_count=self.cu_count, deterministic=self.deterministic)
         aux.set_count(n)
         aux.pose.copy_(eng.pose)
         aux.intr.copy_(eng.intr)
@@ -1161,8 +1170,9 @@ class SimpleGaussian:
     def sample_pixels(self, weights, count):
         """``count`` independent draws (with replacement) of flat pixel indices with probability weights / sum --
         np.random.choice(H*W, size, p) of trainer.py:905 -- by inverse-CDF lookup on the device (torch.multinomial
-        over 4e5 categories took ~25 ms)."""
-        cdf = torch.cumsum(weights.flatten().double(), 0)
+        over 4e5 categories took ~25 ms).  The deterministic mode forms the CDF with the library's scan."""
+        from .sampling import cdf_device
+        cdf = cdf_device(weights, self.deterministic)
         u = torch.rand(count, generator=self.gen, device=self.device, dtype=torch.float64) * cdf[-1]
         return torch.searchsorted(cdf, u, right=True).clamp_(max=cdf.numel() - 1)
 

@@ -101,8 +101,9 @@ typedef enum gfl_status {
  * workspace is smaller.  301: gfl_fit_iteration_snapshot.  302: the tile sorts no longer fill a table of list positions
  * (gfl_tile_sort_with_slots is gone, gfl_tile_sort_ordered / _reserved lost their rec / slot_inv / slot_pool arguments): the
  * per-splat launch finds its pair rows without one.  303: GFL_PIXEL_CENTER, gfl_constants_n.  304: gfl_fit_state.cu_count.
+ * 305: gfl_fit_state.flags (was reserved_) and GFL_FIT_DETERMINISTIC, gfl_scan_f64.
  * A binding checks gfl_version() >= GFL_VERSION of the header it was written for. */
-#define GFL_VERSION 304
+#define GFL_VERSION 305
 int gfl_version(void);
 /* out[10] = TILE, NEAREST, EXTENT, FOV_CLAMP, LOWPASS, EIG_FLOOR, RADIUS_SIGMA, ALPHA_MIN, ALPHA_MAX, T_MIN of this build */
 int gfl_constants(float* out10);
@@ -317,8 +318,24 @@ typedef struct gfl_fit_state {
                                                  * side by side on one device, each on its share of every XCD: gflow_amd/fit_video.py)
                                                  * says so here, and grids and queues are sized for that share.  Fixed for the life
                                                  * of the state's workspace (the queues in it are built for this many). */
-    int32_t reserved_;
+    int32_t flags;                              /* 305: GFL_FIT_* bits below; 0 = the default mode.  Any other bit: GFL_ERR_INVALID */
 } gfl_fit_state;
+
+/* Deterministic mode (305).  With GFL_FIT_DETERMINISTIC in gfl_fit_state.flags, every launch of gfl_fit_* and gfl_render_*
+ * on the state reduces in an order fixed by its inputs, so the same inputs give BIT-IDENTICAL outputs -- render, final_T,
+ * n_contrib, the sorted lists, parameters, Adam moments, pose and depth affine, loss sums, snapshots, d_params / d_extr --
+ * run after run, in one process or several, launched eagerly or replayed from a captured graph, on a stream of its own or
+ * beside other fits.  What changes against the default mode:
+ *   - the backward blend's four waves leave their per-splat sums in one LDS row per 8x8 block with plain stores and the
+ *     tile folds the four rows in block order (the default adds them into one row with LDS float atomics, in arrival order);
+ *   - the tile schedulers order tiles of equal quantised weight by tile index (the default: by LDS-atomic arrival), so the
+ *     choice of the tiles that are walked in segments (backward) or on four CUs (forward) -- which changes the last bits of T,
+ *     the render and the gradients -- is a function of the weights alone.
+ * The contract holds for the same library build, device model, cu_count and environment switches.  It does NOT promise
+ * equality with the default mode, across different cu_count values or CU partitions (the number of queues decides which
+ * tiles are split), across GFL_FWD_SPLIT_MIN values, or across ROCm versions.  gfl_render_fwd in this mode also drops the state's
+ * scheduler feedback first, so that a render does not depend on what the state rendered before.  Cost: see INTEGRATION.md. */
+#define GFL_FIT_DETERMINISTIC 1
 
 typedef struct gfl_fit_hyper {
     float bg, nearest, extent;
@@ -461,6 +478,14 @@ int gfl_selftest_block_mask(const float* rec, int n, int x0, int y0, int box, in
  * negative gfl_status (GFL_ERR_WORKSPACE: cap_vertices too small; 2 n + 8 always suffices). */
 int gfl_concave_hull(const double* points_xy, int n, double concavity, double length_threshold, double* ring_xy,
                      int cap_vertices);
+
+/* ---- deterministic inclusive scan of doubles (305) -----------------------------------------------------------------
+ * out[i] = in[0] + ... + in[i], summed in an order that depends on n alone (blocks of GFL_SCAN_CHUNK values, a fixed
+ * fold inside a block and over the blocks in front of it): the same bits on every call, whatever the device or stream.
+ * in and out may not overlap.  workspace: gfl_scan_f64_workspace_bytes(n). */
+#define GFL_SCAN_CHUNK 2048
+size_t gfl_scan_f64_workspace_bytes(int n);
+int gfl_scan_f64(const double* in, int n, double* out, void* workspace, size_t workspace_bytes, gfl_stream_t stream);
 
 /* sizeof(gfl_fit_state), sizeof(gfl_fit_hyper): lets an FFI binding verify its struct mirrors */
 int gfl_abi_sizes(int* sizeof_fit_state, int* sizeof_fit_hyper);
