@@ -23,7 +23,7 @@ _lib = None
 
 c_void_p, c_int, c_float, c_size_t, c_int64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_int64
 
-MIN_VERSION = 305          # GFL_VERSION of the include/gflow_hip.h this binding mirrors (gfl_fit_state.flags, gfl_scan_f64)
+MIN_VERSION = 306          # GFL_VERSION of the include/gflow_hip.h this binding mirrors (gfl_track_anchor, gfl_track_frame)
 
 # name -> (restype, argtypes); mirrors include/gflow_hip.h one to one
 _P = c_void_p
@@ -81,6 +81,10 @@ SIGNATURES = {
     "gfl_concave_hull": (c_int, [_P, c_int, ctypes.c_double, ctypes.c_double, _P, c_int]),
     "gfl_scan_f64_workspace_bytes": (c_size_t, [c_int]),
     "gfl_scan_f64": (c_int, [_P, c_int, _P, _P, c_size_t, _P]),
+    "gfl_track_anchor_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "gfl_track_anchor": (c_int, [_P, c_int, c_int, _P, c_int, _P, _P, _P, c_size_t, _P]),
+    "gfl_track_frame": (c_int, [_P, c_int, _P, c_int, c_int, _P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_float, _P, _P,
+                                _P]),
     "gfl_abi_sizes": (c_int, [_P, _P]),
     "gfl_profile_enable": (c_int, [ctypes.c_uint]),
     "gfl_profile_read": (c_int, [_P, _P, c_int]),

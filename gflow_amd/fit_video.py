@@ -83,6 +83,31 @@ def reduce_metrics(local, wall_seconds, dist=None, device="cpu", rank=0, world=1
     return out
 
 
+TAPVID_KEYS = ("occlusion_accuracy", "average_jaccard", "average_pts_within_thresh")
+
+
+def reduce_tapvid(preds, gts, n_frames, dropped, dist=None, device="cpu"):
+    """The "tapvid" block of the JSON line: every clip's TAP-Vid score (tracking.evaluate), averaged over the clips as
+    benchmark.py averages its videos; over ranks by ONE more small all-reduce(SUM) of (the three sums, clips, queries
+    dropped)."""
+    from . import tracking as TK
+    sums = [0.0] * len(TAPVID_KEYS)
+    for ci, p in preds.items():
+        pts, occ, h, w = gts[ci]
+        m = TK.evaluate(p, pts, occ, h, w, n_frames[ci])
+        for k, key in enumerate(TAPVID_KEYS):
+            sums[k] += m[key]
+    vec = torch.tensor(sums + [float(len(preds)), float(dropped)], dtype=torch.float64, device=device)
+    if dist is not None and dist.is_initialized():
+        dist.all_reduce(vec, op=dist.ReduceOp.SUM)
+    v = vec.tolist()
+    clips = v[len(TAPVID_KEYS)]
+    out = {k: v[i] / clips if clips else float("nan") for i, k in enumerate(TAPVID_KEYS)}
+    out["clips"] = int(clips)
+    out["queries_dropped"] = int(v[len(TAPVID_KEYS) + 1])
+    return out
+
+
 _FIT_STREAMS = {}
 
 
@@ -190,7 +215,7 @@ def stage_kwargs(c, frames, i, stage):
 
 
 def fit_clip(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, log=None, load_extr=True, keep=None,
-             async_snapshots=None, deterministic=None):
+             async_snapshots=None, deterministic=None, track_queries=None):
     """Fit one clip; returns the metrics dict of this clip (PSNR summed over its frames; with ``cfg["traj_num"]`` > 0 also
     ``"traj"``: the per-frame trajectory images and seed projections, host arrays -- what the reference's frame loop collects in
     ``frames_sequence_traj / frames_sequence_traj_upon / sequence_traj``).
@@ -201,13 +226,17 @@ def fit_clip(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, 
     trajectory images and seed projections as they left for the host (``keep["traj"]``).
     ``deterministic``: the same frames, cfg and seed give the same metrics, parameters and trajectory outputs bit for bit
     (SimpleGaussian(deterministic=)); None follows torch.are_deterministic_algorithms_enabled().  Needs
-    ``fused=True``."""
+    ``fused=True``.
+    ``track_queries``: rows [t, y, x] (pixels) of points to track (gflow_amd.tracking.Tracker; ValueError unless every t is
+    a frame of the clip): every query is anchored at the end of its frame and tracked, with an occlusion flag, at the end of
+    every later one; the dict then has ``"tracks"`` (Tracker.result()).  ``keep["record_track_inputs"] = True``: the
+    per-frame (uv, depth, depth_map) the tracker read, cloned, in ``keep["track_inputs"]``."""
     if deterministic and not fused:
         raise ValueError("fit_clip(deterministic=True) needs fused=True: the operator path's alpha_blending backward has no "
                          "deterministic implementation")
     dev_ = torch.device(device)
     g = fit_clip_steps(frames, device, cfg=cfg, seed=seed, snapshot_interval=snapshot_interval, fused=fused, log=log,
-                       load_extr=load_extr, chunk=None, keep=keep, deterministic=deterministic,
+                       load_extr=load_extr, chunk=None, keep=keep, deterministic=deterministic, track_queries=track_queries,
                        **({} if async_snapshots is None else {"async_snapshots": async_snapshots}))
 
     def drive():
@@ -234,7 +263,7 @@ def fit_clip(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, 
 
 
 def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, log=None, load_extr=True, chunk=None,
-                   async_snapshots=True, keep=None, cu_count=0, deterministic=None):
+                   async_snapshots=True, keep=None, cu_count=0, deterministic=None, track_queries=None):
     """fit_clip as a generator: yields after every ``chunk`` iterations of a stage (None: never) and returns the metrics
     dict.  The caller owns the stream the work is enqueued on (fit_clips_concurrent gives every clip its own)."""
     from .trainer import SimpleGaussian
@@ -243,6 +272,10 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
     if any(isinstance(v, torch.Tensor) and not v.is_cuda for k, v in frames[0].items() if k != "extr"):
         frames = upload_clip(frames, device)         # (bench.py uploads before its clock starts: "inputs resident in HBM")
     f0 = frames[0]
+    tracker = None
+    if track_queries is not None:
+        from .tracking import Tracker
+        tracker = Tracker(track_queries, len(frames), device)        # (ValueError before anything is fitted)
     tr = SimpleGaussian(f0["image"], f0["depth"], num_points=c["num_points"], background=c["background"],
                         device=device, seed=seed, fused=fused, deterministic=deterministic)
     tr.async_snapshots = bool(async_snapshots)       # (trainer.py: snapshots composed beside the next iterations, or behind theirs)
@@ -274,13 +307,41 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
         with torch.no_grad():
             xyz_now = tr.get_attribute("xyz")[traj_index_t].detach().float().clone()
             extr_now = tr.get_extr().detach().clone()
+            aux = None
             if tr.fused and tr.engine is not None and tr.engine.N == tr.current_pts_num():
                 rgb_u8 = tr._render_scene_fused()[0].clone()
+                aux = tr._aux
             else:
                 from . import render as render_mod
                 rgb_u8 = render_mod.render2img_device(render_mod.render_multiple(tr._input_group(detach=True), ["rgb"])["rgb"])
             tr.rasterisations_done += 1
         traj_rec.append((xyz_now, extr_now, rgb_u8))
+        return aux
+
+    def record_tracks(i, shared):
+        # benchmark.py:98-139 for frame i, on the frame's final state: the uv / depth / depth_map of one forward -- the one
+        # record_trajectories has just run on the second engine (``shared``), or one of its own -- go to the tracker's two
+        # launches; nothing is read back
+        with torch.no_grad():
+            if tr.fused and tr.engine is not None and tr.engine.N == tr.current_pts_num():
+                aux = shared
+                if aux is None:
+                    aux = tr._aux_forward()
+                    aux.watch_overflow()
+                    tr.rasterisations_done += 1
+                from .fused import REC
+                n = aux.N
+                uv, uv_stride, depth, depth_stride, dm = aux.rec[:n, 0:2], REC, aux.rec[:n, 9], REC, aux.render[3]
+            else:
+                from . import render as render_mod
+                o = render_mod.render_multiple(tr._input_group(detach=True), ["uv", "depth", "depth_map"])
+                uv, depth = o["uv"].float().contiguous(), o["depth"].float().reshape(-1).contiguous()
+                dm = o["depth_map"].float().reshape(tr.H, tr.W).contiguous()
+                uv_stride, depth_stride = 2, 1
+                tr.rasterisations_done += 1
+            tracker.frame(i, uv, uv_stride, depth, depth_stride, dm)
+            if keep is not None and keep.get("record_track_inputs"):
+                keep.setdefault("track_inputs", []).append((uv.clone(), depth.clone(), dm.clone()))
 
     def draw_trajectories():
         from . import msplat
@@ -303,7 +364,9 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
     if traj:
         traj_index, split_interval = select_traj_seeds(tr, int(c["traj_num"]), int(c["traj_offset"]))
         traj_index_t = torch.as_tensor(traj_index, device=tr.device).long()
-        record_trajectories()
+        shared = record_trajectories()
+    if tracker is not None:
+        record_tracks(0, shared if traj else None)
     # (PSNR stays on the device and is read ONCE at the end of the clip: a float() per frame drained the queue between
     #  two frames; with a log callback the caller asked for the numbers as they come)
     psnr_sum = tr.psnr().double()
@@ -317,8 +380,9 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
             yield from tr.train_steps(**stage_kwargs(c, frames, i, "camera"), **common)
         if c["iterations_after"] > 0:                    # fit_video.py:288-315
             yield from tr.train_steps(**stage_kwargs(c, frames, i, "joint"), **common)
-        if traj:
-            record_trajectories()
+        shared = record_trajectories() if traj else None
+        if tracker is not None:
+            record_tracks(i, shared)
         p = tr.psnr()
         psnr_sum = psnr_sum + p.double()
         if keep is not None:
@@ -353,15 +417,18 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
         # (fit_video.py:226-238, 335-349): images (frames, 2, H, W, 3) uint8 [trajectories alone, upon the render],
         # uv (frames, seeds, 2), index, split_interval.  Not a number: callers that sum the dicts skip it (NUMERIC_KEYS)
         out["traj"] = traj_out
+    if tracker is not None:
+        out["tracks"] = tracker.result()              # (one copy to the host; not a number either)
     return out
 
 
-# the keys of fit_clip's dict that are per-clip numbers (sums over clips make sense); "traj" is the trajectory output
+# the keys of fit_clip's dict that are per-clip numbers (sums over clips make sense); "traj" is the trajectory output,
+# "tracks" the tracker's
 NUMERIC_KEYS = ("psnr_sum", "frames", "iterations", "rasterisations", "clips", "splats_final", "void_iterations")
 
 
 def fit_clips_concurrent(clips, device, cfg=None, seeds=None, snapshot_interval=0, chunk=32, partition=False,
-                         deterministic=None):
+                         deterministic=None, track_queries=None):
     """Fit several clips AT THE SAME TIME on ONE device, in one host thread: every clip has its own trainer, engine and
     STREAM, and the clips take turns enqueueing ``chunk`` iterations each (fit_clip_steps), so their graph launches
     interleave on the device.  One fit leaves the chip partly idle -- its kernels are a chain of dependent launches,
@@ -377,8 +444,11 @@ def fit_clips_concurrent(clips, device, cfg=None, seeds=None, snapshot_interval=
     (gfl_fit_state.cu_count) -- the clips then run SIDE BY SIDE instead of taking turns on every CU.  Results do not depend
     on it (the schedule never enters a result).  Measured in bench.py's ``clips_per_gpu`` table.
     ``deterministic`` (None: torch's switch): every clip's result is bit for bit that of fit_clip(..., deterministic=True)
-    with the same seed -- without ``partition``, which changes the number of tile queues (include/gflow_hip.h)."""
+    with the same seed -- without ``partition``, which changes the number of tile queues (include/gflow_hip.h).
+    ``track_queries``: None, or one entry (fit_clip's ``track_queries``, or None) per clip."""
     n = len(clips)
+    if track_queries is not None and len(track_queries) != n:
+        raise ValueError("fit_clips_concurrent: track_queries needs one entry per clip")
     seeds = list(range(n)) if seeds is None else seeds
     dev = torch.device(device)
     if dev.index is None:
@@ -396,7 +466,8 @@ def fit_clips_concurrent(clips, device, cfg=None, seeds=None, snapshot_interval=
     # (a lone fit takes its snapshots on a side stream; several fits already fill each other's gaps, and a side stream + shadow
     #  engine per clip cost them more than they give)
     gens = [fit_clip_steps(clips[i], dev, cfg, seed=seeds[i], snapshot_interval=snapshot_interval, chunk=chunk,
-                           async_snapshots=n == 1, cu_count=shares[i][1] if shares else 0, deterministic=deterministic)
+                           async_snapshots=n == 1, cu_count=shares[i][1] if shares else 0, deterministic=deterministic,
+                           track_queries=None if track_queries is None else track_queries[i])
             for i in range(n)]
     results = [None] * n
     live = list(range(n))
@@ -434,6 +505,10 @@ def main(argv=None):
     ap.add_argument("--resize", type=int, default=None, help="shorter image side after loading a --sequence")
     ap.add_argument("--deterministic", action="store_true",
                     help="bit-identical results for identical inputs (the library's deterministic mode, INTEGRATION.md)")
+    ap.add_argument("--track", action="store_true",
+                    help="track the first-visible query points of each clip's tracking.pkl (synthetic clips: their "
+                         "make_clip_tracks) through the fit and score them with TAP-Vid (a \"tapvid\" block in the line)")
+    ap.add_argument("--track-out", default=None, help="with --track: write each clip's predicted tracks to DIR/clip_<i>.npz")
     args = ap.parse_args(argv)
     det = True if args.deterministic else None
     from . import synthetic as S
@@ -478,25 +553,53 @@ def main(argv=None):
             clips[ci] = gio.load_sequence(args.sequence[ci], resize=args.resize)
         else:
             clips[ci] = upload_clip(S.make_clip(lengths[ci], args.height, args.width, seed=ci, device=dev), dev)
+    # point tracking: the ground truth of every clip, its first-visible queries (those whose frame is not fitted: dropped)
+    gts, queries, dropped = {}, {}, 0
+    if args.track:
+        from . import tracking as TK
+        for ci in mine:
+            h, w = clips[ci][0]["image"].shape[:2]
+            if args.sequence:
+                pts, occ = TK.read_tapvid_pickle(os.path.join(args.sequence[ci], "tracking.pkl"))
+            else:
+                g = S.make_clip_tracks(lengths[ci], args.height, args.width, seed=ci)
+                pts, occ = g["points"].astype("float32"), g["occluded"]
+            q = TK.first_visible_queries(pts, occ, h, w)
+            keep = q[:, 0] < len(clips[ci])
+            dropped += int((~keep).sum())
+            gts[ci] = (pts[keep], occ[keep], h, w)
+            queries[ci] = q[keep]
     t_load = time.perf_counter() - t_load
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     c = max(1, args.clips_per_gpu)
     order = sorted(clips, key=lambda j: (-lengths[j], j))          # (clips of similar length share the GPU)
+    preds = {}
     for g0 in range(0, len(order), c):
         group = order[g0:g0 + c]
         if len(group) == 1:
             ci = group[0]
-            res = [fit_clip(clips[ci], dev, cfg, seed=ci, deterministic=det,
+            res = [fit_clip(clips[ci], dev, cfg, seed=ci, deterministic=det, track_queries=queries.get(ci),
                             log=(lambda s, ci=ci: print(f"[rank {rank} clip {ci}] {s}")) if args.verbose else None)]
         else:
-            res = fit_clips_concurrent([clips[ci] for ci in group], dev, cfg, seeds=group, deterministic=det)
-        for m in res:
+            res = fit_clips_concurrent([clips[ci] for ci in group], dev, cfg, seeds=group, deterministic=det,
+                                       track_queries=[queries.get(ci) for ci in group] if args.track else None)
+        for ci, m in zip(group, res):
             for k in METRIC_NAMES:
                 local[k] += m[k]
+            if "tracks" in m:
+                preds[ci] = m["tracks"]
     torch.cuda.synchronize()
     out = reduce_metrics(local, time.perf_counter() - t0, dist, torch.device("cpu") if (world > 1 and shared) else dev,
                          rank=rank, world=world)
+    if args.track:
+        out["tapvid"] = reduce_tapvid(preds, gts, {ci: len(clips[ci]) for ci in clips}, dropped, dist,
+                                      torch.device("cpu") if (world > 1 and shared) else dev)
+        if args.track_out:
+            import numpy as np
+            os.makedirs(args.track_out, exist_ok=True)
+            for ci, p in preds.items():
+                np.savez(os.path.join(args.track_out, f"clip_{ci}.npz"), queries=queries[ci], **p)
     if rank == 0:
         out["frames_per_s"] = out["frames"] / out["wall_s"]
         out["iterations_per_s"] = out["iterations"] / out["wall_s"]

@@ -193,3 +193,50 @@ def init_splats(frame, num_points, seed=0, device="cpu", grown=False):
     rotate = torch.nn.functional.normalize(torch.rand(xyz.shape[0], 4, generator=g2))
     out = dict(xyz=xyz, scale=torch.abs(sc), rotate=rotate, opacity=opacity, rgb=rgb, intr=intr, extr=extr)
     return {k: v.contiguous().to(device) for k, v in out.items()}
+
+
+def make_clip_tracks(n_frames, H=480, W=854, seed=0, cam_step=0.01, n_queries=256, query_seed=0):
+    """Ground-truth point tracks of the clip ``make_clip(n_frames, H, W, seed, cam_step=cam_step)`` renders, in the layout
+    of a TAP-Vid ``tracking.pkl``: dict(points (Q, T, 2) float64, (x / W, y / H); occluded (Q, T) bool), plus where each
+    track was sampled (``sample_frame`` (Q,) int64, ``on_disc`` (Q,) bool).
+    A point is drawn at a pixel (u, v) of a frame k drawn over the whole clip.  On the surface it is the point with the
+    surface parameter a = surface_param(u, v, k): frame j sees it at (a - fx c j / D0(a, v), v), hidden while the disc
+    covers it.  On the disc it keeps its offset from the disc's centre.  Every point is occluded outside
+    [0, W - 1] x [0, H - 1].  Samples lie at least 3 px from the image border and from the disc's rim in their frame."""
+    sc = _Scene(H, W, seed, cam_step=cam_step)
+    rng = np.random.default_rng(query_seed)
+    margin = 3.0
+    ks, us, vs = [], [], []
+    while len(ks) < n_queries:
+        m = 4 * n_queries
+        k = rng.integers(0, n_frames, m)
+        u = rng.uniform(margin, W - 1 - margin, m)
+        v = rng.uniform(margin, H - 1 - margin, m)
+        cen = np.array([sc.obj_centre(int(kk)) for kk in k])
+        dist = np.hypot(u - cen[:, 0], v - cen[:, 1])
+        ok = np.abs(dist - sc.obj_r_px) >= margin + 0.5                    # (the soft rim reaches half a pixel out)
+        ks += k[ok].tolist()
+        us += u[ok].tolist()
+        vs += v[ok].tolist()
+    k = np.asarray(ks[:n_queries], dtype=np.int64)
+    u = torch.tensor(us[:n_queries], dtype=torch.float64)
+    v = torch.tensor(vs[:n_queries], dtype=torch.float64)
+    cen_k = torch.tensor([sc.obj_centre(int(kk)) for kk in k], dtype=torch.float64)
+    on_disc = (torch.hypot(u - cen_k[:, 0], v - cen_k[:, 1]) < sc.obj_r_px).numpy()
+    a = torch.stack([sc.surface_param(u[i:i + 1], v[i:i + 1], int(k[i]))[0] for i in range(n_queries)])
+    da = sc.depth0(a, v)
+    off = torch.stack([u - cen_k[:, 0], v - cen_k[:, 1]], dim=-1)
+    pts = np.empty((n_queries, n_frames, 2), dtype=np.float64)
+    occ = np.empty((n_queries, n_frames), dtype=bool)
+    disc = torch.from_numpy(on_disc)
+    for j in range(n_frames):
+        cj = torch.tensor(sc.obj_centre(j), dtype=torch.float64)
+        us_j = a - sc.f * sc.cam_step * j / da
+        x = torch.where(disc, cj[0] + off[:, 0], us_j)
+        y = torch.where(disc, cj[1] + off[:, 1], v)
+        covered = torch.hypot(x - cj[0], y - cj[1]) < sc.obj_r_px
+        outside = (x < 0) | (x > W - 1) | (y < 0) | (y > H - 1)
+        occ[:, j] = (outside | (~disc & covered)).numpy()
+        pts[:, j, 0] = (x / W).numpy()
+        pts[:, j, 1] = (y / H).numpy()
+    return dict(points=pts, occluded=occ, sample_frame=k, on_disc=on_disc)

@@ -1065,6 +1065,15 @@ class SimpleGaussian:
         """(3, H, W, 3) uint8 on the device: rgb, depth colour, centre blobs of the CURRENT splats and camera (what
         render_multiple(["rgb", "center", "depth_map_color"]) + render2img give, trainer.py:765-777) through the fused
         kernels on the second engine: one forward, one gfl_fit_snapshot; nothing is read back."""
+        aux = self._aux_forward()
+        out = aux.snapshot()
+        aux.watch_overflow()
+        return out
+
+    def _aux_forward(self):
+        """One forward of the CURRENT splats and camera on the second engine; returns it, its records (``rec``: uv in
+        columns 0:2, depth in column 9) and ``render`` (rgb, depth_map) holding the result.  The caller watches its
+        overflow flag."""
         from .fused import FitEngine
         eng = self.engine
         n = eng.N
@@ -1078,9 +1087,7 @@ class SimpleGaussian:
         aux.hp.bg = self.bg
         aux.params[:n].copy_(eng.params[:n])
         aux.forward()
-        out = aux.snapshot()
-        aux.watch_overflow()
-        return out
+        return aux
 
     def _render_parts_fused(self):
         """(2, 3, H, W, 3) uint8 on the device: [still splats, moving splats] x [rgb, depth colour, centre blobs] of the

@@ -101,9 +101,9 @@ typedef enum gfl_status {
  * workspace is smaller.  301: gfl_fit_iteration_snapshot.  302: the tile sorts no longer fill a table of list positions
  * (gfl_tile_sort_with_slots is gone, gfl_tile_sort_ordered / _reserved lost their rec / slot_inv / slot_pool arguments): the
  * per-splat launch finds its pair rows without one.  303: GFL_PIXEL_CENTER, gfl_constants_n.  304: gfl_fit_state.cu_count.
- * 305: gfl_fit_state.flags (was reserved_) and GFL_FIT_DETERMINISTIC, gfl_scan_f64.
+ * 305: gfl_fit_state.flags (was reserved_) and GFL_FIT_DETERMINISTIC, gfl_scan_f64.  306: gfl_track_anchor, gfl_track_frame.
  * A binding checks gfl_version() >= GFL_VERSION of the header it was written for. */
-#define GFL_VERSION 305
+#define GFL_VERSION 306
 int gfl_version(void);
 /* out[10] = TILE, NEAREST, EXTENT, FOV_CLAMP, LOWPASS, EIG_FLOOR, RADIUS_SIGMA, ALPHA_MIN, ALPHA_MAX, T_MIN of this build */
 int gfl_constants(float* out10);
@@ -486,6 +486,27 @@ int gfl_concave_hull(const double* points_xy, int n, double concavity, double le
 #define GFL_SCAN_CHUNK 2048
 size_t gfl_scan_f64_workspace_bytes(int n);
 int gfl_scan_f64(const double* in, int n, double* out, void* workspace, size_t workspace_bytes, gfl_stream_t stream);
+
+/* ---- point tracking (306; gflow_amd/tracking.py, INTEGRATION.md "Point tracking") ---------------------------------
+ * gfl_track_anchor: for each of n_new queries query_xy[i] = (x, y) (float64, pixels) the row of uv (N rows of uv_stride
+ * floats, (u, v) in the first two: fit records with stride 12, or a dense (N, 2) array) closest to it -- exactly np.argmin
+ * over the rows of (u - x)^2 + (v - y)^2 in float64, every product and the sum rounded on its own (no FMA): the lowest
+ * index among equal minima, the first NaN distance if there is one.  Writes anchor[i] (int32) and
+ * shift_xy[i] = query_xy[i] - (double)uv[anchor[i]].  Deterministic by construction (a lexicographic min over
+ * (distance, index); no atomics).  Two launches.  workspace: gfl_track_anchor_workspace_bytes(n_new, N).  N >= 1 when
+ * n_new > 0.
+ * gfl_track_frame: for each of the first n_anchored queries, with a = anchor[q] and (u, v) = uv[a]:
+ *   tracks[q][frame] = (float)((double)u + shift_xy[q].x), (float)((double)v + shift_xy[q].y)   (tracks: [Q][T][2] float32)
+ *   occluded[q][frame] = |depth_map[rint(v)][rint(u)] - depth[a * depth_stride]| > occ_threshold  (float32; [Q][T] uint8)
+ * rint rounds half to even; a rounded pixel outside [0, W) x [0, H) is occluded (1); an anchor outside [0, N) gives a NaN
+ * track, occluded.  depth_map: [H][W] (the fused forward's render plane 3).  Other frames' columns are not touched.
+ * Both: no allocation, no host synchronisation; callable on the fit's stream between graph replays. */
+size_t gfl_track_anchor_workspace_bytes(int n_new, int N);
+int gfl_track_anchor(const float* uv, int uv_stride, int N, const double* query_xy, int n_new, int32_t* anchor,
+                     double* shift_xy, void* workspace, size_t workspace_bytes, gfl_stream_t stream);
+int gfl_track_frame(const float* uv, int uv_stride, const float* depth, int depth_stride, int N, const float* depth_map,
+                    int W, int H, const int32_t* anchor, const double* shift_xy, int n_anchored, int frame, int T,
+                    float occ_threshold, float* tracks, uint8_t* occluded, gfl_stream_t stream);
 
 /* sizeof(gfl_fit_state), sizeof(gfl_fit_hyper): lets an FFI binding verify its struct mirrors */
 int gfl_abi_sizes(int* sizeof_fit_state, int* sizeof_fit_hyper);
