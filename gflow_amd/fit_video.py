@@ -234,18 +234,13 @@ def fit_clip(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, 
     if deterministic and not fused:
         raise ValueError("fit_clip(deterministic=True) needs fused=True: the operator path's alpha_blending backward has no "
                          "deterministic implementation")
+    from .trainer import run_to_end
     dev_ = torch.device(device)
     g = fit_clip_steps(frames, device, cfg=cfg, seed=seed, snapshot_interval=snapshot_interval, fused=fused, log=log,
                        load_extr=load_extr, chunk=None, keep=keep, deterministic=deterministic, track_queries=track_queries,
                        **({} if async_snapshots is None else {"async_snapshots": async_snapshots}))
 
-    def drive():
-        try:
-            while True:
-                next(g)
-        except StopIteration as e:
-            return e.value
-
+    drive = lambda: run_to_end(g)
     if dev_.type == "cuda" and torch.cuda.current_stream(dev_) == torch.cuda.default_stream(dev_):
         # Never fit on the default stream: it is HIP's legacy NULL stream, which every other (blocking) stream
         # synchronises with -- the snapshot copies on the copy stream then run BETWEEN the fit's launches instead of
@@ -308,7 +303,7 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
             xyz_now = tr.get_attribute("xyz")[traj_index_t].detach().float().clone()
             extr_now = tr.get_extr().detach().clone()
             aux = None
-            if tr.fused and tr.engine is not None and tr.engine.N == tr.current_pts_num():
+            if tr.engine_current:
                 rgb_u8 = tr._render_scene_fused()[0].clone()
                 aux = tr._aux
             else:
@@ -323,7 +318,7 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
         # record_trajectories has just run on the second engine (``shared``), or one of its own -- go to the tracker's two
         # launches; nothing is read back
         with torch.no_grad():
-            if tr.fused and tr.engine is not None and tr.engine.N == tr.current_pts_num():
+            if tr.engine_current:
                 aux = shared
                 if aux is None:
                     aux = tr._aux_forward()
@@ -396,14 +391,14 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
         # five images and the projections per frame, blocking: render2img, .cpu().numpy())
         imgs_d, uvs_d = draw_trajectories()
         if imgs_d.is_cuda:
-            from .trainer import _PINNED
-            block = _PINNED.take(imgs_d.numel())
+            from .pinned import PINNED
+            block = PINNED.take(imgs_d.numel())
             imgs_h = block[0][:imgs_d.numel()].view(imgs_d.shape)
             imgs_h.copy_(imgs_d, non_blocking=True)
             uvs_h = uvs_d.cpu()                          # (small; waits for the stream, and with it for the images above)
-            traj_out = dict(images=_PINNED.hand_out(block, [imgs_h])[0], uv=uvs_h.numpy(), index=list(traj_index),
+            traj_out = dict(images=PINNED.hand_out(block, [imgs_h])[0], uv=uvs_h.numpy(), index=list(traj_index),
                             split_interval=split_interval)
-            _PINNED.release(block)
+            PINNED.release(block)
         else:
             traj_out = dict(images=imgs_d.numpy(), uv=uvs_d.numpy(), index=list(traj_index), split_interval=split_interval)
         if keep is not None:
@@ -411,7 +406,7 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
     out = dict(psnr_sum=float(psnr_sum), frames=len(frames), iterations=tr.iterations_done,
                rasterisations=tr.rasterisations_done, clips=1, splats_final=tr.current_pts_num(),
                # iterations that stepped nothing because a tile outgrew its reserved region, and were made up for
-               void_iterations=getattr(tr.engine, "regions_outgrown", 0) if tr.engine is not None else 0)
+               void_iterations=tr.engine.regions_outgrown if tr.engine is not None else 0)
     if traj:
         # what the reference appends per frame -- frames_sequence_traj, frames_sequence_traj_upon, sequence_traj
         # (fit_video.py:226-238, 335-349): images (frames, 2, H, W, 3) uint8 [trajectories alone, upon the render],

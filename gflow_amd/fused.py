@@ -134,9 +134,18 @@ class FitEngine:
         self.gt_rgb = self.gt_depth = self.keep = None
         self.move_mask = self.foot_flags = None
         self.flow_target = self.flow_w = self.still_target = self.still_w = self.row_flags = None
-        self.cap = 0
+        self.cap = self.K_cap = 0
         self.K_cap_req = K_cap
-        self._graphs, self._graph_key = {}, None
+        self._K_grown = False          # an overflow has doubled the pair lists: _alloc never goes below that again
+        self.params = self.d_rec = self._state = None
+        self.want_d_rec = False        # allocate ``d_rec`` (an optional output) with the rows
+        self._graphs, self._graph_key, self._graph_trash = {}, None, []
+        self._reserved_sup = (None, 0)                   # (W, H, K_cap) the library was asked about, its answer (_reserved_flag)
+        self.regions_outgrown = self.pairs_grown = 0     # void iterations made up for; times the pair lists were doubled
+        self._pend_event = self._pend_host = self._ovf_event = self._ovf_host = None     # watch_pending, watch_overflow
+        self._snap_ring = self._snap_ring_done = None    # snapshot_ring / snapshot_ring_copied
+        # the image buffer of iteration(snapshot=True), snapshot()'s workspace, the stream graphs are captured on
+        self._snap_out = self._snap_ws = self._capture_stream = None
         self._launched = False
         self._reserved_N = -1          # N of the last full iteration whose last launch reserved the next one's tile regions
         self.busy = False              # checked out by the differentiable operator (gflow_amd.render)
@@ -159,35 +168,34 @@ class FitEngine:
         them where the host has just waited for the device anyway (a densification's read, a blocking look at the overflow
         words, the end of a clip)."""
         if self._graphs:
-            self.__dict__.setdefault("_graph_trash", []).append(self._graphs)
+            self._graph_trash.append(self._graphs)
             self._graphs = {}
-        if len(self.__dict__.get("_graph_trash", ())) > 256:         # (a caller that never reaches a reaping point)
+        if len(self._graph_trash) > 256:         # (a caller that never reaches a reaping point)
             self.reap_graphs()
 
     def reap_graphs(self):
         """Destroy the graphs set aside by ``_retire_graphs`` -- call where the device is idle (see there).  Under the lock,
         never while a capture runs (_GRAPH_LOCK)."""
-        trash = self.__dict__.get("_graph_trash")
-        if trash:
+        if self._graph_trash:
             with _GRAPH_LOCK:
-                for gs in trash:
+                for gs in self._graph_trash:
                     gs.clear()
             self._graph_trash = []
 
     # ------------------------------------------------------------------ storage
     def _alloc(self, cap):
         f32 = dict(dtype=torch.float32, device=self.dev)
-        old = getattr(self, "params", None)
+        old = self.params
         n = self.N
         self.cap = cap
         self.params = torch.zeros(cap, ROW, **f32)
         self.adam_m = torch.zeros(cap, ROW, **f32)
         self.adam_v = torch.zeros(cap, ROW, **f32)
         self.rec = torch.zeros(cap, REC, **f32)
-        self.d_rec = torch.zeros(cap, REC, **f32) if getattr(self, "want_d_rec", False) else None     # (an optional output)
+        self.d_rec = torch.zeros(cap, REC, **f32) if self.want_d_rec else None     # (an optional output)
         if old is not None and n:
             self.params[:n] = old[:n]
-        k_min = getattr(self, "K_cap", 0) if getattr(self, "_K_grown", False) else 0      # (never below what an overflow asked for)
+        k_min = self.K_cap if self._K_grown else 0      # (never below what an overflow asked for)
         self._alloc_pairs(max(int(self.K_cap_req) if self.K_cap_req else max(4_000_000, 8 * cap), k_min))
 
     def _alloc_pairs(self, K_cap):
@@ -296,23 +304,12 @@ class FitEngine:
     # ------------------------------------------------------------------- struct
     def state(self):
         if self._state is None:
-            p = L.ptr
             s = FitState()
             s.N, s.cap, s.W, s.H, s.K_cap = self.N, self.cap, self.W, self.H, self.K_cap
-            for name, t in (("params", self.params), ("adam_m", self.adam_m), ("adam_v", self.adam_v),
-                            ("rec", self.rec), ("d_rec", self.d_rec), ("flow_target", self.flow_target),
-                            ("flow_w", self.flow_w), ("still_target", self.still_target), ("still_w", self.still_w),
-                            ("row_flags", self.row_flags), ("pose", self.pose), ("pose_m", self.pose_m),
-                            ("pose_v", self.pose_v), ("depth_ab", self.depth_ab), ("depth_ab_m", self.ab_m),
-                            ("depth_ab_v", self.ab_v), ("intr", self.intr), ("extr", self.extr),
-                            ("d_extr", self.d_extr), ("step", self.step), ("gt_rgb", self.gt_rgb),
-                            ("gt_depth", self.gt_depth), ("keep", self.keep), ("move_mask", self.move_mask),
-                            ("foot_flags", self.foot_flags), ("render", self.render),
-                            ("final_T", self.final_T), ("n_contrib", self.n_contrib), ("d_render", self.d_render),
-                            ("err_px", self.err_px), ("sums", self.sums), ("tile_offsets", self.tile_offsets),
-                            ("ids", self.ids), ("tile_range", self.tile_range), ("overflow", self.overflow),
-                            ("workspace", self.workspace)):
-                setattr(s, name, None if t is None else t.data_ptr())
+            for name, ctype in FitState._fields_:            # every pointer field: the tensor of the same name
+                if ctype is _P:
+                    t = getattr(self, {"depth_ab_m": "ab_m", "depth_ab_v": "ab_v"}.get(name, name))
+                    setattr(s, name, None if t is None else t.data_ptr())
             s.workspace_bytes = self.workspace.numel()
             s.cu_count = self.cu_count
             s.flags = GFL_FIT_DETERMINISTIC if self._deterministic else 0
@@ -331,21 +328,20 @@ class FitEngine:
     def deterministic(self, on):
         # (the state word is part of the graph key: iteration() re-captures its graphs after a change)
         self._deterministic = bool(on)
-        if getattr(self, "_state", None) is not None:
+        if self._state is not None:
             self._state.flags = GFL_FIT_DETERMINISTIC if self._deterministic else 0
 
     # -------------------------------------------------------------------- calls
     def snapshot_ring(self, rows):
         """(rows, 3, H, W, 3) uint8 on the device: where a train() call keeps its snapshots until its end
-        (trainer.make_stepper).  One ring per engine, grown on demand; the current stream waits for the copy that emptied
+        (stage.RingSink).  One ring per engine, grown on demand; the current stream waits for the copy that emptied
         it last (``snapshot_ring_copied``)."""
-        ring = getattr(self, "_snap_ring", None)
+        ring = self._snap_ring
         if ring is None or ring.shape[0] < rows:
             ring = torch.empty(int(rows), 3, self.H, self.W, 3, dtype=torch.uint8, device=self.dev)
             self._snap_ring = ring
-        done = getattr(self, "_snap_ring_done", None)
-        if done is not None:
-            torch.cuda.current_stream().wait_event(done)
+        if self._snap_ring_done is not None:
+            torch.cuda.current_stream().wait_event(self._snap_ring_done)
         return ring[:rows]
 
     def snapshot_ring_copied(self):
@@ -371,7 +367,7 @@ class FitEngine:
         if self._reserved_N != self.N or self.N <= 0:
             return 0
         key = (self.W, self.H, self.K_cap)
-        if getattr(self, "_reserved_sup", (None, 0))[0] != key:
+        if self._reserved_sup[0] != key:
             self._reserved_sup = (key, int(self.lib.gfl_fit_reserved_supported(ctypes.byref(self.state()),
                                                                                 ctypes.byref(self.hp))))
         return self.GFL_ITER_RESERVED if self._reserved_sup[1] else 0
@@ -389,7 +385,7 @@ class FitEngine:
         if snapshot:
             from .color import lut
             assert count == 1
-            if getattr(self, "_snap_out", None) is None:
+            if self._snap_out is None:
                 self._snap_out = torch.empty(3, self.H, self.W, 3, dtype=torch.uint8, device=self.dev)
             snap_args = (L.ptr(lut("turbo", self.dev)), L.ptr(self._snap_out))
         # (reserved=False: the first iteration of the call takes the exact binning path whatever came before)
@@ -408,7 +404,7 @@ class FitEngine:
                 # protect allocations inside the capture; the library allocates nothing.  "thread_local": a capture
                 # in one host thread must not fail because another thread (another clip on the same device,
                 # fit_video.fit_clips_concurrent) reads a value back at that moment.
-                if getattr(self, "_capture_stream", None) is None:
+                if self._capture_stream is None:
                     self._capture_stream = torch.cuda.Stream(device=self.dev)
                 side = self._capture_stream
                 cur = torch.cuda.current_stream()
@@ -453,7 +449,7 @@ class FitEngine:
         Only AFTER the iteration's backward.  ``out``: a contiguous (3, H, W, 3) uint8 tensor to write into."""
         from .color import lut
         need = self.lib.gfl_fit_snapshot_workspace_bytes(self.N, self.W, self.H)
-        if getattr(self, "_snap_ws", None) is None or self._snap_ws.numel() < need:
+        if self._snap_ws is None or self._snap_ws.numel() < need:
             self._snap_ws = torch.empty(int(need * 1.5), dtype=torch.uint8, device=self.dev)
         if out is None:
             out = torch.empty(3, self.H, self.W, 3, dtype=torch.uint8, device=self.dev)
@@ -476,7 +472,7 @@ class FitEngine:
 
     def restore_state(self, saved):
         """Back to ``save_state``'s moment, on the current stream.  Elementwise kernels, not ``copy_``: device-to-device
-        ``copy_`` goes through the runtime's blit kernel (47 us for 3.7 MB, trainer.py on the snapshot ring)."""
+        ``copy_`` goes through the runtime's blit kernel (47 us for 3.7 MB, stage.py on the snapshot ring)."""
         n = saved["N"]
         if n != self.N:
             raise RuntimeError("FitEngine.restore_state: the splat count has changed since save_state")
@@ -539,30 +535,32 @@ class FitEngine:
             if skipped > 0:
                 # tiles outgrew the regions reserved for them in `skipped` iterations (GFL_ITER_RESERVED): those stepped
                 # nothing, the ones after them were fine again -- nothing to grow, that many iterations more to run
-                self.overflow[1:2].zero_()
-                self.regions_outgrown = getattr(self, "regions_outgrown", 0) + skipped
+                self._count_void(skipped)
             return max(skipped, 0)
         if code != 1:
             self.overflow.zero_()
             raise RuntimeError(self._overflow_message(code))
+        self._double_pairs()
+        self.overflow.zero_()
+        return max(skipped, 0)
+
+    def _count_void(self, skipped):
+        """``skipped`` iterations stepped nothing and nothing has to grow: the word is cleared, the caller runs them again"""
+        self.overflow[1:2].zero_()
+        self.regions_outgrown += skipped
+
+    def _double_pairs(self):
         self._K_grown = True
         self._alloc_pairs(2 * self.K_cap)
-        self.overflow.zero_()
         with _GRAPH_LOCK:
             self._graphs.clear()
         self._graph_key = None
-        self.pairs_grown = getattr(self, "pairs_grown", 0) + 1
-        return max(skipped, 0)
+        self.pairs_grown += 1
 
     def grow_pairs(self):
         """Twice the room for (splat, tile) pairs, before they run out (the caller has drained the stream)."""
         self._pend_event = None
-        self._K_grown = True
-        self._alloc_pairs(2 * self.K_cap)
-        with _GRAPH_LOCK:
-            self._graphs.clear()
-        self._graph_key = None
-        self.pairs_grown = getattr(self, "pairs_grown", 0) + 1
+        self._double_pairs()
 
     def _overflow_message(self, code):
         if code == 2:
@@ -578,7 +576,7 @@ class FitEngine:
         does an iteration on reserved regions -- the region-reserving workgroup of its LAST launch stores the sum of the
         tile counts there (gfl_fit_order.hpp: ``*ro.total = pairs``, ``ro.total = tile_offsets + T`` in gfl_fit.hip) -- so the
         word is at most one iteration old, whichever path ran (ADVICE r05 asked whether the reserved path leaves it stale)."""
-        if getattr(self, "_pend_host", None) is None:
+        if self._pend_host is None:
             self._pend_host = torch.zeros(8, dtype=torch.int32, pin_memory=True)
         self._pend_host[0:5].copy_(self._offsets_and_flags[self.T:self.T + 5], non_blocking=True)      # K, then the four words
         self._pend_event = torch.cuda.Event()
@@ -586,18 +584,37 @@ class FitEngine:
 
     def pending_ready(self):
         """False while a ``watch_pending`` copy has not landed yet (``read_pending`` would wait)."""
-        ev = getattr(self, "_pend_event", None)
-        return ev is None or ev.query()
+        return self._pend_event is None or self._pend_event.query()
 
     def read_pending(self):
         """(code, iterations that stepped nothing, pair count) of the last ``watch_pending``; None without one."""
-        ev = getattr(self, "_pend_event", None)
-        if ev is None:
+        if self._pend_event is None:
             return None
-        ev.synchronize()
+        self._pend_event.synchronize()
         self._pend_event = None
         v = self._pend_host.tolist()
         return v[1], v[2], v[0]
+
+    def drop_pending(self):
+        """forget a ``watch_pending`` nobody has read (a new stage: the watch was the last one's)"""
+        self._pend_event = None
+
+    def take_pending(self):
+        """The last ``watch_pending``, read.  None: there was none.  k >= 0: k iterations stepped nothing (counted, the word
+        cleared): run k again with ``reserved=False``, where they cannot be void again.  -1: go the blocking way
+        (``settle_overflow``) -- pairs were dropped, or the lists were more than half full and have been doubled here."""
+        got = self.read_pending()
+        if got is None:
+            return None
+        code, skipped, pairs = got
+        if code != 0 or 2 * pairs > self.K_cap:
+            if code == 0:
+                torch.cuda.current_stream().synchronize()
+                self.grow_pairs()
+            return -1
+        if skipped > 0:
+            self._count_void(skipped)
+        return max(skipped, 0)
 
     def watch_overflow(self):
         """The same check without stopping the host: the flag is copied to pinned memory behind the work queued so
@@ -605,14 +622,14 @@ class FitEngine:
         dropped pairs.  train() calls this once per frame -- a blocking read there drained the queue between two
         stages -- and fit_clip ends with the blocking check."""
         self.poll_overflow()
-        if getattr(self, "_ovf_host", None) is None:
+        if self._ovf_host is None:
             self._ovf_host = torch.zeros(1, dtype=torch.int32, pin_memory=True)
         self._ovf_host.copy_(self.overflow[0:1], non_blocking=True)
         self._ovf_event = torch.cuda.Event()
         self._ovf_event.record()
 
     def poll_overflow(self):
-        ev = getattr(self, "_ovf_event", None)
+        ev = self._ovf_event
         if ev is not None and ev.query():
             self._ovf_event = None
             if int(self._ovf_host[0]):

@@ -67,7 +67,7 @@ def test_camera_only_phase_moves_the_pose_not_the_splats():
     tr.init_gaussians_from_image(f0["image"], f0["depth"], num_points=1500)
     tr.train(iterations=40, lr=4e-3, lambda_rgb=1.0, lambda_depth=1e-2, lambda_var=10.0, move_mask=f0["move_mask"],
              densify_interval=0, snapshot_interval=0)
-    assert hasattr(tr, "still_mask") and tr.still_mask.dtype == torch.bool
+    assert tr.still_mask is not None and tr.still_mask.dtype == torch.bool
     tr.set_gt_image(f1["image"]); tr.set_gt_depth(f1["depth"]); tr.set_gt_flow(f0["flow"])
     before = {k: v.clone() for k, v in tr._attributes.items()}
     pose0 = tr.pose.detach().clone()

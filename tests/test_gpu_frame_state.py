@@ -44,7 +44,7 @@ class _Spy:
     def __call__(self, **kw):
         tr = self.tr
         pre = dict(xyz=tr._attributes["xyz"].detach().clone().cpu(), camera_only=bool(kw.get("camera_only", False)),
-                   has_still=hasattr(tr, "still_mask"))
+                   has_still=tr.still_mask is not None)
         if pre["has_still"]:
             pre.update(last_uv=tr.last_uv.clone().cpu(), last_still_mask=tr.last_still_mask.clone().cpu(),
                        gt_flow=tr.gt_flow.clone().cpu(), gt_depth=tr.gt_depth.clone().cpu(),
@@ -168,7 +168,7 @@ def test_mask_prompt_points_and_their_propagation_match_the_restatement(fused):
     tr.init_gaussians_from_image(f0["image"], f0["depth"], num_points=N0)
     common = dict(lambda_rgb=1.0, lambda_depth=1e-2, snapshot_interval=0)
     tr.train(iterations=40, lr=4e-3, lambda_var=10.0, densify_interval=15, densify_times=1, move_mask=f0["move_mask"], **common)
-    assert not hasattr(tr, "propagate_seg")
+    assert tr.propagate_seg is None
     prompt = f0["move_mask"]                                         # the first frame's segmentation of the object
     pts = tr.init_mask_prompt_pts(prompt)
     # (the reference renders anew there: the projections of the rows as the LAST Adam step left them, not last_uv)

@@ -7,6 +7,7 @@ import torch
 from gflow_amd import synthetic as S, fit_video as FV
 from gflow_amd import trainer as TR
 from gflow_amd import fused as FU
+from gflow_amd import stage as ST
 
 n_frames = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 snap = int(sys.argv[2]) if len(sys.argv) > 2 else 10
@@ -39,23 +40,25 @@ TR.SimpleGaussian.train = timed("train", TR.SimpleGaussian.train,
                                 key=lambda self, **k: f"train total (it={k.get('iterations')}, cam={k.get('camera_only', False)})")
 TR.SimpleGaussian.make_stepper = timed("  make_stepper", TR.SimpleGaussian.make_stepper)
 TR.SimpleGaussian.densify_by_pixels = timed("    densify_by_pixels", TR.SimpleGaussian.densify_by_pixels)
-TR._Stepper.run = timed("  stepper.run", TR._Stepper.run)
+ST.FusedStage.run = timed("  stepper.run", ST.FusedStage.run)
 FU.FitEngine.snapshot = timed("    snapshot (3 images, device)", FU.FitEngine.snapshot)
 orig_it = FU.FitEngine.iteration
 
 
-def it(self, use_graph=False, count=1, snapshot=False):
-    gkey = ("snap", count) if snapshot else count
+def it(self, use_graph=False, count=1, snapshot=False, **kw):
+    # (the graphs' keys end in the reserved-regions flag, which iteration() decides: a first capture of the OTHER variant of a
+    #  count that has a graph already is timed as an iteration here)
+    gkey = ("snap", count) if snapshot else (count,)
     will_capture = use_graph and self._launched and not FU.PROFILE["mask"] and (
-        self._graph_key != bytes(self.state()) + bytes(self.hp) or gkey not in self._graphs)
+        self._graph_key != bytes(self.state()) + bytes(self.hp) or not any(k[:-1] == gkey for k in self._graphs))
     if will_capture:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        r = orig_it(self, use_graph, count, snapshot)
+        r = orig_it(self, use_graph, count, snapshot, **kw)
         torch.cuda.synchronize()
         add(f"    graph capture + first replay (count={count}, snapshot={snapshot})", time.perf_counter() - t0)
         return r
-    return orig_it(self, use_graph, count, snapshot)
+    return orig_it(self, use_graph, count, snapshot, **kw)
 
 
 FU.FitEngine.iteration = it

@@ -32,7 +32,7 @@ def make(self, *a, **k):
     st = orig_make(self, *a, **k)
     k_iters = k.get("iterations")
     mark("make_stepper end")
-    run0 = st.fn_batch
+    run0 = st.run
     state = {"first": True}
 
     def run(n):
@@ -41,7 +41,7 @@ def make(self, *a, **k):
             mark("first run() call")
         run0(n)
         mark("run(%d) returned at it %d" % (n, st.iteration))
-    st.fn_batch = run
+    st.run = run                       # (on the instance: train_steps calls st.run)
     fin0 = st.settle
 
     def fin(*a, **k):

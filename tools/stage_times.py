@@ -38,7 +38,7 @@ def ev():
 def make(self, *a, **k):
     st = orig_make(self, *a, **k)
     rec = {"cam": bool(k.get("camera_only", False)), "iters": k.get("iterations"), "N0": self.current_pts_num(), "e0": None}
-    run0, fin0 = st.fn_batch, st.settle
+    run0, fin0 = st.run, st.settle
 
     def run(n):
         if rec["e0"] is None:
@@ -54,7 +54,7 @@ def make(self, *a, **k):
         if last_look:
             rec["N1"] = self.current_pts_num()
             stages.append(rec)
-    st.fn_batch, st.settle = run, fin
+    st.run, st.settle = run, fin        # (on the instance: train_steps calls st.run and st.settle)
     return st
 
 
