@@ -12,7 +12,8 @@ import pytest
 import torch
 
 from oracle import msplat_oracle as MO
-from tests.scenes import random_scene, scene_group
+from tests.scenes import (CAMERAS, CLAMPING, assert_regime, camera_scene, check_known_answers, clamp_known_answers,
+                          random_scene, scene_group, take_rows)
 
 pytestmark = pytest.mark.gpu
 
@@ -24,9 +25,9 @@ def _ms():
     return ms
 
 
-def close_frac(a, b, rtol, atol, bad_frac=0.0, hard=None, what=""):
+def close_frac(a, b, rtol, atol, bad_frac=0.0, hard=None, what="", log=False):
     """|a-b| <= atol + rtol*|b| for all but ``bad_frac`` of the entries, and never
-    beyond ``hard`` (absolute)."""
+    beyond ``hard`` (absolute).  ``log``: record what was observed even where nothing may be off."""
     a = torch.as_tensor(a).detach().double().cpu()
     b = torch.as_tensor(b).detach().double().cpu()
     assert a.shape == b.shape, f"{what}: shape {tuple(a.shape)} vs {tuple(b.shape)}"
@@ -38,10 +39,16 @@ def close_frac(a, b, rtol, atol, bad_frac=0.0, hard=None, what=""):
     assert frac <= bad_frac, f"{what}: {frac:.3e} of entries off (allowed {bad_frac:.1e}); max err {err.max().item():.3e}"
     if hard is not None:
         assert err.max().item() <= hard, f"{what}: max err {err.max().item():.3e} > {hard}"
-    if bad_frac > 0 and what:
-        # what was actually observed, for the report (pytest -rP / -s shows it; tests/observed_parity.log collects it)
+    if (bad_frac > 0 or log) and what:
         line = (f"{what}: off-tolerance share {frac:.2e} (allowed {bad_frac:.1e}), max abs err {err.max().item():.3e}"
                 + (f" (hard cap {hard:g})" if hard is not None else "") + f", p99.99 {err.flatten().kthvalue(max(1, int(0.9999 * err.numel()))).values.item():.2e}")
+        observe(line)
+
+
+def observe(*lines):
+    """Print what a comparison saw and append it to the observed-parity log."""
+    for line in lines:
+        # what was actually observed, for the report (pytest -rP / -s shows it; tests/observed_parity.log collects it)
         print(line)
         try:
             import os
@@ -51,6 +58,27 @@ def close_frac(a, b, rtol, atol, bad_frac=0.0, hard=None, what=""):
                 f.write(line + "\n")
         except OSError:
             pass
+
+
+def rel_l2(a, b, rows=None):
+    a, b = torch.as_tensor(a).detach().double().cpu(), torch.as_tensor(b).detach().double().cpu()
+    if rows is not None:
+        a, b = a[rows], b[rows]
+    return ((a - b).norm() / b.norm()).item()
+
+
+def subset_check(a, b, rows, what, rel_bound=None, frac=None):
+    """The bounds a gradient is held to over all rows, once more over ``rows`` only (the splats on the EWA clamp's branch:
+    a handful of wrong rows disappear in a norm over thousands).  ``frac`` = (rtol, atol, bad_frac) of the close_frac
+    call made for the whole tensor -- the same numbers, atol included; ``rel_bound`` = the whole tensor's relative-L2
+    bound.  The relative L2 over the rows is recorded either way."""
+    assert rows.dtype == torch.bool and int(rows.sum()) > 0, what
+    if frac is not None:
+        close_frac(torch.as_tensor(a).detach().cpu()[rows], b.detach()[rows], frac[0], frac[1], bad_frac=frac[2], what=what, log=True)
+    rel = rel_l2(a, b, rows)
+    observe(f"{what}: relative L2 over {int(rows.sum())} rows {rel:.2e}" + (f" (bound {rel_bound:g})" if rel_bound is not None else ""))
+    if rel_bound is not None:
+        assert rel < rel_bound, f"{what}: relative L2 error {rel:.2e}"
 
 
 def to_dev(s):
@@ -63,9 +91,9 @@ def scene():
 
 
 # ------------------------------------------------------------------ project_point
-def test_project_point_forward_backward(scene):
+def _check_project_point(s, tag="", rows=None, expect_culled=True):
     ms = _ms()
-    s, d = scene, to_dev(scene)
+    d = to_dev(s)
     W, H = s["W"], s["H"]
     xyz_c = s["xyz"].clone().requires_grad_(True)
     ext_c = s["extr"].clone().requires_grad_(True)
@@ -74,15 +102,21 @@ def test_project_point_forward_backward(scene):
     ext_g = d["extr"].clone().requires_grad_(True)
     uv_g, dep_g = ms.project_point(xyz_g, d["intr"], ext_g, W, H)
     assert torch.equal((dep_g != 0).cpu(), dep_c != 0)                 # same culling decisions
-    assert int((dep_c == 0).sum()) > 0
-    close_frac(uv_g, uv_c, 1e-5, 1e-3, what="uv")
-    close_frac(dep_g, dep_c, 1e-6, 1e-6, what="depth")
+    assert int((dep_c == 0).sum()) > 0 or not expect_culled
+    close_frac(uv_g, uv_c, 1e-5, 1e-3, what=tag + "uv")
+    close_frac(dep_g, dep_c, 1e-6, 1e-6, what=tag + "depth")
     g = torch.Generator().manual_seed(0)
     wu, wd = torch.randn(uv_c.shape, generator=g), torch.randn(dep_c.shape, generator=g)
     ((uv_c * wu).sum() + (dep_c * wd).sum()).backward()
     ((uv_g * wu.to(DEV)).sum() + (dep_g * wd.to(DEV)).sum()).backward()
-    close_frac(xyz_g.grad, xyz_c.grad, 1e-4, 1e-3, what="d_xyz")
-    close_frac(ext_g.grad, ext_c.grad, 1e-4, 1e-4 * ext_c.grad.abs().max().item(), what="d_extr")
+    close_frac(xyz_g.grad, xyz_c.grad, 1e-4, 1e-3, what=tag + "d_xyz", log=bool(tag))
+    close_frac(ext_g.grad, ext_c.grad, 1e-4, 1e-4 * ext_c.grad.abs().max().item(), what=tag + "d_extr", log=bool(tag))
+    if rows is not None:
+        subset_check(xyz_g.grad, xyz_c.grad, rows, tag + "d_xyz, clamped rows", frac=(1e-4, 1e-3, 0.0))
+
+
+def test_project_point_forward_backward(scene):
+    _check_project_point(scene)
 
 
 # ------------------------------------------------------------------ compute_cov3d
@@ -111,9 +145,9 @@ def _front_end(s, ops, dev):
     return uv, depth, vis, cov
 
 
-def test_ewa_forward_backward(scene):
+def _check_ewa(s, tag="", rows=None):
     ms = _ms()
-    s, d = scene, to_dev(scene)
+    d = to_dev(s)
     W, H = s["W"], s["H"]
     uv_c, dep_c, vis_c, cov_c = _front_end(s, MO, "cpu")
     xyz_c = s["xyz"].clone().requires_grad_(True)
@@ -124,23 +158,30 @@ def test_ewa_forward_backward(scene):
     cov_g = cov_c.detach().to(DEV).requires_grad_(True)
     ext_g = d["extr"].clone().requires_grad_(True)
     con_g, rad_g, til_g = ms.ewa_project(xyz_g, cov_g, d["intr"], ext_g, uv_c.to(DEV), W, H, vis_c.to(DEV))
-    assert rad_g.dtype == torch.int32 and til_g.dtype == torch.int32 and rad_g.shape == (3000, 1)
+    assert rad_g.dtype == torch.int32 and til_g.dtype == torch.int32 and rad_g.shape == (s["xyz"].shape[0], 1)
     same = (rad_g.cpu() == rad_c).reshape(-1)
     assert same.double().mean().item() >= 0.999      # ceil() may flip on an exact boundary
     assert torch.equal(til_g.cpu()[same], til_c[same])
-    close_frac(con_g[same.to(DEV)], con_c[same], 2e-5, 1e-7, what="conic")
+    close_frac(con_g[same.to(DEV)], con_c[same], 2e-5, 1e-7, what=tag + "conic")
+    if rows is not None:
+        close_frac(con_g[(same & rows).to(DEV)], con_c[same & rows], 2e-5, 1e-7, what=tag + "conic, clamped rows", log=True)
     w = torch.randn(con_c.shape, generator=torch.Generator().manual_seed(3)) * same.unsqueeze(1)
     (con_c * w).sum().backward()
     (con_g * w.to(DEV)).sum().backward()
     for name, a, b in (("d_xyz", xyz_g.grad, xyz_c.grad), ("d_cov3d", cov_g.grad, cov_cl.grad),
                        ("d_extr", ext_g.grad, ext_c.grad)):
-        close_frac(a, b, 2e-4, 2e-5 * b.abs().max().item(), bad_frac=2e-4, what=name)
+        close_frac(a, b, 2e-4, 2e-5 * b.abs().max().item(), bad_frac=2e-4, what=tag + name)
+        if rows is not None and name != "d_extr":
+            subset_check(a, b, rows, f"{tag}{name}, clamped rows", frac=(2e-4, 2e-5 * b.abs().max().item(), 2e-4))
+
+
+def test_ewa_forward_backward(scene):
+    _check_ewa(scene)
 
 
 # ------------------------------------------------------------------ sort_gaussian
-def test_sort_matches_oracle_exactly(scene):
+def _check_sort(s):
     ms = _ms()
-    s = scene
     W, H = s["W"], s["H"]
     uv, depth, vis, cov = _front_end(s, MO, "cpu")
     conic, radius, tiles = MO.ewa_project(s["xyz"], cov, s["intr"], s["extr"], uv, W, H, vis)
@@ -153,6 +194,10 @@ def test_sort_matches_oracle_exactly(scene):
     assert ids_g.numel() == int(tiles.sum())
     assert torch.equal(tr_g.cpu(), tr_c)
     assert torch.equal(ids_g.cpu(), ids_c)
+
+
+def test_sort_matches_oracle_exactly(scene):
+    _check_sort(scene)
 
 
 @pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 255, 256, 257, 300, 512, 513, 700, 1024, 1500, 2048, 3000, 4096, 4097])
@@ -197,8 +242,11 @@ def _blend_inputs(s, feat_extra=None):
 
 @pytest.mark.parametrize("C,bg", [(3, 0.0), (1, 0.33), (4, 1.0), (6, 0.2)])
 def test_blend_forward_backward(scene, C, bg):
+    _check_blend(scene, C, bg)
+
+
+def _check_blend(s, C, bg, tag="", rows=None):
     ms = _ms()
-    s = scene
     W, H = s["W"], s["H"]
     uv, conic, depth, ids, tr = _blend_inputs(s)
     g = torch.Generator().manual_seed(7 + C)
@@ -209,16 +257,19 @@ def test_blend_forward_backward(scene, C, bg):
     out_g = ms.alpha_blending(*leaves_g, ids.to(DEV), tr.to(DEV), bg, W, H)
     assert out_g.shape == (C, H, W)
     # 1e-4 relative on rendered values; a flipped 1/255 splat moves a pixel by < 4e-3
-    close_frac(out_g, out_c, 1e-4, 1e-5, bad_frac=1e-4, hard=5e-3, what=f"blend C={C}")
+    close_frac(out_g, out_c, 1e-4, 1e-5, bad_frac=1e-4, hard=5e-3, what=f"{tag}blend C={C}")
     w = torch.randn(out_c.shape, generator=g)
     (out_c * w).sum().backward()
     (out_g * w.to(DEV)).sum().backward()
     for name, a, b in zip(("d_uv", "d_conic", "d_opacity", "d_feature"), leaves_g, leaves_c):
         ref = b.grad
-        close_frac(a.grad, ref, 1e-3, 1e-4 * ref.abs().max().item(), bad_frac=2e-3, what=f"{name} C={C}")
+        close_frac(a.grad, ref, 1e-3, 1e-4 * ref.abs().max().item(), bad_frac=2e-3, what=f"{tag}{name} C={C}")
         # aggregate agreement is much tighter than the per-entry bound
         rel = (a.grad.cpu() - ref).norm() / ref.norm()
-        assert rel < 2e-4, f"{name}: relative L2 error {rel:.2e}"
+        assert rel < 2e-4, f"{tag}{name}: relative L2 error {rel:.2e}"
+        if rows is not None:
+            subset_check(a.grad, ref, rows, f"{tag}{name} C={C}, clamped rows", rel_bound=2e-4,
+                         frac=(1e-3, 1e-4 * ref.abs().max().item(), 2e-3))
 
 
 def test_blend_single_blob_known_answer():
@@ -276,8 +327,12 @@ def test_api_rejects_bad_arguments():
 
 # ---------------------------------------------------------- render_multiple, whole
 def test_render_multiple_end_to_end(scene):
+    _check_render_multiple(scene)
+
+
+def _check_render_multiple(s, tag="", rows=None):
     import gflow_amd.render as R
-    s, d = scene, to_dev(scene)
+    d = to_dev(s)
     W, H = s["W"], s["H"]
     names = ("xyz", "scale", "rotate", "opacity", "rgb")
     lc = [s[k].clone().requires_grad_(True) for k in names]
@@ -288,8 +343,10 @@ def test_render_multiple_end_to_end(scene):
     oc = MO.render_multiple([*lc, s["intr"], ec, 0.2, W, H], types)
     og = R.render_multiple([*lg, d["intr"], eg, 0.2, W, H], types)
     for k in ("rgb", "depth_map", "depth_map_color", "center"):
-        close_frac(og[k], oc[k], 1e-4, 1e-5, bad_frac=3e-4, hard=2e-2, what=k)
-    close_frac(og["uv"], oc["uv"], 1e-5, 1e-3, what="uv")
+        close_frac(og[k], oc[k], 1e-4, 1e-5, bad_frac=3e-4, hard=2e-2, what=tag + k)
+    close_frac(og["uv"], oc["uv"], 1e-5, 1e-3, what=tag + "uv")
+    if tag:
+        close_frac(og["depth"], oc["depth"], 1e-6, 1e-6, what=tag + "depth")
     gen = torch.Generator().manual_seed(9)
     w_rgb, w_dm = torch.randn(3, H, W, generator=gen), torch.randn(1, H, W, generator=gen)
     w_uv = 0.01 * torch.randn(oc["uv"].shape, generator=gen)
@@ -297,10 +354,85 @@ def test_render_multiple_end_to_end(scene):
     ((og["rgb"] * w_rgb.to(DEV)).sum() + (og["depth_map"] * w_dm.to(DEV)).sum() + (og["uv"] * w_uv.to(DEV)).sum()).backward()
     for name, a, b in zip(names, lg, lc):
         rel = (a.grad.cpu() - b.grad).norm() / b.grad.norm()
-        assert rel < 1e-3, f"d_{name}: relative L2 error {rel:.2e}"
-        close_frac(a.grad, b.grad, 2e-3, 2e-4 * b.grad.abs().max().item(), bad_frac=5e-3, what=f"d_{name}")
+        assert rel < 1e-3, f"{tag}d_{name}: relative L2 error {rel:.2e}"
+        close_frac(a.grad, b.grad, 2e-3, 2e-4 * b.grad.abs().max().item(), bad_frac=5e-3, what=f"{tag}d_{name}")
+        if rows is not None:
+            subset_check(a.grad, b.grad, rows, f"{tag}d_{name}, clamped rows", rel_bound=1e-3,
+                         frac=(2e-3, 2e-4 * b.grad.abs().max().item(), 5e-3))
     rel = (eg.grad.cpu() - ec.grad).norm() / ec.grad.norm()
-    assert rel < 1e-3, f"d_extr: relative L2 error {rel:.2e}"
+    if tag:
+        observe(f"{tag}d_extr: relative L2 {rel:.2e} (bound 0.001)")
+    assert rel < 1e-3, f"{tag}d_extr: relative L2 error {rel:.2e}"
+
+
+# ------------------------------------- general cameras: fx != fy, off-centre pp, the EWA clamp
+_CAM_SCENES = {}
+
+
+def cam_scene(cam):
+    """3000 splats at 200 x 136 under the named camera (tests/scenes.py) with the tilted extrinsic, the sets of live splats
+    on the EWA clamp's branches (none under the centred cameras), and -- where there are any -- the scene made of the
+    clamped splats alone: its extrinsic gradient is the clamp backward's and nothing else's.  Checked on the CPU to be
+    in the regime before anything runs on the device."""
+    if cam not in _CAM_SCENES:
+        s = camera_scene(3000, 200, 136, cam, seed=11, sigma_px=2.5)
+        sets = assert_regime(cam, s)
+        rows = sets["any"] if cam in CLAMPING else None
+        only = take_rows(s, rows) if rows is not None else None
+        if only is not None:
+            only_sets = assert_regime(cam, only)
+            assert bool(only_sets["any"].all())
+        _CAM_SCENES[cam] = (s, rows, only)
+    return _CAM_SCENES[cam]
+
+
+@pytest.mark.parametrize("cam", CAMERAS)
+def test_project_point_under_camera(cam):
+    s, rows, only = cam_scene(cam)
+    _check_project_point(s, f"[{cam}] project_point: ", rows)
+    if only is not None:
+        _check_project_point(only, f"[{cam}, clamped splats only] project_point: ", expect_culled=False)
+
+
+@pytest.mark.parametrize("cam", CAMERAS)
+def test_ewa_under_camera(cam):
+    s, rows, only = cam_scene(cam)
+    _check_ewa(s, f"[{cam}] ewa_project: ", rows)
+    if only is not None:
+        _check_ewa(only, f"[{cam}, clamped splats only] ewa_project: ")
+
+
+@pytest.mark.parametrize("cam", CAMERAS)
+def test_sort_under_camera(cam):
+    _check_sort(cam_scene(cam)[0])
+
+
+@pytest.mark.parametrize("cam", CAMERAS)
+def test_blend_under_camera(cam):
+    s, rows, only = cam_scene(cam)
+    _check_blend(s, 4, 1.0, f"[{cam}] alpha_blending: ", rows)
+
+
+@pytest.mark.parametrize("cam", CAMERAS)
+def test_render_multiple_under_camera(cam):
+    s, rows, only = cam_scene(cam)
+    _check_render_multiple(s, f"[{cam}] render_multiple: ", rows)
+    if only is not None:
+        _check_render_multiple(only, f"[{cam}, clamped splats only] render_multiple: ")
+
+
+def test_clamp_known_answers_through_msplat():
+    """The closed-form conics of tests/scenes.py: clamp_known_answers -- on the axis, on each clamp branch, culled one pixel
+    past the frustum, clamped by cx inside it -- from the HIP operators."""
+    ms = _ms()
+    ka = clamp_known_answers()
+    d = to_dev(ka)
+    W, H = ka["W"], ka["H"]
+    uv, depth = ms.project_point(d["xyz"], d["intr"], d["extr"], W, H)
+    vis = depth != 0
+    cov = ms.compute_cov3d(d["scale"], d["rotate"], vis)
+    conic, radius, tiles = ms.ewa_project(d["xyz"], cov, d["intr"], d["extr"], uv, W, H, vis)
+    check_known_answers(ka, uv, depth, conic, radius)
 
 
 # -------------------------------------------- full-size (480p, 60k) properties

@@ -191,3 +191,122 @@ def test_sh_degree_zero_is_constant_and_visible_masks():
     vis = torch.tensor([1, 0, 1, 1, 0], dtype=torch.bool).reshape(5, 1)
     out = MO.compute_sh(shs, d, vis)
     assert torch.all(out[~vis.reshape(-1)] == 0)
+
+
+# ------------------------------------------------------- general cameras: fx != fy, off-centre pp, the EWA clamp
+def test_clamp_known_answers_oracle():
+    """Closed-form conics on and off the clamp (tests/scenes.py: clamp_known_answers): the clamped Jacobian uses the
+    LIMIT, not x / z; the frustum test is about W / 2, the clamp about cx -- a splat one pixel past 1.15 W is culled, one
+    whose |u - cx| is past 0.65 W but whose u is not is visible and clamped."""
+    from tests.scenes import check_known_answers, clamp_known_answers, clamp_sets
+    ka = clamp_known_answers()
+    W, H = ka["W"], ka["H"]
+    uv, depth = MO.project_point(ka["xyz"], ka["intr"], ka["extr"], W, H)
+    vis = depth != 0
+    cov = MO.compute_cov3d(ka["scale"], ka["rotate"], vis)
+    conic, radius, tiles = MO.ewa_project(ka["xyz"], cov, ka["intr"], ka["extr"], uv, W, H, vis)
+    check_known_answers(ka, uv, depth, conic, radius)
+    # the figures the clamp is about, spelled out
+    e = ka["expect"]
+    np.testing.assert_allclose(conic[e["on_axis"][0]].numpy(), [1 / 4.3, 0.0, 1 / 2.1225], rtol=2e-5)
+    a_clamped, a_free = 4.0 * (1 + 1.04 ** 2) + 0.3, 4.0 * (1 + (1.2 * 1.04) ** 2) + 0.3
+    np.testing.assert_allclose(conic[e["x_clamped"][0]].numpy(), [1 / a_clamped, 0.0, 1 / 2.1225], rtol=2e-5)
+    assert a_free - a_clamped > 1.5                         # (10.53 against 8.63: far above any tolerance in use)
+    # and the helper that names the clamped sets agrees with the table
+    sets = clamp_sets(ka)
+    names = {name: k for name, (k, *_r) in e.items()}
+    assert sets["live"].tolist() == [name != "past_the_frustum_by_a_pixel" for name in names]
+    assert [n for n, k in names.items() if sets["x"][k]] == ["x_clamped", "both_clamped", "clamped_by_cx_inside_frustum"]
+    assert [n for n, k in names.items() if sets["y"][k]] == ["y_clamped", "both_clamped"]
+    assert [n for n, k in names.items() if sets["both"][k]] == ["both_clamped"]
+
+
+def test_camera_scene_keeps_random_scene_and_fills_the_regimes():
+    """The general-camera builder gives random_scene's splats under random_scene's camera (to rounding: it divides by
+    sqrt(f f)), and the named cameras are in the regimes their tests rely on."""
+    from tests.scenes import CAMERAS, assert_regime, camera_scene
+    W, H = 200, 136
+    a = random_scene(400, W, H, seed=11, sigma_px=2.5)
+    b = camera_scene(400, W, H, (0.6 * W, 0.6 * W, W / 2, H / 2), seed=11, sigma_px=2.5)
+    for k in ("xyz", "scale", "rotate", "opacity", "rgb", "intr", "extr"):
+        np.testing.assert_allclose(b[k].numpy(), a[k].numpy(), rtol=1e-6, atol=0, err_msg=k)
+    for name in CAMERAS:
+        s = camera_scene(3000, W, H, name, seed=11, sigma_px=2.5)
+        sets = assert_regime(name, s)
+        assert int(sets["live"].sum()) > 2500
+        # a clamped splat is one whose u, v is further than 0.65 W, 0.65 H from the PRINCIPAL POINT
+        uv, _ = MO.project_point(s["xyz"], s["intr"], s["extr"], W, H)
+        far_x = (uv[:, 0] - s["intr"][2]).abs() > 0.65 * W
+        assert (far_x & sets["live"] != sets["x"]).sum() <= 2              # (float32 ties at the limit)
+
+
+def _general_gradcheck_scene():
+    """Eight float64 splats under ``general`` at 48 x 32 with the tilted extrinsic, PLACED on the branches: x-clamped,
+    y-clamped, doubly clamped and free ones, all reaching into the image so the render sees them."""
+    from tests.scenes import camera_scene, clamp_sets
+    W, H = 48, 32
+    s = camera_scene(8, W, H, "general", seed=7, dtype=torch.float64, sigma_px=3.0, behind=0.0)
+    fx, fy, cx, cy = s["intr"].tolist()
+    #                      x-clamped    y-clamped     both          both         free      free      x-clamped   y-clamped
+    uv = torch.tensor([[47.0, 10.0], [20.0, -1.5], [46.0, -1.0], [45.5, 0.5], [20, 15], [30, 20], [44.5, 12], [10.0, -2.0]],
+                      dtype=torch.float64)
+    z = torch.linspace(1.5, 3.0, 8, dtype=torch.float64)
+    cam = torch.stack([(uv[:, 0] - cx) / fx * z, (uv[:, 1] - cy) / fy * z, z], dim=1)
+    s["xyz"] = ((cam - s["extr"][:, 3]) @ s["extr"][:, :3]).contiguous()
+    sets = clamp_sets(s)
+    assert sets["live"].all()
+    assert int(sets["x"].sum()) == 4 and int(sets["y"].sum()) == 4 and int(sets["both"].sum()) == 2, sets
+    assert int((sets["x"] & ~sets["y"]).sum()) >= 1 and int((sets["y"] & ~sets["x"]).sum()) >= 1 and int((~sets["any"]).sum()) >= 1
+    # finite differences are valid: every splat at least 1e-3 from the clamp kinks (in x / z, y / z) and from the cull
+    # limits (in pixels and in depth)
+    pc = s["xyz"] @ s["extr"][:, :3].T + s["extr"][:, 3]
+    rx, ry = pc[:, 0] / pc[:, 2], pc[:, 1] / pc[:, 2]
+    limx, limy = MO.FOV_CLAMP * W / (2 * fx), MO.FOV_CLAMP * H / (2 * fy)
+    assert ((rx.abs() - limx).abs().min() > 1e-3) and ((ry.abs() - limy).abs().min() > 1e-3)
+    u, v = fx * rx + cx, fy * ry + cy
+    for val, half in ((u, W / 2), (v, H / 2)):
+        assert (((val - half).abs() - MO.EXTENT * half).abs().min() > 1e-3)
+    assert (pc[:, 2] - MO.NEAREST).min() > 1e-3
+    return s, sets
+
+
+def test_gradcheck_float64_ops_general_camera():
+    """project_point and ewa_project under fx != fy, an off-centre principal point and the tilted extrinsic, with splats
+    on every branch of the EWA clamp: autograd against finite differences in float64."""
+    s, sets = _general_gradcheck_scene()
+    W, H = s["W"], s["H"]
+    xyz = s["xyz"].clone().requires_grad_(True)
+    extr = s["extr"].clone().requires_grad_(True)
+    assert torch.autograd.gradcheck(lambda a, e: MO.project_point(a, s["intr"], e, W, H), (xyz, extr), atol=1e-7)
+    vis = torch.ones(8, 1, dtype=torch.bool)
+    uv, depth = MO.project_point(s["xyz"], s["intr"], s["extr"], W, H)
+    assert (depth != 0).all()
+    cov = MO.compute_cov3d(s["scale"], s["rotate"], vis).clone().requires_grad_(True)
+    assert torch.autograd.gradcheck(
+        lambda a, c, e: MO.ewa_project(a, c, s["intr"], e, uv, W, H, vis)[0], (xyz, cov, extr), atol=1e-6)
+    # the clamp cuts the gradient where it should: d conic / d x_cam = 0 for an x-clamped splat, not for a free one
+    # (identity extrinsic so that x_cam is xyz[:, 0])
+    eye = torch.eye(4, dtype=torch.float64)[:3]
+    cam = (s["xyz"] @ s["extr"][:, :3].T + s["extr"][:, 3]).clone().requires_grad_(True)
+    con = MO.ewa_project(cam, cov.detach(), s["intr"], eye, uv, W, H, vis)[0]
+    g = torch.autograd.grad(con.sum(), cam)[0]
+    assert torch.all(g[sets["x"], 0] == 0) and torch.all(g[~sets["x"], 0] != 0)
+    assert torch.all(g[sets["y"], 1] == 0) and torch.all(g[~sets["y"], 1] != 0)
+    assert torch.all(g[:, 2] != 0)
+
+
+def test_gradcheck_float64_full_render_general_camera():
+    s, sets = _general_gradcheck_scene()
+    W, H = s["W"], s["H"]
+    leaves = [s[k].clone().requires_grad_(True) for k in ("xyz", "scale", "rotate", "opacity", "rgb")]
+    extr = s["extr"].clone().requires_grad_(True)
+    wts = torch.rand(4, H, W, dtype=torch.float64, generator=torch.Generator().manual_seed(0))
+
+    def fn(xyz, scale, rot, op, rgb, e):
+        o = MO.render_multiple([xyz, scale, rot, op, rgb, s["intr"], e, 0.2, W, H], ["rgb", "depth_map"])
+        return (torch.cat([o["rgb"], o["depth_map"]]) * wts).sum()
+
+    # every placed splat colours pixels: the gradient the check sees goes through the clamped conics
+    g = torch.autograd.grad(fn(*leaves, extr), leaves[1])[0]
+    assert torch.all(g.abs().sum(1) > 0)
+    assert torch.autograd.gradcheck(fn, (*leaves, extr), atol=1e-6, rtol=1e-4, nondet_tol=0.0)
