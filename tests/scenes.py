@@ -190,3 +190,301 @@ def check_known_answers(ka, uv, depth, conic, radius):
         assert depth[k, 0] == 2.0 and radius[k, 0] > 0, name
         np.testing.assert_allclose(uv[k].numpy(), uv_ref, rtol=1e-6, atol=1e-5, err_msg=name)
         np.testing.assert_allclose(conic[k].numpy(), conic_ref, rtol=2e-5, atol=1e-7, err_msg=name)
+
+
+# ------------------------------------------------------------------ opacity regimes
+# Raw (pre-activation) rows, the activations being trainer.py:64-69: |scale|, normalised quaternion, sigmoid(10 opacity),
+# sigmoid(rgb).  Three regimes of the activated opacity o that the blend treats on branches of their own:
+#   capped     o G > ALPHA_MAX at some pixel: alpha = 0.99 there, the gradient passes straight through
+#   threshold  1/255 <= o < 1.05/255: no exact-disc culling in the fused path, one to three pixels see the splat at all
+#   invisible  o < 1/255: in no list
+GROUPS = ("rest", "capped", "threshold", "invisible")
+ATTRS = ("xyz", "scale", "rotate", "opacity", "rgb")
+FRAGILE_MARGIN = 1e-4         # |255 o G - 1| below this: the pair's alpha test hangs on the last bits of exp()
+FRAGILE_SHARE = 0.03          # of a regime's rows may be fragile, no more
+
+
+def raw_rows(s, seed=0):
+    """Raw parameters whose activations reproduce the scene ``s`` (seeded: the signs of the raw scales)."""
+    g = torch.Generator().manual_seed(seed)
+    sign = torch.where(torch.rand(s["scale"].shape, generator=g) > 0.3, 1.0, -1.0).to(s["scale"].dtype)
+    return dict(xyz=s["xyz"].clone(), scale=s["scale"] * sign, rotate=s["rotate"] * 1.7,
+                opacity=torch.logit(s["opacity"].clamp(0.02, 0.98)) / 10.0, rgb=torch.logit(s["rgb"].clamp(0.02, 0.98)))
+
+
+def opacity_regime_scene(N, W, H, seed, n_capped=600, n_threshold=300, n_invisible=300, sigma_px=2.5):
+    """``random_scene(tilt=False)`` as raw rows, with disjoint random subsets of the rows re-drawn into the three opacity
+    regimes: raw opacity uniform in [0.55, 2.0] (o >= 0.9959, part of it exactly 1.0f), o uniform in [1/255, 1.05/255)
+    with raw = logit(o) / 10 worked out in float64, raw opacity uniform in [-1.5, -0.6] (o < 1/255).  The rest keeps
+    logit(o.clamp(0.02, 0.98)) / 10.  Returns the scene's camera and size, ``raw`` and ``group`` (index into GROUPS)."""
+    s = random_scene(N, W, H, seed=seed, sigma_px=sigma_px, tilt=False)
+    raw = raw_rows(s, seed)
+    g = torch.Generator().manual_seed(seed + 1000)
+    perm = torch.randperm(N, generator=g)
+    group = torch.zeros(N, dtype=torch.int64)
+    a, b, c = n_capped, n_capped + n_threshold, n_capped + n_threshold + n_invisible
+    assert c <= N
+    group[perm[:a]], group[perm[a:b]], group[perm[b:c]] = 1, 2, 3
+    op = raw["opacity"].double().clone()
+    rnd = torch.rand(N, 1, generator=g, dtype=torch.float64)
+    o_thr = (1.0 + 0.05 * rnd) / 255.0
+    op = torch.where((group == 1).unsqueeze(1), 0.55 + 1.45 * rnd, op)
+    op = torch.where((group == 2).unsqueeze(1), torch.log(o_thr / (1.0 - o_thr)) / 10.0, op)
+    op = torch.where((group == 3).unsqueeze(1), -1.5 + 0.9 * rnd, op)
+    raw["opacity"] = op.float()
+    return dict(raw=raw, group=group, intr=s["intr"], extr=s["extr"], W=W, H=H)
+
+
+def capped_pile_scene(W=48, H=48, seed=0, n_pile=700, n_rest=300, tile=(1, 1), extr=None, sigma=(20.0, 60.0)):
+    """``n_pile`` capped splats (raw opacity in [0.55, 2.0]) with distinct depths and centres inside ONE 16 x 16 tile,
+    ``sigma`` pixels wide, on top of ``n_rest`` ordinary rows: every pixel of that tile has alpha between ~0.9 and the cap
+    from the nearest layers on and stops after two to four of them, with hundreds of entries of its list behind the stop.
+    The two nearest splats of the pile sit in opposite corners of the tile so that no pixel has both of its first two
+    layers AT the cap: (1 - 0.99)^2 against T_MIN = 1e-4 is decided by the rounding of 0.99 in the number format (float32
+    stops, float64 does not), and that is not what the scene is for.  The pile's rows come first; ``extr`` (3, 4) is the
+    camera the pile is placed for (the identity if None)."""
+    s = random_scene(n_rest, W, H, seed=seed, sigma_px=2.5, tilt=False, behind=0.0)
+    rest = raw_rows(s, seed)
+    g = torch.Generator().manual_seed(seed + 2000)
+    f = float(s["intr"][0])
+    z = 1.0 + 2.0 * (torch.randperm(n_pile, generator=g).double() + 0.5) / n_pile          # distinct, 1 .. 3
+    x0, y0 = 16.0 * tile[0], 16.0 * tile[1]
+    u = x0 + 0.5 + 14.0 * torch.rand(n_pile, generator=g, dtype=torch.float64)
+    v = y0 + 0.5 + 14.0 * torch.rand(n_pile, generator=g, dtype=torch.float64)
+    near = torch.argsort(z)[:2]
+    u[near[0]], v[near[0]], u[near[1]], v[near[1]] = x0 + 1.0, y0 + 1.0, x0 + 14.0, y0 + 14.0
+    sig = sigma[0] * torch.exp(math.log(sigma[1] / sigma[0]) * torch.rand(n_pile, generator=g, dtype=torch.float64))
+    scale = (sig / f * z).unsqueeze(1) * torch.exp(0.1 * torch.randn(n_pile, 3, generator=g, dtype=torch.float64))
+    sign = torch.where(torch.rand(n_pile, 3, generator=g) > 0.3, 1.0, -1.0).double()
+    rot = 1.7 * torch.nn.functional.normalize(torch.randn(n_pile, 4, generator=g, dtype=torch.float64), dim=1)
+    xyz = torch.stack([(u - W / 2) / f * z, (v - H / 2) / f * z, z], dim=1)
+    if extr is not None:
+        xyz = (xyz - extr[:, 3].double()) @ extr[:, :3].double()           # inverse of R x + t
+    # the 24 nearest layers -- the only ones a pixel ever reaches -- keep out of raw opacities between 0.75 and 1.75: there 1 - o
+    # is a few float32 ulps of o, the chain rule's 10 o (1 - o) of a float32 reference is good to a percent only, and over a
+    # dozen contributing rows that does not average out (the regime scene has hundreds of rows in that band)
+    op = 0.55 + 1.45 * torch.rand(n_pile, 1, generator=g, dtype=torch.float64)
+    r = torch.rand(24, 1, generator=g, dtype=torch.float64)
+    op[torch.argsort(z)[:24]] = torch.where(r < 0.5, 0.55 + 0.4 * r, 1.5 + 0.5 * r)
+    pile = dict(xyz=xyz, scale=scale * sign, rotate=rot, opacity=op,
+                rgb=torch.logit(0.02 + 0.96 * torch.rand(n_pile, 3, generator=g, dtype=torch.float64)))
+    raw = {k: torch.cat([pile[k].float(), rest[k]]).contiguous() for k in ATTRS}
+    group = torch.cat([torch.ones(n_pile, dtype=torch.int64), torch.zeros(n_rest, dtype=torch.int64)])
+    return dict(raw=raw, group=group, intr=s["intr"], extr=s["extr"], W=W, H=H, pile_tile=tile[1] * ((W + 15) // 16) + tile[0],
+                n_pile=n_pile)
+
+
+def oracle_front_end(scene, pose, dtype):
+    """Activations, projection, EWA and the sorted lists of the oracle for the raw rows of ``scene`` under ``pose``."""
+    from oracle import fit_oracle as FO
+    from oracle import loss_oracle as LO
+    from oracle import msplat_oracle as MO
+    W, H = scene["W"], scene["H"]
+    xyz, scale, rot, op, rgb = FO.activate({k: v.detach().to(dtype) for k, v in scene["raw"].items()})
+    intr, extr = scene["intr"].to(dtype), LO.pose_to_extr(pose.detach().to(dtype))
+    uv, depth = MO.project_point(xyz, intr, extr, W, H)
+    vis = depth != 0
+    conic, radius, tiles = MO.ewa_project(xyz, MO.compute_cov3d(scale, rot, vis), intr, extr, uv, W, H, vis)
+    ids, tr = MO.sort_gaussian(uv, depth, W, H, radius, tiles)
+    return dict(uv=uv, depth=depth, conic=conic, radius=radius, tiles=tiles, ids=ids, tile_range=tr, opacity=op, rgb=rgb,
+                act=(xyz, scale, rot, op, rgb), extr=extr, intr=intr)
+
+
+def _pair_walk(fe, W, H, max_elems=3_000_000):
+    """The (pixel, splat) pairs of ``MO.alpha_blending`` with the oracle's own decisions, tile batch by tile batch:
+    yields g (nt, L) splat ids and, shaped (nt, 256, L): live (a list entry seen from a pixel inside the image),
+    power, o G, use (passes the alpha test), contrib (use, before the stop) and incl (transmittance behind the pair)."""
+    from oracle import msplat_oracle as MO
+    uv, conic, op, ids_all = fe["uv"], fe["conic"], fe["opacity"], fe["ids"].to(torch.int64)
+    dt = uv.dtype
+    gx, gy = MO.tile_grid(W, H)
+    tr = fe["tile_range"].to(torch.int64)
+    lens = tr[:, 1] - tr[:, 0]
+    order = torch.argsort(lens, descending=True)
+    order = order[lens[order] > 0]
+    px_off = torch.arange(MO.TILE, dtype=dt) + MO.PIXEL_CENTER
+    pos = 0
+    while pos < order.numel():
+        L = int(lens[order[pos]])
+        nt = max(1, min(order.numel() - pos, max_elems // (MO.TILE * MO.TILE * L)))
+        tids = order[pos:pos + nt]
+        pos += nt
+        ar = torch.arange(L)
+        valid = ar.unsqueeze(0) < lens[tids].unsqueeze(1)
+        idx = torch.where(valid, tr[tids, 0].unsqueeze(1) + ar.unsqueeze(0), torch.zeros(1, dtype=torch.int64))
+        g = ids_all[idx]
+        pxx = (tids % gx).to(dt).unsqueeze(1) * MO.TILE + px_off.unsqueeze(0)
+        pyy = (tids // gx).to(dt).unsqueeze(1) * MO.TILE + px_off.unsqueeze(0)
+        PX = pxx.unsqueeze(1).expand(nt, MO.TILE, MO.TILE).reshape(nt, -1, 1)
+        PY = pyy.unsqueeze(2).expand(nt, MO.TILE, MO.TILE).reshape(nt, -1, 1)
+        inside = (PX < W) & (PY < H)
+        gu, gc = uv[g], conic[g]
+        dx = gu[:, :, 0].unsqueeze(1) - PX
+        dy = gu[:, :, 1].unsqueeze(1) - PY
+        power = -0.5 * (gc[:, :, 0].unsqueeze(1) * dx * dx + gc[:, :, 2].unsqueeze(1) * dy * dy) - gc[:, :, 1].unsqueeze(1) * dx * dy
+        araw = op[g].reshape(nt, 1, L) * torch.exp(power)
+        alpha = torch.clamp(araw, max=MO.ALPHA_MAX)
+        live = valid.unsqueeze(1) & inside
+        use = live & (power <= 0) & (alpha >= MO.ALPHA_MIN)
+        incl = torch.cumprod(torch.where(use, 1.0 - alpha, torch.ones_like(alpha)), dim=2)
+        contrib = use & (incl >= MO.T_MIN)
+        yield g, live, power, araw, use, contrib, incl
+
+
+def opacity_sets(scene, pose, margin=FRAGILE_MARGIN):
+    """From the FLOAT64 oracle, boolean masks over the rows of ``scene`` under ``pose``:
+      capped     at least one contributing (pixel, splat) pair with o G > ALPHA_MAX
+      threshold  1/255 <= o and 255 o < 1.05 (the fused path's no-culling branch), contributing at one pixel or more
+      invisible  o < 1/255
+      saturated  the float32 activation gives o == 1
+      fragile    a pair with power <= 0 and |255 o G - 1| < ``margin``: a last-bit difference between two exp()
+                 implementations switches the row's contribution at that pixel on or off
+    plus ``contributing`` (any pair that reaches the image), ``n_capped_pairs``, ``n_stop_edge`` (pairs whose transmittance
+    lands within 1e-5 of T_MIN, relative: the stop rule there is decided by rounding) and ``o`` (float64)."""
+    from oracle import msplat_oracle as MO
+    fe = oracle_front_end(scene, pose, torch.float64)
+    N = scene["raw"]["xyz"].shape[0]
+    W, H = scene["W"], scene["H"]
+    o = fe["opacity"].reshape(-1)
+    count = {k: torch.zeros(N, dtype=torch.int64) for k in ("capped", "contrib", "fragile")}
+    n_stop_edge = 0
+    for g, live, power, araw, use, contrib, incl in _pair_walk(fe, W, H):
+        flat = g.reshape(-1)
+        count["capped"].index_add_(0, flat, (contrib & (araw > MO.ALPHA_MAX)).sum(dim=1).reshape(-1))
+        count["contrib"].index_add_(0, flat, contrib.sum(dim=1).reshape(-1))
+        count["fragile"].index_add_(0, flat, (live & (power <= 0) & ((255.0 * araw - 1.0).abs() < margin)).sum(dim=1).reshape(-1))
+        excl = torch.cat([torch.ones_like(incl[:, :, :1]), incl[:, :, :-1]], dim=2)
+        n_stop_edge += int((use & (excl >= MO.T_MIN) & ((incl / MO.T_MIN - 1.0).abs() < 1e-5)).sum())
+    o32 = torch.sigmoid(10.0 * scene["raw"]["opacity"].float()).reshape(-1)
+    return dict(capped=count["capped"] > 0, threshold=(o >= MO.ALPHA_MIN) & (255.0 * o < 1.05) & (count["contrib"] > 0),
+                invisible=o < MO.ALPHA_MIN, saturated=o32 == 1.0, fragile=count["fragile"] > 0, contributing=count["contrib"] > 0,
+                n_capped_pairs=int(count["capped"].sum()), n_stop_edge=n_stop_edge, o=o)
+
+
+def regime_rows(sets, name):
+    """The rows a per-regime comparison runs over: the regime's, minus the fragile ones."""
+    return sets[name] & ~sets["fragile"]
+
+
+def assert_opacity_regime(sets, ref_grads=None, min_rows=None):
+    """The scene is what its tests are about (checked on the CPU).  ``ref_grads``: the reference gradients by attribute --
+    with them, the threshold rows counted are those with a non-zero gradient.  ``min_rows`` overrides the counts."""
+    need = dict(capped=100, threshold=100, invisible=100, saturated=50, capped_pairs=200)
+    need.update(min_rows or {})
+    thr = sets["threshold"]
+    if ref_grads is not None:
+        nz = torch.zeros_like(thr)
+        for k in ATTRS:
+            nz |= (ref_grads[k].detach().reshape(thr.shape[0], -1) != 0).any(dim=1)
+        thr = thr & nz
+    n = dict(capped=int(sets["capped"].sum()), threshold=int(thr.sum()), invisible=int(sets["invisible"].sum()),
+             saturated=int(sets["saturated"].sum()), capped_pairs=sets["n_capped_pairs"])
+    for k, v in need.items():
+        assert n[k] >= v, f"{k}: {n[k]} (at least {v} wanted)  {n}"
+    for k in ("capped", "threshold"):
+        if int(sets[k].sum()):
+            share = int((sets[k] & sets["fragile"]).sum()) / int(sets[k].sum())
+            assert share <= FRAGILE_SHARE, f"{k}: {share:.3f} of the rows are fragile (at most {FRAGILE_SHARE})"
+    assert sets["n_stop_edge"] == 0, f"{sets['n_stop_edge']} pairs sit on the stop rule's boundary"
+    # a threshold / invisible row must be on its branch in float32 as well: o not within 1e-5 (relative) of a branch point
+    o = sets["o"]
+    for edge in (1.0 / 255.0, 1.05 / 255.0):
+        assert not bool(((o / edge - 1.0).abs() < 1e-5).any()), f"a row's opacity sits on the branch point {edge:.6f}"
+    return n
+
+
+REGIME_LAMBDAS = dict(lambda_rgb=1.0, lambda_depth=0.1, lambda_var=0.0)     # (with lambda_var = 10 the variance term is most of d_scale)
+
+
+def reference_fit(scene, pose, img, dep, dtype=torch.float32, lam=REGIME_LAMBDAS, bg=0.0):
+    """One forward + backward of the oracle's fit iteration on the raw rows of ``scene``: the render (4, H, W), the
+    gradients by attribute (N, width), those of the pose and of the depth affine, the loss terms and the pair count."""
+    from oracle import fit_oracle as FO
+    rc = {k: v.detach().to(dtype).clone().requires_grad_(True) for k, v in scene["raw"].items()}
+    p = pose.detach().to(dtype).clone().requires_grad_(True)
+    ab = torch.tensor([1.0, 0.0], dtype=dtype, requires_grad=True)
+    frame = dict(image=img.to(dtype), depth=dep.to(dtype))
+    loss, info = FO.fit_loss(rc, p, ab, scene["intr"].to(dtype), frame, bg, lam["lambda_rgb"], lam["lambda_depth"], lam["lambda_var"])
+    loss.backward()
+    n = rc["xyz"].shape[0]
+    grads = {k: (rc[k].grad if rc[k].grad is not None else torch.zeros_like(rc[k])).reshape(n, -1) for k in ATTRS}
+    return dict(render=info["render4"].detach(), grads=grads, d_pose=p.grad, d_ab=ab.grad, l_rgb=info["l_rgb"].item(),
+                l_depth=info["l_depth"].item(), K=info["K"])
+
+
+def regime_error(got, ref, rows):
+    """(relative L2, share of entries off rtol 5e-3 / atol 5e-4 max|ref|) of ``got`` against ``ref`` over ``rows`` only --
+    the norm and the atol are the ROWS' own.  A reference that is zero over the rows gives (0 or inf, share)."""
+    a, b = got.detach().double().cpu()[rows], ref.detach().double().cpu()[rows]
+    err = (a - b).abs()
+    den = b.norm().item()
+    rel = (a - b).norm().item() / den if den > 0 else (0.0 if float(err.max()) == 0 else float("inf"))
+    bad = (err > 5e-4 * b.abs().max().item() + 5e-3 * b.abs()).double().mean().item()
+    return rel, bad
+
+
+# ------------------------------------------------------------------ known answers at the cap and at the threshold
+def _f32(x):
+    import struct
+    return struct.unpack("f", struct.pack("f", x))[0]
+
+
+def opacity_known_answers(fmt="float64"):
+    """Closed-form pixels of isotropic splats (conic [A, 0, A], A = 0.05) centred on pixel (8, 8) of a 16 x 16 image over
+    background 0.25, in python floats, without autograd or operators.  ``fmt`` = "float32": the one place where the format
+    decides the ANSWER is honoured -- two layers exactly at the cap leave T (1 - alpha) = (1 - 0.99)^2, which is >= T_MIN =
+    1e-4 with 0.99 and 1e-4 rounded to float64 and < T_MIN with both rounded to float32 (0.0099999905^2 = 9.99998e-5 against
+    9.9999997e-5): the second layer contributes in float64 arithmetic and is stopped in float32 arithmetic.  One pixel
+    further out nothing is at the cap and both formats agree.  Returns a list of cases: name, opacities, features (one
+    channel), depths, {(x, y): value} and, where it applies, d value / d o of the first splat at the centre pixel."""
+    A, bg, c = 0.05, 0.25, (8, 8)
+    r = (lambda x: _f32(x)) if fmt == "float32" else (lambda x: x)
+    cap, amin, tmin = r(0.99), r(1.0 / 255.0), r(1e-4)
+
+    def pixel(ops, feats, x, y):
+        G = math.exp(-0.5 * A * ((c[0] - x) ** 2 + (c[1] - y) ** 2))
+        T, acc = 1.0, 0.0
+        for o, f in zip(ops, feats):
+            a = min(cap, o * G)
+            if a < amin:
+                continue
+            if r(T * r(1.0 - a)) < tmin:
+                break
+            acc += f * a * T
+            T = r(T * r(1.0 - a))
+        return acc + T * bg
+
+    cases = []
+    f = (0.8, 0.3, 0.6)
+    G1 = math.exp(-0.5 * A)
+    # one splat, o = 1: the centre pixel is 0.99 f + 0.01 bg, its neighbour G f + (1 - G) bg; d pixel / d o = G (f - bg) with
+    # G = 1 at the centre: NOT cut by the cap
+    cases.append(dict(name="one_capped", o=[1.0], f=f[:1], px={c: 0.99 * f[0] + 0.01 * bg, (9, 8): G1 * f[0] + (1 - G1) * bg},
+                      d_o=1.0 * (f[0] - bg)))
+    # two: at the centre the second adds 0.99 * 0.01 f2 (float64) or is stopped (float32); at the neighbour both formats blend two
+    two_c = 0.99 * f[0] + 0.99 * 0.01 * f[1] + 0.01 * 0.01 * bg if fmt != "float32" else 0.99 * f[0] + 0.01 * bg
+    two_n = G1 * f[0] + G1 * (1 - G1) * f[1] + (1 - G1) ** 2 * bg
+    cases.append(dict(name="two_capped", o=[1.0, 1.0], f=f[:2], px={c: two_c, (9, 8): two_n}))
+    # three: the third is stopped everywhere near the centre (0.01^3, (1 - G1)^3 = 1.5e-5 < 1e-4)
+    cases.append(dict(name="three_capped", o=[1.0, 1.0, 1.0], f=f, px={c: two_c, (9, 8): two_n}))
+    # at the threshold: 1.02 / 255 is seen at its centre pixel only (1.02 G1 = 0.995 < 1), 0.99 / 255 nowhere
+    o_in, o_out = 1.02 / 255.0, 0.99 / 255.0
+    cases.append(dict(name="just_visible", o=[o_in], f=f[:1], px={c: o_in * f[0] + (1 - o_in) * bg, (9, 8): bg, (8, 7): bg, (9, 9): bg}))
+    cases.append(dict(name="just_invisible", o=[o_out], f=f[:1], px={c: bg, (9, 8): bg, (0, 0): bg}))
+    for case in cases:        # the closed forms above against the literal loop, in the format's arithmetic
+        for (x, y), want in case["px"].items():
+            assert abs(pixel(case["o"], case["f"], x, y) - want) < 1e-7, (case["name"], x, y)
+    return dict(W=16, H=16, A=A, bg=bg, centre=c, cases=cases)
+
+
+def known_answer_inputs(case, ka, dtype=torch.float32):
+    """uv, conic, opacity, feature, depth of a case of ``opacity_known_answers`` (nearest first) and the radius / tile
+    count an operator-level caller passes to sort_gaussian."""
+    n = len(case["o"])
+    uv = torch.tensor([[float(ka["centre"][0]), float(ka["centre"][1])]] * n, dtype=dtype)
+    conic = torch.tensor([[ka["A"], 0.0, ka["A"]]] * n, dtype=dtype)
+    op = torch.tensor(case["o"], dtype=dtype).reshape(n, 1)
+    feat = torch.tensor(case["f"], dtype=dtype).reshape(n, 1)
+    depth = torch.arange(1, n + 1, dtype=dtype).reshape(n, 1)
+    radius = torch.full((n, 1), 14, dtype=torch.int32)
+    return uv, conic, op, feat, depth, radius, torch.ones(n, 1, dtype=torch.int32)
