@@ -108,6 +108,33 @@ def reduce_tapvid(preds, gts, n_frames, dropped, dist=None, device="cpu"):
     return out
 
 
+DAVIS_KEYS = ("J", "F", "J&F")
+
+
+def reduce_davis(segs, dist=None, device="cpu"):
+    """The "davis" block of the JSON line: every clip's J, F and J&F (segmentation.evaluate: means over its scored
+    frames), averaged over the clips that have a scored frame; ``frames_scored`` is their total.  Over ranks by ONE more
+    small all-reduce(SUM) of (the three sums, frames scored, clips)."""
+    from . import segmentation as SG
+    sums, frames, clips = [0.0] * len(DAVIS_KEYS), 0, 0
+    for seg in segs.values():
+        m = SG.evaluate(seg)
+        if m["frames_scored"]:
+            for k, key in enumerate(DAVIS_KEYS):
+                sums[k] += m[key]
+            frames += m["frames_scored"]
+            clips += 1
+    vec = torch.tensor(sums + [float(frames), float(clips)], dtype=torch.float64, device=device)
+    if dist is not None and dist.is_initialized():
+        dist.all_reduce(vec, op=dist.ReduceOp.SUM)
+    v = vec.tolist()
+    clips = v[len(DAVIS_KEYS) + 1]
+    out = {k: v[i] / clips if clips else float("nan") for i, k in enumerate(DAVIS_KEYS)}
+    out["frames_scored"] = int(v[len(DAVIS_KEYS)])
+    out["clips"] = int(clips)
+    return out
+
+
 _FIT_STREAMS = {}
 
 
@@ -215,7 +242,7 @@ def stage_kwargs(c, frames, i, stage):
 
 
 def fit_clip(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, log=None, load_extr=True, keep=None,
-             async_snapshots=None, deterministic=None, track_queries=None):
+             async_snapshots=None, deterministic=None, track_queries=None, segment=False):
     """Fit one clip; returns the metrics dict of this clip (PSNR summed over its frames; with ``cfg["traj_num"]`` > 0 also
     ``"traj"``: the per-frame trajectory images and seed projections, host arrays -- what the reference's frame loop collects in
     ``frames_sequence_traj / frames_sequence_traj_upon / sequence_traj``).
@@ -230,7 +257,12 @@ def fit_clip(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, 
     ``track_queries``: rows [t, y, x] (pixels) of points to track (gflow_amd.tracking.Tracker; ValueError unless every t is
     a frame of the clip): every query is anchored at the end of its frame and tracked, with an occlusion flag, at the end of
     every later one; the dict then has ``"tracks"`` (Tracker.result()).  ``keep["record_track_inputs"] = True``: the
-    per-frame (uv, depth, depth_map) the tracker read, cloned, in ``keep["track_inputs"]``."""
+    per-frame (uv, depth, depth_map) the tracker read, cloned, in ``keep["track_inputs"]``.
+    ``segment``: also the moving region of every frame and its DAVIS score against the frame's ``move_mask``
+    (gflow_amd.segmentation.MoveSegRecorder; INTEGRATION.md, "Moving-region segmentation"): the dict then has
+    ``"segmentation"`` = dict(masks (T, H, W) uint8, valid (T,) bool, counts (T, 6) int64, J, F, JF (T,) float64).  Nothing
+    is read back while the clip is fitted.  ``keep["record_seg_inputs"] = True``: the per-frame (uv, sel) the masks are
+    built from, cloned, in ``keep["seg_inputs"]`` (None for a frame without a joint stage)."""
     if deterministic and not fused:
         raise ValueError("fit_clip(deterministic=True) needs fused=True: the operator path's alpha_blending backward has no "
                          "deterministic implementation")
@@ -238,7 +270,7 @@ def fit_clip(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, 
     dev_ = torch.device(device)
     g = fit_clip_steps(frames, device, cfg=cfg, seed=seed, snapshot_interval=snapshot_interval, fused=fused, log=log,
                        load_extr=load_extr, chunk=None, keep=keep, deterministic=deterministic, track_queries=track_queries,
-                       **({} if async_snapshots is None else {"async_snapshots": async_snapshots}))
+                       segment=segment, **({} if async_snapshots is None else {"async_snapshots": async_snapshots}))
 
     drive = lambda: run_to_end(g)
     if dev_.type == "cuda" and torch.cuda.current_stream(dev_) == torch.cuda.default_stream(dev_):
@@ -258,7 +290,7 @@ def fit_clip(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, 
 
 
 def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, log=None, load_extr=True, chunk=None,
-                   async_snapshots=True, keep=None, cu_count=0, deterministic=None, track_queries=None):
+                   async_snapshots=True, keep=None, cu_count=0, deterministic=None, track_queries=None, segment=False):
     """fit_clip as a generator: yields after every ``chunk`` iterations of a stage (None: never) and returns the metrics
     dict.  The caller owns the stream the work is enqueued on (fit_clips_concurrent gives every clip its own)."""
     from .trainer import SimpleGaussian
@@ -275,6 +307,9 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
                         device=device, seed=seed, fused=fused, deterministic=deterministic)
     tr.async_snapshots = bool(async_snapshots)       # (trainer.py: snapshots composed beside the next iterations, or behind theirs)
     tr.cu_count = int(cu_count)                      # (the caller's stream is CU-masked: fit_clips_concurrent(partition=True))
+    if segment:
+        from .segmentation import MoveSegRecorder
+        tr.seg_recorder = MoveSegRecorder(len(frames), tr.H, tr.W, tr.device)
     tr.load_camera(focal=f0["focal"], pp=f0["pp"])
     if load_extr and f0.get("extr") is not None:
         tr.load_camera(extr=f0["extr"])
@@ -371,6 +406,8 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
         log(f"frame 0: psnr {float(psnr_sum):.2f} dB, splats {tr.current_pts_num()}")
     for i, fr in enumerate(frames[1:], start=1):
         begin_frame(tr, frames, i, load_extr)
+        if segment:
+            tr.seg_recorder.frame = i
         if c["camera_first"]:                            # fit_video.py:256-278
             yield from tr.train_steps(**stage_kwargs(c, frames, i, "camera"), **common)
         if c["iterations_after"] > 0:                    # fit_video.py:288-315
@@ -414,16 +451,22 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
         out["traj"] = traj_out
     if tracker is not None:
         out["tracks"] = tracker.result()              # (one copy to the host; not a number either)
+    if segment:
+        # one copy of every frame's (uv, sel) to the host, the hull masks, one launch that scores them all
+        rec = tr.seg_recorder
+        if keep is not None and keep.get("record_seg_inputs"):
+            keep["seg_inputs"] = [None if x is None else (x[0].clone(), x[1].clone()) for x in rec.inputs]
+        out["segmentation"] = rec.result([fr["move_mask"] for fr in frames])
     return out
 
 
 # the keys of fit_clip's dict that are per-clip numbers (sums over clips make sense); "traj" is the trajectory output,
-# "tracks" the tracker's
+# "tracks" the tracker's, "segmentation" the moving-region masks and their score
 NUMERIC_KEYS = ("psnr_sum", "frames", "iterations", "rasterisations", "clips", "splats_final", "void_iterations")
 
 
 def fit_clips_concurrent(clips, device, cfg=None, seeds=None, snapshot_interval=0, chunk=32, partition=False,
-                         deterministic=None, track_queries=None):
+                         deterministic=None, track_queries=None, segment=False):
     """Fit several clips AT THE SAME TIME on ONE device, in one host thread: every clip has its own trainer, engine and
     STREAM, and the clips take turns enqueueing ``chunk`` iterations each (fit_clip_steps), so their graph launches
     interleave on the device.  One fit leaves the chip partly idle -- its kernels are a chain of dependent launches,
@@ -440,7 +483,8 @@ def fit_clips_concurrent(clips, device, cfg=None, seeds=None, snapshot_interval=
     on it (the schedule never enters a result).  Measured in bench.py's ``clips_per_gpu`` table.
     ``deterministic`` (None: torch's switch): every clip's result is bit for bit that of fit_clip(..., deterministic=True)
     with the same seed -- without ``partition``, which changes the number of tile queues (include/gflow_hip.h).
-    ``track_queries``: None, or one entry (fit_clip's ``track_queries``, or None) per clip."""
+    ``track_queries``: None, or one entry (fit_clip's ``track_queries``, or None) per clip.  ``segment``: fit_clip's, for
+    all clips."""
     n = len(clips)
     if track_queries is not None and len(track_queries) != n:
         raise ValueError("fit_clips_concurrent: track_queries needs one entry per clip")
@@ -462,7 +506,7 @@ def fit_clips_concurrent(clips, device, cfg=None, seeds=None, snapshot_interval=
     #  engine per clip cost them more than they give)
     gens = [fit_clip_steps(clips[i], dev, cfg, seed=seeds[i], snapshot_interval=snapshot_interval, chunk=chunk,
                            async_snapshots=n == 1, cu_count=shares[i][1] if shares else 0, deterministic=deterministic,
-                           track_queries=None if track_queries is None else track_queries[i])
+                           track_queries=None if track_queries is None else track_queries[i], segment=segment)
             for i in range(n)]
     results = [None] * n
     live = list(range(n))
@@ -504,6 +548,11 @@ def main(argv=None):
                     help="track the first-visible query points of each clip's tracking.pkl (synthetic clips: their "
                          "make_clip_tracks) through the fit and score them with TAP-Vid (a \"tapvid\" block in the line)")
     ap.add_argument("--track-out", default=None, help="with --track: write each clip's predicted tracks to DIR/clip_<i>.npz")
+    ap.add_argument("--seg", action="store_true",
+                    help="keep every frame's moving-region mask and score it against the frame's move_mask with DAVIS J, F "
+                         "and J&F (a \"davis\" block in the line)")
+    ap.add_argument("--seg-out", default=None,
+                    help="with --seg: write each clip's masks to DIR/clip_<i>/move_mask_<frame>.png")
     args = ap.parse_args(argv)
     det = True if args.deterministic else None
     from . import synthetic as S
@@ -569,21 +618,24 @@ def main(argv=None):
     t0 = time.perf_counter()
     c = max(1, args.clips_per_gpu)
     order = sorted(clips, key=lambda j: (-lengths[j], j))          # (clips of similar length share the GPU)
-    preds = {}
+    preds, segs = {}, {}
     for g0 in range(0, len(order), c):
         group = order[g0:g0 + c]
         if len(group) == 1:
             ci = group[0]
-            res = [fit_clip(clips[ci], dev, cfg, seed=ci, deterministic=det, track_queries=queries.get(ci),
+            res = [fit_clip(clips[ci], dev, cfg, seed=ci, deterministic=det, track_queries=queries.get(ci), segment=args.seg,
                             log=(lambda s, ci=ci: print(f"[rank {rank} clip {ci}] {s}")) if args.verbose else None)]
         else:
             res = fit_clips_concurrent([clips[ci] for ci in group], dev, cfg, seeds=group, deterministic=det,
-                                       track_queries=[queries.get(ci) for ci in group] if args.track else None)
+                                       track_queries=[queries.get(ci) for ci in group] if args.track else None,
+                                       segment=args.seg)
         for ci, m in zip(group, res):
             for k in METRIC_NAMES:
                 local[k] += m[k]
             if "tracks" in m:
                 preds[ci] = m["tracks"]
+            if "segmentation" in m:
+                segs[ci] = m["segmentation"]
     torch.cuda.synchronize()
     out = reduce_metrics(local, time.perf_counter() - t0, dist, torch.device("cpu") if (world > 1 and shared) else dev,
                          rank=rank, world=world)
@@ -595,6 +647,16 @@ def main(argv=None):
             os.makedirs(args.track_out, exist_ok=True)
             for ci, p in preds.items():
                 np.savez(os.path.join(args.track_out, f"clip_{ci}.npz"), queries=queries[ci], **p)
+    if args.seg:
+        out["davis"] = reduce_davis(segs, dist, torch.device("cpu") if (world > 1 and shared) else dev)
+        if args.seg_out:
+            from PIL import Image
+            for ci, seg in segs.items():
+                d = os.path.join(args.seg_out, f"clip_{ci}")
+                os.makedirs(d, exist_ok=True)
+                for t in range(len(seg["masks"])):
+                    if seg["valid"][t]:                      # (no file for a frame without a mask, like the reference)
+                        Image.fromarray(seg["masks"][t]).save(os.path.join(d, f"move_mask_{t:05d}.png"))
     if rank == 0:
         out["frames_per_s"] = out["frames"] / out["wall_s"]
         out["iterations_per_s"] = out["iterations"] / out["wall_s"]

@@ -109,6 +109,7 @@ class SimpleGaussian:
         if log_dir is not None:
             os.makedirs(log_dir, exist_ok=True)
         self.move_seg = None
+        self.seg_recorder = None          # segmentation.MoveSegRecorder of the clip being fitted (fit_clip(segment=True))
         self.iterations_done = 0          # bookkeeping for throughput reports
         self.rasterisations_done = 0
         # ---- what exists only once something has happened: None until then
@@ -481,6 +482,9 @@ class SimpleGaussian:
                 self.move_seg = (FastConcaveHull2D(pts).mask(W, H) * 255).astype(np.uint8)
                 # cv2.erode(move_seg, ones((20, 20))): minimum over x-10 .. x+9, nothing eroded from the border
                 self.move_seg_erode = minimum_filter(self.move_seg, size=20, mode="constant", cval=255)
+        if self.seg_recorder is not None:
+            # the same two tensors, kept for the end of the clip: the masks of every frame are built then, from one copy
+            self.seg_recorder.record(uv_d, within & ~self.still_mask[:uv_d.shape[0]])
         if self.mask_prompt_pts is not None:
             # trainer.py:611-619: the first frame's mask prompt, carried by the splats that lay under it: the smoothed
             # concave hull of where THOSE splats project now (the reference builds it after every joint train() once

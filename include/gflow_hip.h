@@ -102,8 +102,9 @@ typedef enum gfl_status {
  * (gfl_tile_sort_with_slots is gone, gfl_tile_sort_ordered / _reserved lost their rec / slot_inv / slot_pool arguments): the
  * per-splat launch finds its pair rows without one.  303: GFL_PIXEL_CENTER, gfl_constants_n.  304: gfl_fit_state.cu_count.
  * 305: gfl_fit_state.flags (was reserved_) and GFL_FIT_DETERMINISTIC, gfl_scan_f64.  306: gfl_track_anchor, gfl_track_frame.
+ * 307: gfl_seg_score.
  * A binding checks gfl_version() >= GFL_VERSION of the header it was written for. */
-#define GFL_VERSION 306
+#define GFL_VERSION 307
 int gfl_version(void);
 /* out[10] = TILE, NEAREST, EXTENT, FOV_CLAMP, LOWPASS, EIG_FLOOR, RADIUS_SIGMA, ALPHA_MIN, ALPHA_MAX, T_MIN of this build */
 int gfl_constants(float* out10);
@@ -507,6 +508,23 @@ int gfl_track_anchor(const float* uv, int uv_stride, int N, const double* query_
 int gfl_track_frame(const float* uv, int uv_stride, const float* depth, int depth_stride, int N, const float* depth_map,
                     int W, int H, const int32_t* anchor, const double* shift_xy, int n_anchored, int frame, int T,
                     float occ_threshold, float* tracks, uint8_t* occluded, gfl_stream_t stream);
+
+/* ---- moving-region segmentation score (307; gflow_amd/segmentation.py, INTEGRATION.md "Moving-region segmentation") ----
+ * The sums behind the reference's per-frame J and F (gflow/benchmark.py:244-285, utils/measures/jaccard.py:14-34,
+ * utils/measures/f_boundary.py:15-132) for a whole clip in one launch.  pred, gt: [T][H][W] uint8, nonzero = foreground.
+ * valid: [T] or NULL; a frame with valid[t] == 0 is not read and its row of counts is zero.  counts: [T][6] uint32,
+ * WRITTEN (not accumulated) by the call:
+ *   0 inter = |pred & gt|        1 uni = |pred | gt|
+ *   2 n_fg, 3 n_gt: boundary pixels of pred / of gt -- seg2bmap at equal size: a pixel that differs from its right, lower
+ *     or lower-right neighbour; in the last row only the right neighbour counts, in the last column only the lower one,
+ *     the bottom-right pixel never
+ *   4 fg_match: boundary pixels of pred with a boundary pixel of gt at (dx, dy), dx^2 + dy^2 <= radius^2 (pixels outside
+ *     the image contribute nothing: binary_dilation with disk(radius) and a zero border; the disc is symmetric, so this
+ *     is the reference's boundary * dilated_other)        5 gt_match: the same with pred and gt exchanged
+ * radius in [1, 64], else GFL_ERR_INVALID; T == 0 is GFL_OK.  Integer sums: deterministic in every mode.  No allocation,
+ * no workspace, no host synchronisation (a memset of counts and one launch on `stream`). */
+int gfl_seg_score(const uint8_t* pred, const uint8_t* gt, const uint8_t* valid, int T, int H, int W, int radius,
+                  uint32_t* counts, gfl_stream_t stream);
 
 /* sizeof(gfl_fit_state), sizeof(gfl_fit_hyper): lets an FFI binding verify its struct mirrors */
 int gfl_abi_sizes(int* sizeof_fit_state, int* sizeof_fit_hyper);
