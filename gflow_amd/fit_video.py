@@ -135,6 +135,75 @@ def reduce_davis(segs, dist=None, device="cpu"):
     return out
 
 
+RECON_KEYS = ("PSNR", "SSIM")
+
+
+def reduce_recon(recons, dist=None, device="cpu"):
+    """The "recon" block of the JSON line: every clip's PSNR and SSIM (quality.evaluate: means over its frames), averaged over
+    the clips as reduce_davis does; ``frames`` is their total.  Over ranks by ONE more small all-reduce(SUM) of (the two
+    sums, frames, clips)."""
+    from . import quality as QL
+    sums, frames, clips = [0.0] * len(RECON_KEYS), 0, 0
+    for rec in recons.values():
+        m = QL.evaluate(rec)
+        if m["frames"]:
+            for k, key in enumerate(RECON_KEYS):
+                sums[k] += m[key]
+            frames += m["frames"]
+            clips += 1
+    vec = torch.tensor(sums + [float(frames), float(clips)], dtype=torch.float64, device=device)
+    if dist is not None and dist.is_initialized():
+        dist.all_reduce(vec, op=dist.ReduceOp.SUM)
+    v = vec.tolist()
+    clips = v[len(RECON_KEYS) + 1]
+    out = {k: v[i] / clips if clips else float("nan") for i, k in enumerate(RECON_KEYS)}
+    out["frames"] = int(v[len(RECON_KEYS)])
+    out["clips"] = int(clips)
+    return out
+
+
+CAMERA_KEYS = ("ATE", "RPE_t", "RPE_r")
+
+
+def reduce_camera(cams, dist=None, device="cpu"):
+    """The "camera" block of the JSON line: every clip's ATE, RPE_t and RPE_r (fit_clip's ``out["camera"]``), averaged over
+    the clips that have a score; a clip whose score is None (camera.evaluate: no alignment exists) counts in
+    ``clips_unscored``, not in the mean.  The three are None when no clip was scored.  Over ranks by ONE more small
+    all-reduce(SUM) of (the three sums, clips, clips unscored)."""
+    sums, clips, unscored = [0.0] * len(CAMERA_KEYS), 0, 0
+    for cam in cams.values():
+        if any(cam[k] is None for k in CAMERA_KEYS):
+            unscored += 1
+            continue
+        for k, key in enumerate(CAMERA_KEYS):
+            sums[k] += float(cam[key])
+        clips += 1
+    vec = torch.tensor(sums + [float(clips), float(unscored)], dtype=torch.float64, device=device)
+    if dist is not None and dist.is_initialized():
+        dist.all_reduce(vec, op=dist.ReduceOp.SUM)
+    v = vec.tolist()
+    clips = v[len(CAMERA_KEYS)]
+    out = {k: v[i] / clips if clips else None for i, k in enumerate(CAMERA_KEYS)}
+    out["clips"] = int(clips)
+    out["clips_unscored"] = int(v[len(CAMERA_KEYS) + 1])
+    return out
+
+
+def csv_metrics(out):
+    """The JSON line's blocks under the reference's metrics.csv keys (quality.CSV_KEYS); only the blocks that are there"""
+    m = {}
+    if "recon" in out:
+        m.update({"PSNR": out["recon"]["PSNR"], "SSIM": out["recon"]["SSIM"]})
+    if "tapvid" in out:
+        m.update({"Occlusion_Accuracy": out["tapvid"]["occlusion_accuracy"], "Average_Jaccard": out["tapvid"]["average_jaccard"],
+                  "Average_PTS_within_threshold": out["tapvid"]["average_pts_within_thresh"]})
+    if "davis" in out:
+        m.update({"J_zero": out["davis"]["J"], "F_zero": out["davis"]["F"], "J&F_zero": out["davis"]["J&F"]})
+    if "camera" in out:
+        m.update({k: out["camera"][k] for k in CAMERA_KEYS})
+    return m
+
+
 _FIT_STREAMS = {}
 
 
@@ -242,7 +311,7 @@ def stage_kwargs(c, frames, i, stage):
 
 
 def fit_clip(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, log=None, load_extr=True, keep=None,
-             async_snapshots=None, deterministic=None, track_queries=None, segment=False):
+             async_snapshots=None, deterministic=None, track_queries=None, segment=False, recon=False, camera=False):
     """Fit one clip; returns the metrics dict of this clip (PSNR summed over its frames; with ``cfg["traj_num"]`` > 0 also
     ``"traj"``: the per-frame trajectory images and seed projections, host arrays -- what the reference's frame loop collects in
     ``frames_sequence_traj / frames_sequence_traj_upon / sequence_traj``).
@@ -262,7 +331,15 @@ def fit_clip(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, 
     (gflow_amd.segmentation.MoveSegRecorder; INTEGRATION.md, "Moving-region segmentation"): the dict then has
     ``"segmentation"`` = dict(masks (T, H, W) uint8, valid (T,) bool, counts (T, 6) int64, J, F, JF (T,) float64).  Nothing
     is read back while the clip is fitted.  ``keep["record_seg_inputs"] = True``: the per-frame (uv, sel) the masks are
-    built from, cloned, in ``keep["seg_inputs"]`` (None for a frame without a joint stage)."""
+    built from, cloned, in ``keep["seg_inputs"]`` (None for a frame without a joint stage).
+    ``recon``: also every frame's reconstruction score (gflow_amd.quality.ReconRecorder; INTEGRATION.md, "Reconstruction
+    score"): where the frame's PSNR is taken, one gfl_recon_frame call on ``last_render`` and ``gt_image``; the dict then has
+    ``"recon"`` = dict(sse, ssim_sum, PSNR, SSIM (T,) float64).  ``keep["record_recon_inputs"] = True``: a clone of each
+    frame's ``last_render[:3]`` in ``keep["recon_inputs"]``.
+    ``camera``: also the camera path and its score (gflow_amd.camera; INTEGRATION.md, "Camera score"): the dict then has
+    ``"camera"`` = dict(extr (T, 3, 4) float32 -- every frame's ``get_extr()`` at its end --, ATE, RPE_t, RPE_r: floats or
+    None) against each frame's ``extr_gt`` if it has one, else its ``extr``; a frame with neither is a ValueError before
+    anything is fitted."""
     if deterministic and not fused:
         raise ValueError("fit_clip(deterministic=True) needs fused=True: the operator path's alpha_blending backward has no "
                          "deterministic implementation")
@@ -270,7 +347,8 @@ def fit_clip(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, 
     dev_ = torch.device(device)
     g = fit_clip_steps(frames, device, cfg=cfg, seed=seed, snapshot_interval=snapshot_interval, fused=fused, log=log,
                        load_extr=load_extr, chunk=None, keep=keep, deterministic=deterministic, track_queries=track_queries,
-                       segment=segment, **({} if async_snapshots is None else {"async_snapshots": async_snapshots}))
+                       segment=segment, recon=recon, camera=camera,
+                       **({} if async_snapshots is None else {"async_snapshots": async_snapshots}))
 
     drive = lambda: run_to_end(g)
     if dev_.type == "cuda" and torch.cuda.current_stream(dev_) == torch.cuda.default_stream(dev_):
@@ -290,7 +368,8 @@ def fit_clip(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, 
 
 
 def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, log=None, load_extr=True, chunk=None,
-                   async_snapshots=True, keep=None, cu_count=0, deterministic=None, track_queries=None, segment=False):
+                   async_snapshots=True, keep=None, cu_count=0, deterministic=None, track_queries=None, segment=False,
+                   recon=False, camera=False):
     """fit_clip as a generator: yields after every ``chunk`` iterations of a stage (None: never) and returns the metrics
     dict.  The caller owns the stream the work is enqueued on (fit_clips_concurrent gives every clip its own)."""
     from .trainer import SimpleGaussian
@@ -303,6 +382,14 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
     if track_queries is not None:
         from .tracking import Tracker
         tracker = Tracker(track_queries, len(frames), device)        # (ValueError before anything is fitted)
+    cam_rec = None
+    if camera:
+        from .camera import CameraRecorder
+        cam_gt = [fr["extr_gt"] if fr.get("extr_gt") is not None else fr.get("extr") for fr in frames]
+        missing = [t for t, e in enumerate(cam_gt) if e is None]
+        if missing:
+            raise ValueError(f"fit_clip(camera=True): frames {missing} carry neither extr_gt nor extr")
+        cam_rec = CameraRecorder(len(frames))
     tr = SimpleGaussian(f0["image"], f0["depth"], num_points=c["num_points"], background=c["background"],
                         device=device, seed=seed, fused=fused, deterministic=deterministic)
     tr.async_snapshots = bool(async_snapshots)       # (trainer.py: snapshots composed beside the next iterations, or behind theirs)
@@ -310,6 +397,10 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
     if segment:
         from .segmentation import MoveSegRecorder
         tr.seg_recorder = MoveSegRecorder(len(frames), tr.H, tr.W, tr.device)
+    recon_rec = None
+    if recon:
+        from .quality import ReconRecorder
+        recon_rec = ReconRecorder(len(frames), tr.H, tr.W, tr.device)
     tr.load_camera(focal=f0["focal"], pp=f0["pp"])
     if load_extr and f0.get("extr") is not None:
         tr.load_camera(extr=f0["extr"])
@@ -373,6 +464,17 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
             if keep is not None and keep.get("record_track_inputs"):
                 keep.setdefault("track_inputs", []).append((uv.clone(), depth.clone(), dm.clone()))
 
+    def record_scores(i):
+        # benchmark.py:191-230 and :323-329 for frame i, on what the frame's PSNR is taken from and what save_checkpoint
+        # stores: two small launches that write one row of the clip's sums, and a clone of the pose; nothing is read back
+        with torch.no_grad():
+            if recon_rec is not None:
+                recon_rec.frame(i, tr.last_render, tr.gt_image)
+                if keep is not None and keep.get("record_recon_inputs"):
+                    keep.setdefault("recon_inputs", []).append(tr.last_render[:3].clone())
+            if cam_rec is not None:
+                cam_rec.frame(i, tr.get_extr())
+
     def draw_trajectories():
         from . import msplat
         from . import render as render_mod
@@ -400,6 +502,8 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
     # (PSNR stays on the device and is read ONCE at the end of the clip: a float() per frame drained the queue between
     #  two frames; with a log callback the caller asked for the numbers as they come)
     psnr_sum = tr.psnr().double()
+    if recon_rec is not None or cam_rec is not None:
+        record_scores(0)
     if keep is not None:
         keep["trainer"], keep["psnr"] = tr, [psnr_sum]
     if log:
@@ -417,6 +521,8 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
             record_tracks(i, shared)
         p = tr.psnr()
         psnr_sum = psnr_sum + p.double()
+        if recon_rec is not None or cam_rec is not None:
+            record_scores(i)
         if keep is not None:
             keep["psnr"].append(p)
         if log:
@@ -457,16 +563,25 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
         if keep is not None and keep.get("record_seg_inputs"):
             keep["seg_inputs"] = [None if x is None else (x[0].clone(), x[1].clone()) for x in rec.inputs]
         out["segmentation"] = rec.result([fr["move_mask"] for fr in frames])
+    if recon_rec is not None:
+        out["recon"] = recon_rec.result()             # (one copy of the (T, 2) sums)
+    if cam_rec is not None:
+        import numpy as np
+        from . import camera as CM
+        extr = cam_rec.result()                       # (one stacked copy)
+        gt = np.stack([torch.as_tensor(e).detach().cpu().double().numpy().reshape(3, 4) for e in cam_gt])
+        out["camera"] = dict(extr=extr, **CM.evaluate(extr, gt))
     return out
 
 
 # the keys of fit_clip's dict that are per-clip numbers (sums over clips make sense); "traj" is the trajectory output,
-# "tracks" the tracker's, "segmentation" the moving-region masks and their score
+# "tracks" the tracker's, "segmentation" the moving-region masks and their score, "recon" and "camera" the per-frame
+# reconstruction sums and the camera path with its score
 NUMERIC_KEYS = ("psnr_sum", "frames", "iterations", "rasterisations", "clips", "splats_final", "void_iterations")
 
 
 def fit_clips_concurrent(clips, device, cfg=None, seeds=None, snapshot_interval=0, chunk=32, partition=False,
-                         deterministic=None, track_queries=None, segment=False):
+                         deterministic=None, track_queries=None, segment=False, recon=False, camera=False, load_extr=True):
     """Fit several clips AT THE SAME TIME on ONE device, in one host thread: every clip has its own trainer, engine and
     STREAM, and the clips take turns enqueueing ``chunk`` iterations each (fit_clip_steps), so their graph launches
     interleave on the device.  One fit leaves the chip partly idle -- its kernels are a chain of dependent launches,
@@ -483,8 +598,8 @@ def fit_clips_concurrent(clips, device, cfg=None, seeds=None, snapshot_interval=
     on it (the schedule never enters a result).  Measured in bench.py's ``clips_per_gpu`` table.
     ``deterministic`` (None: torch's switch): every clip's result is bit for bit that of fit_clip(..., deterministic=True)
     with the same seed -- without ``partition``, which changes the number of tile queues (include/gflow_hip.h).
-    ``track_queries``: None, or one entry (fit_clip's ``track_queries``, or None) per clip.  ``segment``: fit_clip's, for
-    all clips."""
+    ``track_queries``: None, or one entry (fit_clip's ``track_queries``, or None) per clip.  ``segment``, ``recon``,
+    ``camera``, ``load_extr``: fit_clip's, for all clips."""
     n = len(clips)
     if track_queries is not None and len(track_queries) != n:
         raise ValueError("fit_clips_concurrent: track_queries needs one entry per clip")
@@ -506,7 +621,8 @@ def fit_clips_concurrent(clips, device, cfg=None, seeds=None, snapshot_interval=
     #  engine per clip cost them more than they give)
     gens = [fit_clip_steps(clips[i], dev, cfg, seed=seeds[i], snapshot_interval=snapshot_interval, chunk=chunk,
                            async_snapshots=n == 1, cu_count=shares[i][1] if shares else 0, deterministic=deterministic,
-                           track_queries=None if track_queries is None else track_queries[i], segment=segment)
+                           track_queries=None if track_queries is None else track_queries[i], segment=segment,
+                           recon=recon, camera=camera, load_extr=load_extr)
             for i in range(n)]
     results = [None] * n
     live = list(range(n))
@@ -553,6 +669,17 @@ def main(argv=None):
                          "and J&F (a \"davis\" block in the line)")
     ap.add_argument("--seg-out", default=None,
                     help="with --seg: write each clip's masks to DIR/clip_<i>/move_mask_<frame>.png")
+    ap.add_argument("--recon", action="store_true",
+                    help="score every frame's render with PSNR and SSIM on the device (a \"recon\" block in the line)")
+    ap.add_argument("--camera", action="store_true",
+                    help="keep every frame's camera and score the path against the clip's own (extr_gt, else extr) with "
+                         "ATE and RPE (a \"camera\" block in the line)")
+    ap.add_argument("--no-load-extr", action="store_true",
+                    help="do not load the frames' camera poses (extr): the camera-only stages estimate them, as the "
+                         "reference's scripts/fit_video.sh runs")
+    ap.add_argument("--metrics-csv", default=None,
+                    help="rank 0 writes the blocks that were asked for as key,value lines under the reference's "
+                         "metrics.csv keys")
     args = ap.parse_args(argv)
     det = True if args.deterministic else None
     from . import synthetic as S
@@ -618,17 +745,19 @@ def main(argv=None):
     t0 = time.perf_counter()
     c = max(1, args.clips_per_gpu)
     order = sorted(clips, key=lambda j: (-lengths[j], j))          # (clips of similar length share the GPU)
-    preds, segs = {}, {}
+    preds, segs, recons, cams = {}, {}, {}, {}
+    load_extr = not args.no_load_extr
     for g0 in range(0, len(order), c):
         group = order[g0:g0 + c]
         if len(group) == 1:
             ci = group[0]
             res = [fit_clip(clips[ci], dev, cfg, seed=ci, deterministic=det, track_queries=queries.get(ci), segment=args.seg,
+                            recon=args.recon, camera=args.camera, load_extr=load_extr,
                             log=(lambda s, ci=ci: print(f"[rank {rank} clip {ci}] {s}")) if args.verbose else None)]
         else:
             res = fit_clips_concurrent([clips[ci] for ci in group], dev, cfg, seeds=group, deterministic=det,
                                        track_queries=[queries.get(ci) for ci in group] if args.track else None,
-                                       segment=args.seg)
+                                       segment=args.seg, recon=args.recon, camera=args.camera, load_extr=load_extr)
         for ci, m in zip(group, res):
             for k in METRIC_NAMES:
                 local[k] += m[k]
@@ -636,6 +765,10 @@ def main(argv=None):
                 preds[ci] = m["tracks"]
             if "segmentation" in m:
                 segs[ci] = m["segmentation"]
+            if "recon" in m:
+                recons[ci] = m["recon"]
+            if "camera" in m:
+                cams[ci] = m["camera"]
     torch.cuda.synchronize()
     out = reduce_metrics(local, time.perf_counter() - t0, dist, torch.device("cpu") if (world > 1 and shared) else dev,
                          rank=rank, world=world)
@@ -657,6 +790,13 @@ def main(argv=None):
                 for t in range(len(seg["masks"])):
                     if seg["valid"][t]:                      # (no file for a frame without a mask, like the reference)
                         Image.fromarray(seg["masks"][t]).save(os.path.join(d, f"move_mask_{t:05d}.png"))
+    if args.recon:
+        out["recon"] = reduce_recon(recons, dist, torch.device("cpu") if (world > 1 and shared) else dev)
+    if args.camera:
+        out["camera"] = reduce_camera(cams, dist, torch.device("cpu") if (world > 1 and shared) else dev)
+    if rank == 0 and args.metrics_csv:
+        from .quality import write_metrics_csv
+        write_metrics_csv(args.metrics_csv, csv_metrics(out))
     if rank == 0:
         out["frames_per_s"] = out["frames"] / out["wall_s"]
         out["iterations_per_s"] = out["iterations"] / out["wall_s"]

@@ -102,9 +102,9 @@ typedef enum gfl_status {
  * (gfl_tile_sort_with_slots is gone, gfl_tile_sort_ordered / _reserved lost their rec / slot_inv / slot_pool arguments): the
  * per-splat launch finds its pair rows without one.  303: GFL_PIXEL_CENTER, gfl_constants_n.  304: gfl_fit_state.cu_count.
  * 305: gfl_fit_state.flags (was reserved_) and GFL_FIT_DETERMINISTIC, gfl_scan_f64.  306: gfl_track_anchor, gfl_track_frame.
- * 307: gfl_seg_score.
+ * 307: gfl_seg_score.  308: gfl_recon_frame.
  * A binding checks gfl_version() >= GFL_VERSION of the header it was written for. */
-#define GFL_VERSION 307
+#define GFL_VERSION 308
 int gfl_version(void);
 /* out[10] = TILE, NEAREST, EXTENT, FOV_CLAMP, LOWPASS, EIG_FLOOR, RADIUS_SIGMA, ALPHA_MIN, ALPHA_MAX, T_MIN of this build */
 int gfl_constants(float* out10);
@@ -525,6 +525,25 @@ int gfl_track_frame(const float* uv, int uv_stride, const float* depth, int dept
  * no workspace, no host synchronisation (a memset of counts and one launch on `stream`). */
 int gfl_seg_score(const uint8_t* pred, const uint8_t* gt, const uint8_t* valid, int T, int H, int W, int radius,
                   uint32_t* counts, gfl_stream_t stream);
+
+/* ---- reconstruction score of one frame (308; gflow_amd/quality.py, INTEGRATION.md "Reconstruction score") ----------
+ * The two sums behind the reference's per-image PSNR and SSIM (gflow/benchmark.py:191-230: piqa.PSNR() / piqa.SSIM() on the
+ * saved PNG).  render: planes r, g, b, [>=3][H][W] float32 (the fused forward's render or any CHW image); gt_rgb: [H][W][3].
+ *   prediction: the saved byte k = uint8(clamp(x, 0, 1) * 255), float32 with truncation (render2img), read back as
+ *     p = (double)((float)k / 255.0f);  target: g = (double)clamp(gt, 0, 1);  everything after that is float64
+ *   sse      = sum of (p - g)^2 over all 3 H W values
+ *   ssim_sum = sum of the SSIM map over the 3 channels and the (H - 10)(W - 10) valid window positions (no padding, piqa's
+ *     default): window w[i] ~ exp(-(i - 5)^2 / (2 * 1.5^2)), 11 taps, normalised, separable; mu_x, mu_y, E[x^2], E[y^2],
+ *     E[xy] under the window, s_xx = E[x^2] - mu_x^2 (s_yy, s_xy likewise);
+ *     ss = (2 mu_x mu_y + C1)(2 s_xy + C2) / ((mu_x^2 + mu_y^2 + C1)(s_xx + s_yy + C2)), C1 = 1e-4, C2 = 9e-4
+ * On the host: PSNR = 10 log10(1 / (sse / (3 H W) + 1e-8)), SSIM = ssim_sum / (3 (H - 10)(W - 10)).
+ * sums: [T][2] float64; row `frame` is WRITTEN {sse, ssim_sum}, the other rows are not touched.  H < 11, W < 11 or frame
+ * outside [0, T): GFL_ERR_INVALID.  workspace: gfl_recon_workspace_bytes(W, H) (per-workgroup partial sums).  Two launches
+ * (tiles, then an ordered fold), no atomics: the same bits on every call, in every mode.  No allocation, no host
+ * synchronisation; callable on the fit's stream between graph replays. */
+size_t gfl_recon_workspace_bytes(int W, int H);
+int gfl_recon_frame(const float* render, const float* gt_rgb, int W, int H, int frame, int T, double* sums, void* workspace,
+                    size_t workspace_bytes, gfl_stream_t stream);
 
 /* sizeof(gfl_fit_state), sizeof(gfl_fit_hyper): lets an FFI binding verify its struct mirrors */
 int gfl_abi_sizes(int* sizeof_fit_state, int* sizeof_fit_hyper);
