@@ -23,7 +23,7 @@ _lib = None
 
 c_void_p, c_int, c_float, c_size_t, c_int64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_int64
 
-MIN_VERSION = 308          # GFL_VERSION of the include/gflow_hip.h this binding mirrors (gfl_recon_frame)
+MIN_VERSION = 309          # GFL_VERSION of the include/gflow_hip.h this binding mirrors (the *_bwd_cam entries)
 
 # name -> (restype, argtypes); mirrors include/gflow_hip.h one to one
 _P = c_void_p
@@ -35,12 +35,15 @@ SIGNATURES = {
     "gfl_status_string": (ctypes.c_char_p, [c_int]),
     "gfl_last_hip_error": (c_int, []),
     "gfl_reduce_workspace_bytes": (c_size_t, [c_int]),
+    "gfl_reduce_cam_workspace_bytes": (c_size_t, [c_int]),
     "gfl_project_point_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, c_float, _P, _P, _P]),
     "gfl_project_point_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, c_size_t, _P]),
+    "gfl_project_point_bwd_cam": (c_int, [_P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "gfl_cov3d_fwd": (c_int, [_P, _P, _P, c_int, _P, _P]),
     "gfl_cov3d_bwd": (c_int, [_P, _P, _P, _P, c_int, _P, _P, _P]),
     "gfl_ewa_fwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P]),
     "gfl_ewa_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "gfl_ewa_bwd_cam": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
     "gfl_bin_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "gfl_bin_count": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P]),
     "gfl_bin_sort": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P, c_size_t, _P]),
@@ -72,6 +75,7 @@ SIGNATURES = {
     "gfl_fit_iteration_snapshot": (c_int, [_P, _P, _P, _P, _P]),
     "gfl_render_fwd": (c_int, [_P, _P, _P]),
     "gfl_render_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "gfl_render_bwd_cam": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gfl_fit_prepare_targets": (c_int, [_P, _P]),
     "gfl_fit_schedule_info": (c_int, [_P, _P, _P, _P, _P]),
     "gfl_fit_schedule_info_fwd": (c_int, [_P, _P, _P, _P, _P]),

@@ -274,11 +274,11 @@ __device__ __forceinline__ void block_reduce_store(float (&vals)[NV], float* __r
     }
 }
 
+// one block; thread t folds rows t, t+256, ... in order, then a fixed-shape
+// wave/LDS tree combines the 256 partials: bitwise reproducible run to run.
+// Returns channel threadIdx.x's total to the threads below NV.
 template <int NV>
-__global__ void __launch_bounds__(256) fold_partials_kernel(const float* __restrict__ partial, int rows,
-                                                            float* __restrict__ out) {
-    // one block; thread t folds rows t, t+256, ... in order, then a fixed-shape
-    // wave/LDS tree combines the 256 partials: bitwise reproducible run to run.
+__device__ __forceinline__ float fold_partials_block(const float* __restrict__ partial, int rows) {
     float acc[NV];
 #pragma unroll
     for (int k = 0; k < NV; ++k) acc[k] = 0.f;
@@ -295,7 +295,26 @@ __global__ void __launch_bounds__(256) fold_partials_kernel(const float* __restr
         if (lane == 63) red[wid][k] = s;
     }
     __syncthreads();
-    if (threadIdx.x < NV) out[threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+    if (threadIdx.x < NV) return red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+    return 0.f;
+}
+
+template <int NV>
+__global__ void __launch_bounds__(256) fold_partials_kernel(const float* __restrict__ partial, int rows,
+                                                            float* __restrict__ out) {
+    const float t = fold_partials_block<NV>(partial, rows);
+    if (threadIdx.x < NV) out[threadIdx.x] = t;
+}
+
+// rows that hold two gradients side by side (N0 + N1 channels; 12 extr + 4 intr): the same fold, each to its own output.
+// A channel's sum is formed exactly as fold_partials_kernel forms it: out0 has the bits fold_partials_kernel<N0> gives for
+// rows of N0 alone.
+template <int N0, int N1>
+__global__ void __launch_bounds__(256) fold_partials_split_kernel(const float* __restrict__ partial, int rows,
+                                                                  float* __restrict__ out0, float* __restrict__ out1) {
+    const float t = fold_partials_block<N0 + N1>(partial, rows);
+    if (threadIdx.x < N0) out0[threadIdx.x] = t;
+    else if (threadIdx.x < N0 + N1) out1[threadIdx.x - N0] = t;
 }
 
 constexpr int REDUCE_BLOCK = 256;

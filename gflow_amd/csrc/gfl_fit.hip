@@ -92,7 +92,9 @@ size_t gfl_fit_workspace_bytes(int cap, int K_cap, int W, int H) {
            + up256((size_t)2 * fit_nblk(cap > 0 ? cap : 1) * sizeof(int32_t))          // rows of the scale term per 256 splats
            + up256((T * 4 + SORT_ORDER_TRAILER) * sizeof(int32_t))                     // the tile sort's order (+ its split list)
            + up256((T * 4 + SORT_ORDER_TRAILER) * sizeof(int32_t))                     // reserved tile regions: the next sort order,
-           + up256(T * sizeof(int4)) + up256(T * sizeof(int32_t));                      //   {start, capacity, position} per tile, fill counters
+           + up256(T * sizeof(int4)) + up256(T * sizeof(int32_t))                       //   {start, capacity, position} per tile, fill counters
+           + up256((size_t)reduce_rows(cap > 0 ? cap : 1) * 4 * sizeof(float))         // gfl_render_bwd_cam: intr partials,
+           + up256((size_t)(cap > 0 ? cap : 1) * REC * sizeof(float));                  //   the rows its two launches hand over
 }
 
 
@@ -157,6 +159,8 @@ static FitWs carve(const gfl_fit_state* st) {
     w.sort_order_next = (int4*)((char*)w.sort_order + up256((T * 4 + SORT_ORDER_TRAILER) * sizeof(int32_t)));
     w.region = (int4*)((char*)w.sort_order_next + up256((T * 4 + SORT_ORDER_TRAILER) * sizeof(int32_t)));
     w.fill = (int32_t*)((char*)w.region + up256(T * sizeof(int4)));
+    w.partial_cam = (float*)((char*)w.fill + up256(T * sizeof(int32_t)));
+    w.d_rec_cam = (float*)((char*)w.partial_cam + up256((size_t)reduce_rows(st->cap > 0 ? st->cap : 1) * 4 * sizeof(float)));
     return w;
 }
 
@@ -431,11 +435,9 @@ int gfl_render_fwd(const gfl_fit_state* st, const gfl_fit_hyper* hp, gfl_stream_
     return fit_forward_impl(st, hp, stream, 1);
 }
 
-int gfl_render_bwd(const gfl_fit_state* st, const gfl_fit_hyper* hp, const float* d_render, const float* d_uv,
-                   const float* d_depth, float* d_params, float* d_extr, gfl_stream_t stream) {
-    int rc = fit_check(st, hp);
-    if (rc) return rc;
-    if (!d_render || !d_params || !d_extr) return GFL_ERR_INVALID;
+// d_intr == nullptr: gfl_render_bwd (12 camera accumulators); otherwise gfl_render_bwd_cam (16)
+static int render_bwd_impl(const gfl_fit_state* st, const gfl_fit_hyper* hp, const float* d_render, const float* d_uv,
+                           const float* d_depth, float* d_params, float* d_extr, float* d_intr, gfl_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     const int gx = (st->W + GFL_TILE - 1) / GFL_TILE, gy = (st->H + GFL_TILE - 1) / GFL_TILE, T = gx * gy;
     const FitWs w = carve(st);
@@ -447,9 +449,30 @@ int gfl_render_bwd(const gfl_fit_state* st, const gfl_fit_hyper* hp, const float
     {
         StageScope p(ST_PRE_BWD_ADAM, s);
         const NextSched ns = next_sched(w, reduce_rows(st->N > 0 ? st->N : 1), T);
-        launch_splat_bwd_op(st, w, gx, gy, ns, next_sched_blocks(w, T), next_sched_lds(w, T), d_uv, d_depth, d_params, d_extr, s);
+        if (d_intr)
+            launch_splat_bwd_op_cam(st, w, gx, gy, ns, next_sched_blocks(w, T), next_sched_lds(w, T), d_uv, d_depth, d_params, d_extr,
+                                    d_intr, s);
+        else
+            launch_splat_bwd_op(st, w, gx, gy, ns, next_sched_blocks(w, T), next_sched_lds(w, T), d_uv, d_depth, d_params, d_extr, s);
     }
     return check_launch();
+}
+
+int gfl_render_bwd(const gfl_fit_state* st, const gfl_fit_hyper* hp, const float* d_render, const float* d_uv,
+                   const float* d_depth, float* d_params, float* d_extr, gfl_stream_t stream) {
+    int rc = fit_check(st, hp);
+    if (rc) return rc;
+    if (!d_render || !d_params || !d_extr) return GFL_ERR_INVALID;
+    return render_bwd_impl(st, hp, d_render, d_uv, d_depth, d_params, d_extr, nullptr, stream);
+}
+
+int gfl_render_bwd_cam(const gfl_fit_state* st, const gfl_fit_hyper* hp, const float* d_render, const float* d_uv,
+                       const float* d_depth, float* d_params, float* d_extr, float* d_intr, gfl_stream_t stream) {
+    if (!d_extr || !d_intr) return GFL_ERR_INVALID;
+    int rc = fit_check(st, hp);
+    if (rc) return rc;
+    if (!d_render || !d_params) return GFL_ERR_INVALID;
+    return render_bwd_impl(st, hp, d_render, d_uv, d_depth, d_params, d_extr, d_intr, stream);
 }
 
 int gfl_fit_backward_step(const gfl_fit_state* st, const gfl_fit_hyper* hp, gfl_stream_t stream) {

@@ -331,6 +331,8 @@ struct FitWs {
     int32_t* hist;
     unsigned long long* keys;
     float* partial;
+    float* partial_cam;         // gfl_render_bwd_cam, the last two carves: partial rows of 4 (intr) and, when the state has no
+    float* d_rec_cam;           //   d_rec of its own, the rows [cap][12] the per-splat launch leaves for the intrinsics launch
     int32_t* tile_counts;
     float* pair_grad;
     // pair rows (round 5): the backward blend writes the gradient row of the pair (splat g, tile) at a place the per-splat
@@ -396,6 +398,8 @@ void launch_splat_bwd_adam(const gfl_fit_state* st, const FitWs& w, int gx, int 
                            const NextSched& ns, int extra, size_t lds, hipStream_t s);
 void launch_splat_bwd_op(const gfl_fit_state* st, const FitWs& w, int gx, int gy, const NextSched& ns, int extra, size_t lds,
                          const float* d_uv, const float* d_depth, float* d_params, float* d_extr, hipStream_t s);
+void launch_splat_bwd_op_cam(const gfl_fit_state* st, const FitWs& w, int gx, int gy, const NextSched& ns, int extra, size_t lds,
+                             const float* d_uv, const float* d_depth, float* d_params, float* d_extr, float* d_intr, hipStream_t s);
 void launch_camera_adam(const gfl_fit_state* st, const FitWs& w, int rows, const float* p_ssim, int n_ssim, const float* p_grad,
                         int n_grad, const AdamCfg& ac_cam, const AdamCfg& ac_ab, int step_camera, hipStream_t s);
 #ifdef GFL_TRACE

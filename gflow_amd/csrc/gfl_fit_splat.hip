@@ -352,6 +352,39 @@ __global__ void __launch_bounds__(REDUCE_BLOCK) fused_preprocess_bwd_adam_kernel
     GFL_PHASE(3, 7);
 }
 
+// d_intr of the differentiable operator's backward (gfl_render_bwd_cam): a launch of its own BEHIND the per-splat one, which
+// stays the launch of gfl_render_bwd -- the same code object, so d_params and d_extr have its bits.  (As a second template
+// flag on that kernel, four more accumulators moved the last bit of the other gradients: the compiler packs and fuses the
+// shared arithmetic differently around them.)  Reads what that launch left in d_rec -- the row's gathered du dv dA dB | dC --,
+// adds the caller's dL/d uv, and reduces the four sums the way the extr partials are reduced.
+__global__ void __launch_bounds__(REDUCE_BLOCK) splat_intr_bwd_kernel(
+    const float* __restrict__ params, const float* __restrict__ intr, const float* __restrict__ extr,
+    const float* __restrict__ rec, const float* __restrict__ d_rec, const float* __restrict__ d_uv_in, int N, int W, int H,
+    float* __restrict__ partial) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    float e[4] = {0.f, 0.f, 0.f, 0.f};
+    if (i < N && rec[(size_t)i * REC + 9] != 0.f) {         // depth != 0: visible
+        const Cam c = load_cam(intr, extr);
+        const float4* prow = reinterpret_cast<const float4*>(params + (size_t)i * ROW);
+        const Splat s = splat_from_row(prow[0], prow[1], prow[2], prow[3], true);
+        const float4 g0 = reinterpret_cast<const float4*>(d_rec + (size_t)i * REC)[0];
+        const float dC = d_rec[(size_t)i * REC + 4];
+        float du = g0.x, dv = g0.y;
+        if (d_uv_in) { du += d_uv_in[2 * i]; dv += d_uv_in[2 * i + 1]; }
+        const float px = c.r00 * s.x + c.r01 * s.y + c.r02 * s.z + c.t0;
+        const float py = c.r10 * s.x + c.r11 * s.y + c.r12 * s.z + c.t1;
+        const float pz = c.r20 * s.x + c.r21 * s.y + c.r22 * s.z + c.t2;
+        float2 df = project_bwd_intr(px, py, pz, du, dv);
+        if (__float_as_int(rec[(size_t)i * REC + 11]) > 0) {   // radius > 0: the conic was produced
+            Cov6 cv;
+            cov3d_fwd(s.s, s.q, cv.v);
+            df = ewa_bwd_intr(c, px, py, pz, cv, g0.z, g0.w, dC, W, H, df);
+        }
+        e[0] = df.x; e[1] = df.y; e[2] = du; e[3] = dv;
+    }
+    block_reduce_store<4, REDUCE_BLOCK>(e, partial);
+}
+
 // camera + depth affine: fold the extr partials, chain to the pose, Adam, step += 1
 // One block of 1024 lanes also folds the loss partial rows (no separate fold launch): every lane
 // is at most a couple of loads deep, the tree has a fixed shape (reproducible).
@@ -477,6 +510,21 @@ void launch_splat_bwd_op(const gfl_fit_state* st, const FitWs& w, int gx, int gy
         gx, gy, st->N, st->W, st->H, nullptr, nullptr, nullptr, nullptr, nullptr, RegCfg{}, AdamCfg{}, nullptr, w.partial, d_uv,
         d_depth, d_params, nullptr, ns, nullptr);
     fold_partials_kernel<12><<<1, 256, 0, s>>>(w.partial, ns.rows, d_extr);
+}
+
+// the same with d_intr (gfl_render_bwd_cam): the per-splat launch also leaves its gathered rows in d_rec (the caller's, or a
+// carve of the workspace), the intrinsics launch reads them; partial rows of 4, folded in the same fixed order
+void launch_splat_bwd_op_cam(const gfl_fit_state* st, const FitWs& w, int gx, int gy, const NextSched& ns, int extra, size_t lds,
+                             const float* d_uv, const float* d_depth, float* d_params, float* d_extr, float* d_intr, hipStream_t s) {
+    float* d_rec = st->d_rec ? st->d_rec : w.d_rec_cam;
+    fused_preprocess_bwd_adam_kernel<true><<<ns.rows + extra, REDUCE_BLOCK, lds, s>>>(
+        st->params, nullptr, nullptr, st->intr, st->extr, st->rec, d_rec, w.pair_grad, w.wide_off, w.wide_base, w.stamp,
+        gx, gy, st->N, st->W, st->H, nullptr, nullptr, nullptr, nullptr, nullptr, RegCfg{}, AdamCfg{}, nullptr, w.partial, d_uv,
+        d_depth, d_params, nullptr, ns, nullptr);
+    fold_partials_kernel<12><<<1, 256, 0, s>>>(w.partial, ns.rows, d_extr);
+    splat_intr_bwd_kernel<<<ns.rows, REDUCE_BLOCK, 0, s>>>(st->params, st->intr, st->extr, st->rec, d_rec, d_uv, st->N, st->W,
+                                                            st->H, w.partial_cam);
+    fold_partials_kernel<4><<<1, 256, 0, s>>>(w.partial_cam, ns.rows, d_intr);
 }
 
 void launch_camera_adam(const gfl_fit_state* st, const FitWs& w, int rows, const float* p_ssim, int n_ssim, const float* p_grad,

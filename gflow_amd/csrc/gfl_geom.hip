@@ -23,14 +23,16 @@ __global__ void __launch_bounds__(256) project_fwd_kernel(const float* __restric
     depth[i] = p.vis ? p.pz : 0.f;
 }
 
+// NE = EXTR_ACC: partial rows of d_extr; NE = CAM_ACC: d_extr and d_intr in one row of 16 (gfl_project_point_bwd_cam)
+template <int NE>
 __global__ void __launch_bounds__(REDUCE_BLOCK) project_bwd_kernel(
     const float* __restrict__ xyz, const float* __restrict__ intr, const float* __restrict__ extr,
     const float* __restrict__ depth, const float* __restrict__ d_uv, const float* __restrict__ d_depth, int N,
     float* __restrict__ d_xyz, float* __restrict__ partial) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    float e[12];
+    float e[NE];
 #pragma unroll
-    for (int k = 0; k < 12; ++k) e[k] = 0.f;
+    for (int k = 0; k < NE; ++k) e[k] = 0.f;
     if (i < N) {
         const Cam c = load_cam(intr, extr);
         float dx = 0.f, dy = 0.f, dz = 0.f;
@@ -42,10 +44,14 @@ __global__ void __launch_bounds__(REDUCE_BLOCK) project_bwd_kernel(
             float gx, gy, gz;
             project_bwd_cam(c, px, py, pz, d_uv[2 * i], d_uv[2 * i + 1], d_depth[i], gx, gy, gz);
             cam_grad_to_world(c, x, y, z, gx, gy, gz, dx, dy, dz, e);
+            if constexpr (NE == CAM_ACC) {
+                const float2 df = project_bwd_intr(px, py, pz, d_uv[2 * i], d_uv[2 * i + 1]);
+                e[12] = df.x; e[13] = df.y; e[14] = d_uv[2 * i]; e[15] = d_uv[2 * i + 1];
+            }
         }
         d_xyz[3 * i] = dx; d_xyz[3 * i + 1] = dy; d_xyz[3 * i + 2] = dz;
     }
-    block_reduce_store<12, REDUCE_BLOCK>(e, partial);
+    block_reduce_store<NE, REDUCE_BLOCK>(e, partial);
 }
 
 // --------------------------------------------------------------------- cov3d
@@ -125,14 +131,15 @@ __global__ void __launch_bounds__(256) ewa_fwd_kernel(const float* __restrict__ 
     tiles[i] = nt;
 }
 
+template <int NE>      // (as project_bwd_kernel)
 __global__ void __launch_bounds__(REDUCE_BLOCK) ewa_bwd_kernel(
     const float* __restrict__ xyz, const float* __restrict__ cov3d, const float* __restrict__ intr,
     const float* __restrict__ extr, const int32_t* __restrict__ radius, const float* __restrict__ d_conic, int N,
     int W, int H, float* __restrict__ d_xyz, float* __restrict__ d_cov3d, float* __restrict__ partial) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    float e[12];
+    float e[NE];
 #pragma unroll
-    for (int k = 0; k < 12; ++k) e[k] = 0.f;
+    for (int k = 0; k < NE; ++k) e[k] = 0.f;
     if (i < N) {
         float dx = 0.f, dy = 0.f, dz = 0.f;
         float gcov[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -149,12 +156,18 @@ __global__ void __launch_bounds__(REDUCE_BLOCK) ewa_bwd_kernel(
             float gx, gy, gz;
             ewa_bwd(c, f, px, py, cov, d_conic[3 * i], d_conic[3 * i + 1], d_conic[3 * i + 2], gcov, gx, gy, gz, e);
             cam_grad_to_world(c, x, y, z, gx, gy, gz, dx, dy, dz, e);
+            if constexpr (NE == CAM_ACC) {
+                const Cov6 cv = {{cov[0], cov[1], cov[2], cov[3], cov[4], cov[5]}};
+                const float2 df = ewa_bwd_intr(c, px, py, pz, cv, d_conic[3 * i], d_conic[3 * i + 1], d_conic[3 * i + 2], W, H,
+                                               make_float2(0.f, 0.f));
+                e[12] = df.x; e[13] = df.y;
+            }
         }
         d_xyz[3 * i] = dx; d_xyz[3 * i + 1] = dy; d_xyz[3 * i + 2] = dz;
 #pragma unroll
         for (int k = 0; k < 6; ++k) d_cov3d[6 * i + k] = gcov[k];
     }
-    block_reduce_store<12, REDUCE_BLOCK>(e, partial);
+    block_reduce_store<NE, REDUCE_BLOCK>(e, partial);
 }
 
 }  // namespace gfl
@@ -194,6 +207,7 @@ const char* gfl_status_string(int status) {
 int gfl_last_hip_error(void) { return g_last_hip_error; }
 
 size_t gfl_reduce_workspace_bytes(int N) { return (size_t)(reduce_rows(N > 0 ? N : 1)) * 12 * sizeof(float); }
+size_t gfl_reduce_cam_workspace_bytes(int N) { return (size_t)(reduce_rows(N > 0 ? N : 1)) * CAM_ACC * sizeof(float); }
 
 int gfl_project_point_fwd(const float* xyz, const float* intr, const float* extr, int N, int W, int H,
                           float nearest, float extent, float* uv, float* depth, gfl_stream_t stream) {
@@ -214,9 +228,27 @@ int gfl_project_point_bwd(const float* xyz, const float* intr, const float* extr
     if (!xyz || !depth || !d_uv || !d_depth || !d_xyz || !workspace) return GFL_ERR_INVALID;
     if (workspace_bytes < gfl_reduce_workspace_bytes(N)) return GFL_ERR_WORKSPACE;
     const int rows = reduce_rows(N);
-    project_bwd_kernel<<<rows, REDUCE_BLOCK, 0, s>>>(xyz, intr, extr, depth, d_uv, d_depth, N, d_xyz,
-                                                     (float*)workspace);
+    project_bwd_kernel<EXTR_ACC><<<rows, REDUCE_BLOCK, 0, s>>>(xyz, intr, extr, depth, d_uv, d_depth, N, d_xyz,
+                                                               (float*)workspace);
     fold_partials_kernel<12><<<1, 256, 0, s>>>((const float*)workspace, rows, d_extr);
+    return check_launch();
+}
+
+int gfl_project_point_bwd_cam(const float* xyz, const float* intr, const float* extr, const float* depth,
+                              const float* d_uv, const float* d_depth, int N, float* d_xyz, float* d_extr, float* d_intr,
+                              void* workspace, size_t workspace_bytes, gfl_stream_t stream) {
+    if (N < 0 || !intr || !extr || !d_extr || !d_intr) return GFL_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    if (N == 0) {
+        if (check(hipMemsetAsync(d_extr, 0, 12 * sizeof(float), s))) return GFL_ERR_HIP;
+        return check(hipMemsetAsync(d_intr, 0, 4 * sizeof(float), s));
+    }
+    if (!xyz || !depth || !d_uv || !d_depth || !d_xyz || !workspace) return GFL_ERR_INVALID;
+    if (workspace_bytes < gfl_reduce_cam_workspace_bytes(N)) return GFL_ERR_WORKSPACE;
+    const int rows = reduce_rows(N);
+    project_bwd_kernel<CAM_ACC><<<rows, REDUCE_BLOCK, 0, s>>>(xyz, intr, extr, depth, d_uv, d_depth, N, d_xyz,
+                                                              (float*)workspace);
+    fold_partials_split_kernel<EXTR_ACC, CAM_ACC - EXTR_ACC><<<1, 256, 0, s>>>((const float*)workspace, rows, d_extr, d_intr);
     return check_launch();
 }
 
@@ -259,9 +291,27 @@ int gfl_ewa_bwd(const float* xyz, const float* cov3d, const float* intr, const f
     if (!xyz || !cov3d || !radius || !d_conic || !d_xyz || !d_cov3d || !workspace) return GFL_ERR_INVALID;
     if (workspace_bytes < gfl_reduce_workspace_bytes(N)) return GFL_ERR_WORKSPACE;
     const int rows = reduce_rows(N);
-    ewa_bwd_kernel<<<rows, REDUCE_BLOCK, 0, s>>>(xyz, cov3d, intr, extr, radius, d_conic, N, W, H, d_xyz, d_cov3d,
-                                                 (float*)workspace);
+    ewa_bwd_kernel<EXTR_ACC><<<rows, REDUCE_BLOCK, 0, s>>>(xyz, cov3d, intr, extr, radius, d_conic, N, W, H, d_xyz, d_cov3d,
+                                                           (float*)workspace);
     fold_partials_kernel<12><<<1, 256, 0, s>>>((const float*)workspace, rows, d_extr);
+    return check_launch();
+}
+
+int gfl_ewa_bwd_cam(const float* xyz, const float* cov3d, const float* intr, const float* extr, const int32_t* radius,
+                    const float* d_conic, int N, int W, int H, float* d_xyz, float* d_cov3d, float* d_extr, float* d_intr,
+                    void* workspace, size_t workspace_bytes, gfl_stream_t stream) {
+    if (N < 0 || W <= 0 || H <= 0 || !intr || !extr || !d_extr || !d_intr) return GFL_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    if (N == 0) {
+        if (check(hipMemsetAsync(d_extr, 0, 12 * sizeof(float), s))) return GFL_ERR_HIP;
+        return check(hipMemsetAsync(d_intr, 0, 4 * sizeof(float), s));
+    }
+    if (!xyz || !cov3d || !radius || !d_conic || !d_xyz || !d_cov3d || !workspace) return GFL_ERR_INVALID;
+    if (workspace_bytes < gfl_reduce_cam_workspace_bytes(N)) return GFL_ERR_WORKSPACE;
+    const int rows = reduce_rows(N);
+    ewa_bwd_kernel<CAM_ACC><<<rows, REDUCE_BLOCK, 0, s>>>(xyz, cov3d, intr, extr, radius, d_conic, N, W, H, d_xyz, d_cov3d,
+                                                          (float*)workspace);
+    fold_partials_split_kernel<EXTR_ACC, CAM_ACC - EXTR_ACC><<<1, 256, 0, s>>>((const float*)workspace, rows, d_extr, d_intr);
     return check_launch();
 }
 

@@ -40,10 +40,27 @@ __device__ __forceinline__ void project_bwd_cam(const Cam& c, float px, float py
     gz = dd - (du * c.fx * px + dv * c.fy * py) * iz * iz;
 }
 
+// Camera accumulators of a backward: e[0..12) = extr (row-major 3x4: R | t); a kernel that also returns the gradient
+// of the intrinsics carries CAM_ACC of them, e[12..16) = d_fx d_fy d_cx d_cy.  cam_grad_to_world and ewa_bwd are
+// templates on the array's width and touch e[0..12) only.
+constexpr int EXTR_ACC = 12, CAM_ACC = 16;
+
+// ---- the intrinsics' gradient.  These two are NOT inlined, and they take a kernel's inputs, not its intermediates: the
+// arithmetic of the extr / xyz / cov gradients around the call then stays what the compiler makes of it without them
+// (inlined, their multiplies were packed and fused together with the caller's and d_extr moved in the last bit), so a
+// kernel that asks for d_intr returns every other gradient with the bits of the kernel that does not.
+// Projection, a VISIBLE row (u = fx px / pz + cx, v = fy py / pz + cy): returns (d_fx, d_fy); d_cx = du, d_cy = dv.
+// Whether a row is visible depends on intr too; the culling is not differentiated (as in the oracle).
+__device__ __noinline__ float2 project_bwd_intr(float px, float py, float pz, float du, float dv) {
+    const float iz = 1.0f / pz;
+    return make_float2(du * (px * iz), dv * (py * iz));
+}
+
 // Fold a camera-space point gradient g into world xyz gradient and the 12 extr
 // gradient accumulators e[] (row-major 3x4: R | t).
+template <int NE>
 __device__ __forceinline__ void cam_grad_to_world(const Cam& c, float x, float y, float z, float gx, float gy,
-                                                  float gz, float& dx, float& dy, float& dz, float (&e)[12]) {
+                                                  float gz, float& dx, float& dy, float& dz, float (&e)[NE]) {
     dx += c.r00 * gx + c.r10 * gy + c.r20 * gz;
     dy += c.r01 * gx + c.r11 * gy + c.r21 * gz;
     dz += c.r02 * gx + c.r12 * gy + c.r22 * gz;
@@ -256,10 +273,12 @@ __device__ __forceinline__ void tile_rect(float u, float v, int radius, int gx, 
 // Backward of conic = [c/det, -b/det, a/det] through Sigma2 = M Sigma M^T + 0.3 I.
 // In: dA,dB,dC (true gradients wrt the three conic entries).  Out: gcov[6] (wrt
 // stored cov3d entries), camera-space point gradient (gx,gy,gz) and the rotation
-// part of the extr gradient accumulated into e[] (entries 0..2,4..6,8..10).
+// part of the extr gradient accumulated into e[] (entries 0..2,4..6,8..10).  dj (may be null): the gradient of the
+// Jacobian's four entries j00 j02 j11 j12, for ewa_bwd_intr.
+template <int NE>
 __device__ __forceinline__ void ewa_bwd(const Cam& c, const Ewa& f, float px, float py, const float (&cov)[6],
                                         float dA, float dB, float dC, float (&gcov)[6], float& gx, float& gy,
-                                        float& gz, float (&e)[12]) {
+                                        float& gz, float (&e)[NE], float* dj = nullptr) {
     const float inv2 = 1.0f / (f.det * f.det);
     const float da = inv2 * (-f.c * f.c * dA + f.b * f.c * dB + (f.det - f.a * f.c) * dC);
     const float dc = inv2 * (-f.a * f.a * dC + f.a * f.b * dB + (f.det - f.a * f.c) * dA);
@@ -293,6 +312,9 @@ __device__ __forceinline__ void ewa_bwd(const Cam& c, const Ewa& f, float px, fl
     if (f.clamp_x) {
         gx = 0.f;
         gz += -f.j02 * iz * dj02;  // j02 = -fx*L/z  ->  d/dz = fx*L/z^2 = -j02/z
+        // (d j02 / d fx = 0 here: L = limx z with limx = FOV_CLAMP W / (2 fx), so j02 = -+FOV_CLAMP W / (2 z).  Autograd
+        //  finds the same zero as two terms that cancel, through tx and through limx; the intrinsics gradient below
+        //  writes the zero instead of the cancellation.  The same for j12 and fy.)
     } else {
         gx = -c.fx * iz2 * dj02;
         gz += 2.f * c.fx * px * iz2 * iz * dj02;
@@ -304,6 +326,25 @@ __device__ __forceinline__ void ewa_bwd(const Cam& c, const Ewa& f, float px, fl
         gy = -c.fy * iz2 * dj12;
         gz += 2.f * c.fy * py * iz2 * iz * dj12;
     }
+    if (dj) { dj[0] = dj00; dj[1] = dj02; dj[2] = dj11; dj[3] = dj12; }
+}
+
+// The focal lengths' gradient through the Jacobian (the conic does not depend on cx, cy), added to acc = (d_fx, d_fy):
+// j00 = fx / z, j02 = -fx px / z^2 -- or, clamped, a j02 without fx in it (see the clamp_x branch above); j11, j12
+// likewise in fy.  Not inlined, from the kernel's inputs (see project_bwd_intr): it runs the forward (the same bits:
+// ewa_fwd does not contract) and forms dj once more for itself.
+struct Cov6 { float v[6]; };
+__device__ __noinline__ float2 ewa_bwd_intr(Cam c, float px, float py, float pz, Cov6 cov, float dA, float dB, float dC,
+                                            int W, int H, float2 acc) {
+    const Ewa f = ewa_fwd(c, px, py, pz, cov.v, W, H);
+    float gcov[6], gx, gy, gz, e[EXTR_ACC], dj[4];
+#pragma unroll
+    for (int k = 0; k < EXTR_ACC; ++k) e[k] = 0.f;
+    ewa_bwd(c, f, px, py, cov.v, dA, dB, dC, gcov, gx, gy, gz, e, dj);
+    const float iz = 1.0f / f.z, iz2 = iz * iz;
+    acc.x += dj[0] * iz + (f.clamp_x ? 0.f : dj[1] * -(px * iz2));
+    acc.y += dj[2] * iz + (f.clamp_y ? 0.f : dj[3] * -(py * iz2));
+    return acc;
 }
 
 // ---------------------------------------------------------------- which pixel boxes can a splat reach?

@@ -63,6 +63,8 @@ def _declare(lib):
     lib.gfl_fit_iteration_snapshot.argtypes = [ctypes.POINTER(FitState), ctypes.POINTER(FitHyper), _P, _P, _P]
     lib.gfl_render_bwd.restype = ctypes.c_int
     lib.gfl_render_bwd.argtypes = [ctypes.POINTER(FitState), ctypes.POINTER(FitHyper), _P, _P, _P, _P, _P, _P]
+    lib.gfl_render_bwd_cam.restype = ctypes.c_int
+    lib.gfl_render_bwd_cam.argtypes = [ctypes.POINTER(FitState), ctypes.POINTER(FitHyper), _P, _P, _P, _P, _P, _P, _P]
     lib._fit_declared = True
 
 

@@ -8,9 +8,12 @@ each a ``torch.autograd.Function`` over the C ABI of libgflow_hip.so.  Use as
 
 ``compute_sh`` is provided as an optional sixth operator.
 
-Gradients provided (the ones the reference consumes):
-project_point -> xyz, extr; compute_cov3d -> scale, rotate;
-ewa_project -> xyz, cov3d, extr; alpha_blending -> uv, conic, opacity, feature.
+Gradients provided (the ones the reference consumes, SURVEY.md 8b, and the camera's intrinsics):
+project_point -> xyz, intr, extr; compute_cov3d -> scale, rotate;
+ewa_project -> xyz, cov3d, intr, extr; alpha_blending -> uv, conic, opacity, feature.
+The gradient of ``intr`` is computed only for a caller who asks for it (``intr.requires_grad_()``): the backward then
+calls the ``*_bwd_cam`` entry of the library, and otherwise exactly the entry it always called.  The culling decisions
+(visibility, radius, tile rectangle) depend on ``intr`` and are not differentiated.
 """
 import warnings
 
@@ -38,7 +41,7 @@ def _cam(intr, extr):
     if intr.numel() != 4 or extr.numel() != 12:
         raise RuntimeError("msplat: intr must have 4 elements [fx,fy,cx,cy] and extr must be (3,4)")
     L.need_device(intr, extr)
-    return intr.detach().float().contiguous(), extr.float().contiguous()
+    return intr.float().contiguous(), extr.float().contiguous()
 
 
 def _vis(visible, n):
@@ -73,6 +76,14 @@ class _ProjectPoint(torch.autograd.Function):
         n = xyz.shape[0]
         d_xyz = torch.empty_like(xyz)
         d_extr = torch.empty((3, 4), dtype=torch.float32, device=xyz.device)
+        if ctx.needs_input_grad[1]:
+            d_intr = torch.empty(4, dtype=torch.float32, device=xyz.device)
+            ws = L.scratch(lib.gfl_reduce_cam_workspace_bytes(n), xyz.device)
+            L.check(lib.gfl_project_point_bwd_cam(L.ptr(xyz), L.ptr(intr), L.ptr(extr), L.ptr(depth),
+                                                  L.ptr(d_uv.contiguous()), L.ptr(d_depth.contiguous()), n, L.ptr(d_xyz),
+                                                  L.ptr(d_extr), L.ptr(d_intr), L.ptr(ws), ws.numel(), L.stream()),
+                    "project_point backward")
+            return d_xyz, d_intr.reshape(intr.shape), d_extr, None, None, None, None
         ws = L.scratch(lib.gfl_reduce_workspace_bytes(n), xyz.device)
         L.check(lib.gfl_project_point_bwd(L.ptr(xyz), L.ptr(intr), L.ptr(extr), L.ptr(depth),
                                           L.ptr(d_uv.contiguous()), L.ptr(d_depth.contiguous()), n, L.ptr(d_xyz),
@@ -82,7 +93,7 @@ class _ProjectPoint(torch.autograd.Function):
 
 def project_point(xyz, intr, extr, W, H, nearest=NEAREST, extent=EXTENT):
     """xyz (N,3), intr (4,), extr (3,4) -> uv (N,2), depth (N,1).  Culled points have
-    depth 0 and uv (0,0) (render.py:29 derives ``visible`` from that)."""
+    depth 0 and uv (0,0) (render.py:29 derives ``visible`` from that).  Differentiable in xyz, extr and intr."""
     xyz = _f32(xyz, "xyz", (3,))
     intr, extr = _cam(intr, extr)
     return _ProjectPoint.apply(xyz, intr, extr, int(W), int(H), float(nearest), float(extent))
@@ -144,6 +155,13 @@ class _Ewa(torch.autograd.Function):
         d_xyz = torch.empty_like(xyz)
         d_cov = torch.empty_like(cov3d)
         d_extr = torch.empty((3, 4), dtype=torch.float32, device=xyz.device)
+        if ctx.needs_input_grad[2]:
+            d_intr = torch.empty(4, dtype=torch.float32, device=xyz.device)
+            ws = L.scratch(lib.gfl_reduce_cam_workspace_bytes(n), xyz.device)
+            L.check(lib.gfl_ewa_bwd_cam(L.ptr(xyz), L.ptr(cov3d), L.ptr(intr), L.ptr(extr), L.ptr(radius),
+                                        L.ptr(d_conic.contiguous()), n, W, H, L.ptr(d_xyz), L.ptr(d_cov), L.ptr(d_extr),
+                                        L.ptr(d_intr), L.ptr(ws), ws.numel(), L.stream()), "ewa_project backward")
+            return d_xyz, d_cov, d_intr.reshape(intr.shape), d_extr, None, None, None, None
         ws = L.scratch(lib.gfl_reduce_workspace_bytes(n), xyz.device)
         L.check(lib.gfl_ewa_bwd(L.ptr(xyz), L.ptr(cov3d), L.ptr(intr), L.ptr(extr), L.ptr(radius),
                                 L.ptr(d_conic.contiguous()), n, W, H, L.ptr(d_xyz), L.ptr(d_cov), L.ptr(d_extr),

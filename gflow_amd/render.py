@@ -113,6 +113,7 @@ class _FusedRender(torch.autograd.Function):
             raise
         if any(ctx.needs_input_grad):
             ctx.eng, ctx.n, ctx.keep, ctx.token = eng, n, (intr_c, extr_c, out, rec), token
+            ctx.intr_shape = intr.shape
             # a graph that is dropped without backward frees the engine too; backward() calls this same finalizer,
             # which runs at most once
             ctx.fin = weakref.finalize(ctx, _release, eng, token)
@@ -137,11 +138,20 @@ class _FusedRender(torch.autograd.Function):
         d_depth = None if d_depth is None else d_depth.float().contiguous()
         d_params = torch.empty(max(n, 1), 16, dtype=torch.float32, device=dev)
         d_extr = torch.empty(12, dtype=torch.float32, device=dev)
-        L.check(eng.lib.gfl_render_bwd(ctypes.byref(eng.state()), ctypes.byref(eng.hp), L.ptr(d_render), L.ptr(d_uv),
-                                       L.ptr(d_depth), L.ptr(d_params), L.ptr(d_extr), L.stream()), "render backward")
+        d_intr = None
+        if ctx.needs_input_grad[5]:
+            # asked for (intr.requires_grad_()): the entry whose per-splat launch also reduces the four intrinsics sums
+            d_intr = torch.empty(4, dtype=torch.float32, device=dev)
+            L.check(eng.lib.gfl_render_bwd_cam(ctypes.byref(eng.state()), ctypes.byref(eng.hp), L.ptr(d_render), L.ptr(d_uv),
+                                               L.ptr(d_depth), L.ptr(d_params), L.ptr(d_extr), L.ptr(d_intr), L.stream()),
+                    "render backward")
+            d_intr = d_intr.reshape(ctx.intr_shape)
+        else:
+            L.check(eng.lib.gfl_render_bwd(ctypes.byref(eng.state()), ctypes.byref(eng.hp), L.ptr(d_render), L.ptr(d_uv),
+                                           L.ptr(d_depth), L.ptr(d_params), L.ptr(d_extr), L.stream()), "render backward")
         ctx.fin()
         g = d_params[:n]
-        return (g[:, 0:3], g[:, 3:6], g[:, 6:10], g[:, 10:11], g[:, 11:14], None, d_extr.reshape(3, 4), None, None, None)
+        return (g[:, 0:3], g[:, 3:6], g[:, 6:10], g[:, 10:11], g[:, 11:14], d_intr, d_extr.reshape(3, 4), None, None, None)
 
 
 def render(gaussians, camera, bg=0.0):
@@ -149,7 +159,8 @@ def render(gaussians, camera, bg=0.0):
     scale (N,3), rotate (N,4, unit, wxyz), opacity (N,1), rgb (N,3); camera: dict with intr (4,), extr (3,4),
     W, H.  Returns dict(rgb (3,H,W), depth_map (1,H,W), uv (N,2), depth (N,1)) -- what
     render_multiple(input_group, ["rgb", "uv", "depth", "depth_map"]) returns (render.py:6-108), with gradients to
-    the five attributes and to extr.
+    the five attributes, to extr and to intr.  The gradient of intr (4,) is computed when the caller asks for it
+    (``intr.requires_grad_()``) and costs nothing otherwise; culling, radius and tile rectangles are not differentiated.
     Under torch.use_deterministic_algorithms(True) the call runs in the library's deterministic mode (GFL_FIT_DETERMINISTIC,
     include/gflow_hip.h): forward and backward give bit-identical results for identical inputs."""
     L.need_device(gaussians["xyz"])

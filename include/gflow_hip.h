@@ -102,9 +102,10 @@ typedef enum gfl_status {
  * (gfl_tile_sort_with_slots is gone, gfl_tile_sort_ordered / _reserved lost their rec / slot_inv / slot_pool arguments): the
  * per-splat launch finds its pair rows without one.  303: GFL_PIXEL_CENTER, gfl_constants_n.  304: gfl_fit_state.cu_count.
  * 305: gfl_fit_state.flags (was reserved_) and GFL_FIT_DETERMINISTIC, gfl_scan_f64.  306: gfl_track_anchor, gfl_track_frame.
- * 307: gfl_seg_score.  308: gfl_recon_frame.
+ * 307: gfl_seg_score.  308: gfl_recon_frame.  309: the gradient of the intrinsics -- gfl_reduce_cam_workspace_bytes,
+ * gfl_project_point_bwd_cam, gfl_ewa_bwd_cam, gfl_render_bwd_cam; the fit workspace is 12 floats per row of cap larger.
  * A binding checks gfl_version() >= GFL_VERSION of the header it was written for. */
-#define GFL_VERSION 308
+#define GFL_VERSION 309
 int gfl_version(void);
 /* out[10] = TILE, NEAREST, EXTENT, FOV_CLAMP, LOWPASS, EIG_FLOOR, RADIUS_SIGMA, ALPHA_MIN, ALPHA_MAX, T_MIN of this build */
 int gfl_constants(float* out10);
@@ -119,6 +120,8 @@ const char* gfl_status_string(int status);
 int gfl_last_hip_error(void);
 /* bytes of scratch any *_bwd that reduces camera gradients needs for N splats */
 size_t gfl_reduce_workspace_bytes(int N);
+/* 309: the same for the *_bwd_cam entries, which reduce the gradient of the intrinsics beside it (16 floats per 256 splats) */
+size_t gfl_reduce_cam_workspace_bytes(int N);
 
 /* ---- A4  msplat.project_point  (render.py:21-24,116-119; trainer.py:955) ------
  * uv[N,2], depth[N,1]; culled splats get uv=(0,0), depth=0 (render.py:29). */
@@ -128,6 +131,13 @@ int gfl_project_point_fwd(const float* xyz, const float* intr, const float* extr
 int gfl_project_point_bwd(const float* xyz, const float* intr, const float* extr, const float* depth,
                           const float* d_uv, const float* d_depth, int N, float* d_xyz, float* d_extr,
                           void* workspace, size_t workspace_bytes, gfl_stream_t stream);
+/* 309: the same plus d_intr[4] = dL/d (fx, fy, cx, cy) -- msplat.project_point is differentiable in its camera, intrinsics
+ * included (render.py:21-24 passes both).  u = fx x/z + cx, v = fy y/z + cy over the visible rows; which rows are visible
+ * depends on intr too and is not differentiated.  d_xyz and d_extr have the bits gfl_project_point_bwd gives.
+ * workspace: gfl_reduce_cam_workspace_bytes(N).  N == 0 zero-fills d_extr and d_intr. */
+int gfl_project_point_bwd_cam(const float* xyz, const float* intr, const float* extr, const float* depth,
+                              const float* d_uv, const float* d_depth, int N, float* d_xyz, float* d_extr,
+                              float* d_intr, void* workspace, size_t workspace_bytes, gfl_stream_t stream);
 
 /* ---- A5  msplat.compute_cov3d  (render.py:37-41) -------------------------------
  * rotate is WXYZ; visible is uint8[N]; cov3d[N,6] = xx,xy,xz,yy,yz,zz */
@@ -146,6 +156,14 @@ int gfl_ewa_fwd(const float* xyz, const float* cov3d, const float* intr, const f
 int gfl_ewa_bwd(const float* xyz, const float* cov3d, const float* intr, const float* extr,
                 const int32_t* radius, const float* d_conic, int N, int W, int H, float* d_xyz,
                 float* d_cov3d, float* d_extr, void* workspace, size_t workspace_bytes, gfl_stream_t stream);
+/* 309: the same plus d_intr[4] (render.py:44-49 passes intr): the conic depends on fx, fy through the Jacobian
+ * J = [[fx/z, 0, -fx tx/z^2], [0, fy/z, -fy ty/z^2]] and not on cx, cy (d_intr[2] = d_intr[3] = 0).  Where x/z (y/z) is
+ * clamped at GFL_FOV_CLAMP W / (2 fx), the third column is -+GFL_FOV_CLAMP W / (2 z) and carries no fx (fy).  radius and
+ * tiles_touched are not differentiated.  workspace: gfl_reduce_cam_workspace_bytes(N). */
+int gfl_ewa_bwd_cam(const float* xyz, const float* cov3d, const float* intr, const float* extr,
+                    const int32_t* radius, const float* d_conic, int N, int W, int H, float* d_xyz,
+                    float* d_cov3d, float* d_extr, float* d_intr, void* workspace, size_t workspace_bytes,
+                    gfl_stream_t stream);
 
 /* ---- A7  msplat.sort_gaussian  (render.py:52-54) -------------------------------
  * Two phases so the host can size gaussian_ids_sorted exactly when it wants to:
@@ -397,6 +415,12 @@ int gfl_fit_reserved_supported(const gfl_fit_state* st, const gfl_fit_hyper* hp)
 int gfl_render_fwd(const gfl_fit_state* st, const gfl_fit_hyper* hp, gfl_stream_t stream);
 int gfl_render_bwd(const gfl_fit_state* st, const gfl_fit_hyper* hp, const float* d_render, const float* d_uv,
                    const float* d_depth, float* d_params, float* d_extr, gfl_stream_t stream);
+/* 309: gfl_render_bwd plus d_intr[4], the intrinsics' gradient through projection and EWA of render.py:21-49 (culling,
+ * radius and tile rectangles are not differentiated).  d_params and d_extr have the bits gfl_render_bwd gives; in the
+ * deterministic mode d_intr is bit-identical run to run as well.  The per-splat launch is gfl_render_bwd's own (it also
+ * writes d_rec -- the state's, or rows in the workspace); a second small launch over the splats reduces d_intr from them. */
+int gfl_render_bwd_cam(const gfl_fit_state* st, const gfl_fit_hyper* hp, const float* d_render, const float* d_uv,
+                       const float* d_depth, float* d_params, float* d_extr, float* d_intr, gfl_stream_t stream);
 /* The three snapshot images GFlow keeps every 10th iteration (trainer.py:573-582) in one call, entirely on the
  * device: rgb of the last forward, the turbo-coloured depth map and the centre blobs (render.py:76-106; both composites
  * of the same lists, the per-splat values are derived while the records are staged), each clamped, scaled by 255 and
