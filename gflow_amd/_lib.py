@@ -23,7 +23,7 @@ _lib = None
 
 c_void_p, c_int, c_float, c_size_t, c_int64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_int64
 
-MIN_VERSION = 309          # GFL_VERSION of the include/gflow_hip.h this binding mirrors (the *_bwd_cam entries)
+MIN_VERSION = 310          # GFL_VERSION of the include/gflow_hip.h this binding mirrors (gfl_flow_pair)
 
 # name -> (restype, argtypes); mirrors include/gflow_hip.h one to one
 _P = c_void_p
@@ -92,6 +92,9 @@ SIGNATURES = {
     "gfl_seg_score": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     "gfl_recon_workspace_bytes": (c_size_t, [c_int, c_int]),
     "gfl_recon_frame": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "gfl_flow_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "gfl_flow_pair": (c_int, [_P, c_int, _P, _P, _P, c_int, _P, c_int, c_int, _P, _P, c_int, c_int, c_float, c_int, c_int, _P,
+                              _P, _P, _P, c_size_t, _P]),
     "gfl_abi_sizes": (c_int, [_P, _P]),
     "gfl_profile_enable": (c_int, [ctypes.c_uint]),
     "gfl_profile_read": (c_int, [_P, _P, c_int]),

@@ -6,6 +6,7 @@
 // The tile's depth-sorted splat list is staged through LDS 256 records at a time
 // (three wide LDS reads per splat, all lanes the same address = broadcast).
 #include "gfl_common.hpp"
+#include "gfl_splat_alpha.hpp"   // splat_alpha: the blend rule, shared with gfl_flow.hip
 
 namespace gfl {
 
@@ -16,21 +17,6 @@ struct SplatRec {            // 40 bytes + pad: what a pixel needs from one spla
     float4 p1;               // conic c, opacity, f0, f1
     float2 p2;               // f2, f3
 };
-
-// alpha of one splat at one pixel; identical instruction sequence in the forward
-// and the backward (explicit fma, contraction off) so both take the same
-// skip/keep decision.  Returns false when the splat is skipped.
-__device__ __forceinline__ bool splat_alpha(float u, float v, float A, float B, float C, float o, float fx, float fy,
-                                            float& alpha, float& G) {
-#pragma clang fp contract(off)
-    const float dx = u - fx, dy = v - fy;
-    const float q = __builtin_fmaf(A * dx, dx, (C * dy) * dy);
-    const float power = __builtin_fmaf(-0.5f, q, -((B * dx) * dy));
-    if (power > 0.f) return false;
-    G = __expf(power);
-    alpha = fminf(GFL_ALPHA_MAX, o * G);
-    return alpha >= GFL_ALPHA_MIN;
-}
 
 template <int C>
 __device__ __forceinline__ void stage_splat(SplatRec* __restrict__ rec, int g, const float* __restrict__ uv,

@@ -189,6 +189,36 @@ def reduce_camera(cams, dist=None, device="cpu"):
     return out
 
 
+FLOW_KEYS = ("EPE", "EPE_still", "EPE_moving", "acc_1px", "acc_3px", "acc_5px", "coverage")
+
+
+def reduce_flow(flows, dist=None, device="cpu"):
+    """The "flow" block of the JSON line: every clip's numbers (flow.evaluate: pooled over its pairs), each averaged over
+    the clips where it is a number (a clip without a moving pixel has no EPE_moving; a one-frame clip has nothing);
+    ``pairs`` is the clips' total, ``clips`` those with a pair.  None where no clip has the number.  Over ranks by ONE more
+    small all-reduce(SUM) of (the seven sums, their seven counts, pairs, clips)."""
+    import math
+    from . import flow as FL
+    k = len(FLOW_KEYS)
+    sums, counts, pairs, clips = [0.0] * k, [0.0] * k, 0, 0
+    for fl in flows.values():
+        m = FL.evaluate(fl)
+        pairs += m["pairs"]
+        clips += 1 if m["pairs"] else 0
+        for j, key in enumerate(FLOW_KEYS):
+            if not math.isnan(m[key]):
+                sums[j] += m[key]
+                counts[j] += 1.0
+    vec = torch.tensor(sums + counts + [float(pairs), float(clips)], dtype=torch.float64, device=device)
+    if dist is not None and dist.is_initialized():
+        dist.all_reduce(vec, op=dist.ReduceOp.SUM)
+    v = vec.tolist()
+    out = {key: v[j] / v[k + j] if v[k + j] else None for j, key in enumerate(FLOW_KEYS)}
+    out["pairs"] = int(v[2 * k])
+    out["clips"] = int(v[2 * k + 1])
+    return out
+
+
 def csv_metrics(out):
     """The JSON line's blocks under the reference's metrics.csv keys (quality.CSV_KEYS); only the blocks that are there"""
     m = {}
@@ -311,7 +341,8 @@ def stage_kwargs(c, frames, i, stage):
 
 
 def fit_clip(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, log=None, load_extr=True, keep=None,
-             async_snapshots=None, deterministic=None, track_queries=None, segment=False, recon=False, camera=False):
+             async_snapshots=None, deterministic=None, track_queries=None, segment=False, recon=False, camera=False,
+             flow=False):
     """Fit one clip; returns the metrics dict of this clip (PSNR summed over its frames; with ``cfg["traj_num"]`` > 0 also
     ``"traj"``: the per-frame trajectory images and seed projections, host arrays -- what the reference's frame loop collects in
     ``frames_sequence_traj / frames_sequence_traj_upon / sequence_traj``).
@@ -339,7 +370,13 @@ def fit_clip(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, 
     ``camera``: also the camera path and its score (gflow_amd.camera; INTEGRATION.md, "Camera score"): the dict then has
     ``"camera"`` = dict(extr (T, 3, 4) float32 -- every frame's ``get_extr()`` at its end --, ATE, RPE_t, RPE_r: floats or
     None) against each frame's ``extr_gt`` if it has one, else its ``extr``; a frame with neither is a ValueError before
-    anything is fitted."""
+    anything is fitted.
+    ``flow``: also the dense optical flow the fitted splats imply between consecutive frames and its end-point error
+    against the flow the fit was given (gflow_amd.flow.FlowRecorder; INTEGRATION.md, "Flow score"): the dict then has
+    ``"flow"`` = dict(sums (T-1, 3, 6), EPE, acc_1px, acc_3px, acc_5px, coverage (T-1, 3) float64 -- per pair and class (all,
+    still, moving)); ``flow="maps"`` also keeps the maps: ``maps`` (T-1, H, W, 2) float32, frame i -> i + 1 on frame i's
+    grid, and ``valid`` (T-1, H, W) bool.  A one-frame clip gives empty arrays.  ``keep["record_flow_inputs"] = True``: clones
+    of each pair's kernel inputs (dicts) in ``keep["flow_inputs"]``."""
     if deterministic and not fused:
         raise ValueError("fit_clip(deterministic=True) needs fused=True: the operator path's alpha_blending backward has no "
                          "deterministic implementation")
@@ -347,7 +384,7 @@ def fit_clip(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, 
     dev_ = torch.device(device)
     g = fit_clip_steps(frames, device, cfg=cfg, seed=seed, snapshot_interval=snapshot_interval, fused=fused, log=log,
                        load_extr=load_extr, chunk=None, keep=keep, deterministic=deterministic, track_queries=track_queries,
-                       segment=segment, recon=recon, camera=camera,
+                       segment=segment, recon=recon, camera=camera, flow=flow,
                        **({} if async_snapshots is None else {"async_snapshots": async_snapshots}))
 
     drive = lambda: run_to_end(g)
@@ -369,7 +406,7 @@ def fit_clip(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, 
 
 def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, log=None, load_extr=True, chunk=None,
                    async_snapshots=True, keep=None, cu_count=0, deterministic=None, track_queries=None, segment=False,
-                   recon=False, camera=False):
+                   recon=False, camera=False, flow=False):
     """fit_clip as a generator: yields after every ``chunk`` iterations of a stage (None: never) and returns the metrics
     dict.  The caller owns the stream the work is enqueued on (fit_clips_concurrent gives every clip its own)."""
     from .trainer import SimpleGaussian
@@ -401,6 +438,12 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
     if recon:
         from .quality import ReconRecorder
         recon_rec = ReconRecorder(len(frames), tr.H, tr.W, tr.device)
+    flow_rec = None
+    if flow:
+        from .flow import FlowRecorder
+        flow_rec = FlowRecorder(len(frames), tr.H, tr.W, tr.device, keep_maps=flow == "maps")
+        if keep is not None and keep.get("record_flow_inputs"):
+            flow_rec.inputs = keep.setdefault("flow_inputs", [])
     tr.load_camera(focal=f0["focal"], pp=f0["pp"])
     if load_extr and f0.get("extr") is not None:
         tr.load_camera(extr=f0["extr"])
@@ -463,6 +506,26 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
             tracker.frame(i, uv, uv_stride, depth, depth_stride, dm)
             if keep is not None and keep.get("record_track_inputs"):
                 keep.setdefault("track_inputs", []).append((uv.clone(), depth.clone(), dm.clone()))
+            return aux if tr.engine_current else None
+
+    def record_flow(i, shared):
+        # frame i's final records and sorted tile lists go to the flow recorder: those of the forward the trajectory recorder
+        # or the tracker has just run on the second engine (``shared``), or of one of its own; on the operator path the
+        # five operators' outputs, packed.  From frame 1 on one gfl_flow_pair for the pair (i - 1, i); nothing is read back
+        with torch.no_grad():
+            if tr.engine_current:
+                aux = shared
+                if aux is None:
+                    aux = tr._aux_forward()
+                    aux.watch_overflow()
+                    tr.rasterisations_done += 1
+                rec, n, ids, tile_range = aux.rec, aux.N, aux.ids, aux.tile_range
+            else:
+                from .flow import operator_state
+                rec, n, ids, tile_range = operator_state(tr._input_group(detach=True))
+                tr.rasterisations_done += 1
+            prev = frames[i - 1] if i else None
+            flow_rec.frame(i, rec, n, ids, tile_range, prev["flow"] if prev else None, prev["move_mask"] if prev else None)
 
     def record_scores(i):
         # benchmark.py:191-230 and :323-329 for frame i, on what the frame's PSNR is taken from and what save_checkpoint
@@ -497,8 +560,11 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
         traj_index, split_interval = select_traj_seeds(tr, int(c["traj_num"]), int(c["traj_offset"]))
         traj_index_t = torch.as_tensor(traj_index, device=tr.device).long()
         shared = record_trajectories()
+    shared = shared if traj else None
     if tracker is not None:
-        record_tracks(0, shared if traj else None)
+        shared = record_tracks(0, shared) or shared
+    if flow_rec is not None:
+        record_flow(0, shared)
     # (PSNR stays on the device and is read ONCE at the end of the clip: a float() per frame drained the queue between
     #  two frames; with a log callback the caller asked for the numbers as they come)
     psnr_sum = tr.psnr().double()
@@ -518,7 +584,9 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
             yield from tr.train_steps(**stage_kwargs(c, frames, i, "joint"), **common)
         shared = record_trajectories() if traj else None
         if tracker is not None:
-            record_tracks(i, shared)
+            shared = record_tracks(i, shared) or shared
+        if flow_rec is not None:
+            record_flow(i, shared)
         p = tr.psnr()
         psnr_sum = psnr_sum + p.double()
         if recon_rec is not None or cam_rec is not None:
@@ -571,17 +639,20 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
         extr = cam_rec.result()                       # (one stacked copy)
         gt = np.stack([torch.as_tensor(e).detach().cpu().double().numpy().reshape(3, 4) for e in cam_gt])
         out["camera"] = dict(extr=extr, **CM.evaluate(extr, gt))
+    if flow_rec is not None:
+        out["flow"] = flow_rec.result()               # (one copy of the (T-1, 3, 6) sums; with "maps" the maps behind it)
     return out
 
 
 # the keys of fit_clip's dict that are per-clip numbers (sums over clips make sense); "traj" is the trajectory output,
 # "tracks" the tracker's, "segmentation" the moving-region masks and their score, "recon" and "camera" the per-frame
-# reconstruction sums and the camera path with its score
+# reconstruction sums and the camera path with its score, "flow" the per-pair flow sums (and maps)
 NUMERIC_KEYS = ("psnr_sum", "frames", "iterations", "rasterisations", "clips", "splats_final", "void_iterations")
 
 
 def fit_clips_concurrent(clips, device, cfg=None, seeds=None, snapshot_interval=0, chunk=32, partition=False,
-                         deterministic=None, track_queries=None, segment=False, recon=False, camera=False, load_extr=True):
+                         deterministic=None, track_queries=None, segment=False, recon=False, camera=False, load_extr=True,
+                         flow=False):
     """Fit several clips AT THE SAME TIME on ONE device, in one host thread: every clip has its own trainer, engine and
     STREAM, and the clips take turns enqueueing ``chunk`` iterations each (fit_clip_steps), so their graph launches
     interleave on the device.  One fit leaves the chip partly idle -- its kernels are a chain of dependent launches,
@@ -599,7 +670,7 @@ def fit_clips_concurrent(clips, device, cfg=None, seeds=None, snapshot_interval=
     ``deterministic`` (None: torch's switch): every clip's result is bit for bit that of fit_clip(..., deterministic=True)
     with the same seed -- without ``partition``, which changes the number of tile queues (include/gflow_hip.h).
     ``track_queries``: None, or one entry (fit_clip's ``track_queries``, or None) per clip.  ``segment``, ``recon``,
-    ``camera``, ``load_extr``: fit_clip's, for all clips."""
+    ``camera``, ``load_extr``, ``flow``: fit_clip's, for all clips."""
     n = len(clips)
     if track_queries is not None and len(track_queries) != n:
         raise ValueError("fit_clips_concurrent: track_queries needs one entry per clip")
@@ -622,7 +693,7 @@ def fit_clips_concurrent(clips, device, cfg=None, seeds=None, snapshot_interval=
     gens = [fit_clip_steps(clips[i], dev, cfg, seed=seeds[i], snapshot_interval=snapshot_interval, chunk=chunk,
                            async_snapshots=n == 1, cu_count=shares[i][1] if shares else 0, deterministic=deterministic,
                            track_queries=None if track_queries is None else track_queries[i], segment=segment,
-                           recon=recon, camera=camera, load_extr=load_extr)
+                           recon=recon, camera=camera, load_extr=load_extr, flow=flow)
             for i in range(n)]
     results = [None] * n
     live = list(range(n))
@@ -674,6 +745,13 @@ def main(argv=None):
     ap.add_argument("--camera", action="store_true",
                     help="keep every frame's camera and score the path against the clip's own (extr_gt, else extr) with "
                          "ATE and RPE (a \"camera\" block in the line)")
+    ap.add_argument("--flow", action="store_true",
+                    help="the dense optical flow the fitted splats imply between consecutive frames, scored against the flow "
+                         "the clip came with: end-point error, still / moving, accuracies, coverage (a \"flow\" block in the "
+                         "line)")
+    ap.add_argument("--flow-out", default=None,
+                    help="with --flow: write each clip's flow maps to DIR/clip_<i>/flow_<frame>.flo (frame -> frame + 1 on "
+                         "the frame's grid; pixels without a flow are 1e10, Middlebury's mark)")
     ap.add_argument("--no-load-extr", action="store_true",
                     help="do not load the frames' camera poses (extr): the camera-only stages estimate them, as the "
                          "reference's scripts/fit_video.sh runs")
@@ -745,19 +823,20 @@ def main(argv=None):
     t0 = time.perf_counter()
     c = max(1, args.clips_per_gpu)
     order = sorted(clips, key=lambda j: (-lengths[j], j))          # (clips of similar length share the GPU)
-    preds, segs, recons, cams = {}, {}, {}, {}
+    preds, segs, recons, cams, flows = {}, {}, {}, {}, {}
+    flow = ("maps" if args.flow_out else True) if args.flow else False
     load_extr = not args.no_load_extr
     for g0 in range(0, len(order), c):
         group = order[g0:g0 + c]
         if len(group) == 1:
             ci = group[0]
             res = [fit_clip(clips[ci], dev, cfg, seed=ci, deterministic=det, track_queries=queries.get(ci), segment=args.seg,
-                            recon=args.recon, camera=args.camera, load_extr=load_extr,
+                            recon=args.recon, camera=args.camera, load_extr=load_extr, flow=flow,
                             log=(lambda s, ci=ci: print(f"[rank {rank} clip {ci}] {s}")) if args.verbose else None)]
         else:
             res = fit_clips_concurrent([clips[ci] for ci in group], dev, cfg, seeds=group, deterministic=det,
                                        track_queries=[queries.get(ci) for ci in group] if args.track else None,
-                                       segment=args.seg, recon=args.recon, camera=args.camera, load_extr=load_extr)
+                                       segment=args.seg, recon=args.recon, camera=args.camera, load_extr=load_extr, flow=flow)
         for ci, m in zip(group, res):
             for k in METRIC_NAMES:
                 local[k] += m[k]
@@ -769,6 +848,8 @@ def main(argv=None):
                 recons[ci] = m["recon"]
             if "camera" in m:
                 cams[ci] = m["camera"]
+            if "flow" in m:
+                flows[ci] = m["flow"]
     torch.cuda.synchronize()
     out = reduce_metrics(local, time.perf_counter() - t0, dist, torch.device("cpu") if (world > 1 and shared) else dev,
                          rank=rank, world=world)
@@ -794,6 +875,12 @@ def main(argv=None):
         out["recon"] = reduce_recon(recons, dist, torch.device("cpu") if (world > 1 and shared) else dev)
     if args.camera:
         out["camera"] = reduce_camera(cams, dist, torch.device("cpu") if (world > 1 and shared) else dev)
+    if args.flow:
+        out["flow"] = reduce_flow(flows, dist, torch.device("cpu") if (world > 1 and shared) else dev)
+        if args.flow_out:
+            from .flow import write_flo_maps
+            for ci, fl in flows.items():
+                write_flo_maps(os.path.join(args.flow_out, f"clip_{ci}"), fl)
     if rank == 0 and args.metrics_csv:
         from .quality import write_metrics_csv
         write_metrics_csv(args.metrics_csv, csv_metrics(out))

@@ -104,8 +104,9 @@ typedef enum gfl_status {
  * 305: gfl_fit_state.flags (was reserved_) and GFL_FIT_DETERMINISTIC, gfl_scan_f64.  306: gfl_track_anchor, gfl_track_frame.
  * 307: gfl_seg_score.  308: gfl_recon_frame.  309: the gradient of the intrinsics -- gfl_reduce_cam_workspace_bytes,
  * gfl_project_point_bwd_cam, gfl_ewa_bwd_cam, gfl_render_bwd_cam; the fit workspace is 12 floats per row of cap larger.
+ * 310: gfl_flow_pair, gfl_flow_workspace_bytes.
  * A binding checks gfl_version() >= GFL_VERSION of the header it was written for. */
-#define GFL_VERSION 309
+#define GFL_VERSION 310
 int gfl_version(void);
 /* out[10] = TILE, NEAREST, EXTENT, FOV_CLAMP, LOWPASS, EIG_FLOOR, RADIUS_SIGMA, ALPHA_MIN, ALPHA_MAX, T_MIN of this build */
 int gfl_constants(float* out10);
@@ -568,6 +569,40 @@ int gfl_seg_score(const uint8_t* pred, const uint8_t* gt, const uint8_t* valid, 
 size_t gfl_recon_workspace_bytes(int W, int H);
 int gfl_recon_frame(const float* render, const float* gt_rgb, int W, int H, int frame, int T, double* sums, void* workspace,
                     size_t workspace_bytes, gfl_stream_t stream);
+
+/* ---- dense optical flow of a frame pair and its end-point error (310; gflow_amd/flow.py, INTEGRATION.md "Flow score") ----
+ * The motion field the splats of frame A imply towards frame B, on A's pixel grid, and its distance from a given flow.
+ * rec_a: frame A's fit records, [n_a][12] float32, 16-byte aligned (u v A B | C opacity . . | . depth . .: what
+ * gfl_fit_forward leaves in gfl_fit_state.rec; only columns 0..5 are read); ids, tile_range: frame A's depth-sorted tile
+ * lists, tile_range [T][2] = start / end into ids, T = ceil(W / 16) * ceil(H / 16) (the lists may lie anywhere in ids, with
+ * anything between them: reserved regions).  uv_b / depth_b: frame B's rows (n_b rows of uv_b_stride / depth_b_stride
+ * floats, (u, v) in the first two / the depth in the first; views of B's records: stride 12).  Rows keep their index
+ * from A to B (splats are only ever appended).
+ * Every pixel (x, y), sampled at (x + GFL_PIXEL_CENTER, y + GFL_PIXEL_CENTER), walks its tile's list front to back under
+ * the rule of gfl_blend_fwd: power > 0 skips; alpha = min(GFL_ALPHA_MAX, o G); alpha < GFL_ALPHA_MIN skips; the walk stops
+ * BEFORE adding when T (1 - alpha) < GFL_T_MIN.  With w = alpha T:
+ *   row j has a future iff j < n_b and depth_b[j] != 0; then d = (u_b - u_a, v_b - v_a) (one float32 subtraction each),
+ *   num += w d, den += w.  A row without a future adds nothing, but occludes like any other: T *= 1 - alpha.
+ * The pixel is valid iff den >= min_weight and both components of gt_flow are finite; then F = num / den (float32), else
+ * flow_out = (0, 0) and valid_out = 0.  min_weight in (0, 1]: the share of the pixel's colour that must come from splats
+ * with a known motion.  gt_flow: [H][W][2], the flow A -> B on A's grid; move_mask: [H][W] uint8 or NULL.
+ * Error, float64: ex = (double)F.x - (double)gt.x, ey likewise, epe = sqrt(ex^2 + ey^2).  Three classes -- 0: every pixel,
+ * 1: move_mask == 0, 2: move_mask != 0 (NULL mask: classes 1 and 2 stay zero) -- and per class six doubles
+ *   {n_pixels, n_valid, epe_sum, n(epe < 1), n(epe < 3), n(epe < 5)}     (the last four over the valid pixels)
+ * sums: [n_pairs][3][6] float64; row `pair` is WRITTEN, the other rows are not touched.  flow_out [H][W][2] float32 and
+ * valid_out [H][W] uint8: written for every pixel, or NULL.
+ * GFL_ERR_INVALID: pair outside [0, n_pairs), min_weight outside (0, 1], W or H < 1, more than 16384 tiles,
+ * uv_b_stride < 2, depth_b_stride < 1, negative counts, a null or misaligned pointer that is needed, workspace_bytes <
+ * gfl_flow_workspace_bytes(W, H) (0 for sizes that are refused).  n_a == 0 is GFL_OK: every pixel is invalid, only n_pixels
+ * is non-zero (rec_a, ids, tile_range are not read).
+ * Two launches (one workgroup per tile, then a fold of the tiles' partial sums in a fixed order), no atomics: the same bits
+ * on every call, in every mode.  No allocation, no host synchronisation; callable on the fit's stream between graph
+ * replays. */
+size_t gfl_flow_workspace_bytes(int W, int H);
+int gfl_flow_pair(const float* rec_a, int n_a, const int32_t* ids, const int32_t* tile_range, const float* uv_b,
+                  int uv_b_stride, const float* depth_b, int depth_b_stride, int n_b, const float* gt_flow,
+                  const uint8_t* move_mask, int W, int H, float min_weight, int pair, int n_pairs, double* sums,
+                  float* flow_out, uint8_t* valid_out, void* workspace, size_t workspace_bytes, gfl_stream_t stream);
 
 /* sizeof(gfl_fit_state), sizeof(gfl_fit_hyper): lets an FFI binding verify its struct mirrors */
 int gfl_abi_sizes(int* sizeof_fit_state, int* sizeof_fit_hyper);
