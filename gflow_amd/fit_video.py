@@ -20,10 +20,17 @@ clips than GPUs.
 """
 import argparse
 import json
+import math
 import os
 import time
 
 import torch
+
+from . import camera as CM
+from . import flow as FL
+from . import quality as QL
+from . import segmentation as SG
+from . import tracking as TK
 
 # Canonical hyper-parameters: the README's example (README.md:85-110), which is what BASELINE.json's configs quote
 # (60 000 splats, 500 / 300 iterations, 150 camera-only).  scripts/fit_video.sh:16-39 runs a different set
@@ -84,139 +91,72 @@ def reduce_metrics(local, wall_seconds, dist=None, device="cpu", rank=0, world=1
 
 
 TAPVID_KEYS = ("occlusion_accuracy", "average_jaccard", "average_pts_within_thresh")
+DAVIS_KEYS = ("J", "F", "J&F")
+RECON_KEYS = ("PSNR", "SSIM")
+CAMERA_KEYS = CM.SCORE_KEYS
+FLOW_KEYS = FL.EVAL_KEYS
+
+
+def _mean_over_clips(keys, scores, totals, dist=None, device="cpu", none=float("nan")):
+    """What the ``reduce_*`` blocks of the JSON line share.  ``scores``: per clip of this rank a dict with a value for every
+    key of ``keys`` -- None or NaN where the clip has no such number; ``totals``: this rank's integers that ride along.
+    Returns every key's mean over the clips of ALL ranks where it is a number (``none`` where no clip has it), then every
+    total summed, as ints: ONE small all-reduce(SUM) of (the sums, a clip count per key, the totals)."""
+    n = len(keys)
+    sums, counts = [0.0] * n, [0.0] * n
+    for m in scores:
+        for j, k in enumerate(keys):
+            if m[k] is not None and not math.isnan(m[k]):
+                sums[j] += float(m[k])
+                counts[j] += 1.0
+    vec = torch.tensor(sums + counts + [float(t) for t in totals.values()], dtype=torch.float64, device=device)
+    if dist is not None and dist.is_initialized():
+        dist.all_reduce(vec, op=dist.ReduceOp.SUM)
+    v = vec.tolist()
+    out = {k: v[j] / v[n + j] if v[n + j] else none for j, k in enumerate(keys)}
+    out.update(zip(totals, (int(t) for t in v[2 * n:])))
+    return out
 
 
 def reduce_tapvid(preds, gts, n_frames, dropped, dist=None, device="cpu"):
-    """The "tapvid" block of the JSON line: every clip's TAP-Vid score (tracking.evaluate), averaged over the clips as
-    benchmark.py averages its videos; over ranks by ONE more small all-reduce(SUM) of (the three sums, clips, queries
-    dropped)."""
-    from . import tracking as TK
-    sums = [0.0] * len(TAPVID_KEYS)
-    for ci, p in preds.items():
-        pts, occ, h, w = gts[ci]
-        m = TK.evaluate(p, pts, occ, h, w, n_frames[ci])
-        for k, key in enumerate(TAPVID_KEYS):
-            sums[k] += m[key]
-    vec = torch.tensor(sums + [float(len(preds)), float(dropped)], dtype=torch.float64, device=device)
-    if dist is not None and dist.is_initialized():
-        dist.all_reduce(vec, op=dist.ReduceOp.SUM)
-    v = vec.tolist()
-    clips = v[len(TAPVID_KEYS)]
-    out = {k: v[i] / clips if clips else float("nan") for i, k in enumerate(TAPVID_KEYS)}
-    out["clips"] = int(clips)
-    out["queries_dropped"] = int(v[len(TAPVID_KEYS) + 1])
-    return out
-
-
-DAVIS_KEYS = ("J", "F", "J&F")
+    """The "tapvid" block: every clip's TAP-Vid score (tracking.evaluate), averaged over the clips as benchmark.py averages
+    its videos; ``clips`` is their number, ``queries_dropped`` what the caller left out."""
+    ms = [TK.evaluate(p, *gts[ci], n_frames[ci]) for ci, p in preds.items()]
+    return _mean_over_clips(TAPVID_KEYS, ms, dict(clips=len(ms), queries_dropped=dropped), dist, device)
 
 
 def reduce_davis(segs, dist=None, device="cpu"):
-    """The "davis" block of the JSON line: every clip's J, F and J&F (segmentation.evaluate: means over its scored
-    frames), averaged over the clips that have a scored frame; ``frames_scored`` is their total.  Over ranks by ONE more
-    small all-reduce(SUM) of (the three sums, frames scored, clips)."""
-    from . import segmentation as SG
-    sums, frames, clips = [0.0] * len(DAVIS_KEYS), 0, 0
-    for seg in segs.values():
-        m = SG.evaluate(seg)
-        if m["frames_scored"]:
-            for k, key in enumerate(DAVIS_KEYS):
-                sums[k] += m[key]
-            frames += m["frames_scored"]
-            clips += 1
-    vec = torch.tensor(sums + [float(frames), float(clips)], dtype=torch.float64, device=device)
-    if dist is not None and dist.is_initialized():
-        dist.all_reduce(vec, op=dist.ReduceOp.SUM)
-    v = vec.tolist()
-    clips = v[len(DAVIS_KEYS) + 1]
-    out = {k: v[i] / clips if clips else float("nan") for i, k in enumerate(DAVIS_KEYS)}
-    out["frames_scored"] = int(v[len(DAVIS_KEYS)])
-    out["clips"] = int(clips)
-    return out
-
-
-RECON_KEYS = ("PSNR", "SSIM")
+    """The "davis" block: every clip's J, F and J&F (segmentation.evaluate: means over its scored frames), averaged over
+    the clips that have a scored frame (``clips``); ``frames_scored`` is their total."""
+    ms = [SG.evaluate(seg) for seg in segs.values()]
+    totals = dict(frames_scored=sum(m["frames_scored"] for m in ms), clips=sum(1 for m in ms if m["frames_scored"]))
+    return _mean_over_clips(DAVIS_KEYS, ms, totals, dist, device)
 
 
 def reduce_recon(recons, dist=None, device="cpu"):
-    """The "recon" block of the JSON line: every clip's PSNR and SSIM (quality.evaluate: means over its frames), averaged over
-    the clips as reduce_davis does; ``frames`` is their total.  Over ranks by ONE more small all-reduce(SUM) of (the two
-    sums, frames, clips)."""
-    from . import quality as QL
-    sums, frames, clips = [0.0] * len(RECON_KEYS), 0, 0
-    for rec in recons.values():
-        m = QL.evaluate(rec)
-        if m["frames"]:
-            for k, key in enumerate(RECON_KEYS):
-                sums[k] += m[key]
-            frames += m["frames"]
-            clips += 1
-    vec = torch.tensor(sums + [float(frames), float(clips)], dtype=torch.float64, device=device)
-    if dist is not None and dist.is_initialized():
-        dist.all_reduce(vec, op=dist.ReduceOp.SUM)
-    v = vec.tolist()
-    clips = v[len(RECON_KEYS) + 1]
-    out = {k: v[i] / clips if clips else float("nan") for i, k in enumerate(RECON_KEYS)}
-    out["frames"] = int(v[len(RECON_KEYS)])
-    out["clips"] = int(clips)
-    return out
-
-
-CAMERA_KEYS = ("ATE", "RPE_t", "RPE_r")
+    """The "recon" block: every clip's PSNR and SSIM (quality.evaluate: means over its frames), averaged over the clips
+    that have a frame (``clips``); ``frames`` is their total."""
+    ms = [QL.evaluate(rec) for rec in recons.values()]
+    totals = dict(frames=sum(m["frames"] for m in ms), clips=sum(1 for m in ms if m["frames"]))
+    return _mean_over_clips(RECON_KEYS, ms, totals, dist, device)
 
 
 def reduce_camera(cams, dist=None, device="cpu"):
-    """The "camera" block of the JSON line: every clip's ATE, RPE_t and RPE_r (fit_clip's ``out["camera"]``), averaged over
-    the clips that have a score; a clip whose score is None (camera.evaluate: no alignment exists) counts in
-    ``clips_unscored``, not in the mean.  The three are None when no clip was scored.  Over ranks by ONE more small
-    all-reduce(SUM) of (the three sums, clips, clips unscored)."""
-    sums, clips, unscored = [0.0] * len(CAMERA_KEYS), 0, 0
-    for cam in cams.values():
-        if any(cam[k] is None for k in CAMERA_KEYS):
-            unscored += 1
-            continue
-        for k, key in enumerate(CAMERA_KEYS):
-            sums[k] += float(cam[key])
-        clips += 1
-    vec = torch.tensor(sums + [float(clips), float(unscored)], dtype=torch.float64, device=device)
-    if dist is not None and dist.is_initialized():
-        dist.all_reduce(vec, op=dist.ReduceOp.SUM)
-    v = vec.tolist()
-    clips = v[len(CAMERA_KEYS)]
-    out = {k: v[i] / clips if clips else None for i, k in enumerate(CAMERA_KEYS)}
-    out["clips"] = int(clips)
-    out["clips_unscored"] = int(v[len(CAMERA_KEYS) + 1])
-    return out
-
-
-FLOW_KEYS = ("EPE", "EPE_still", "EPE_moving", "acc_1px", "acc_3px", "acc_5px", "coverage")
+    """The "camera" block: every clip's ATE, RPE_t and RPE_r (fit_clip's ``out["camera"]``), averaged over the clips that
+    have a score (``clips``); a clip whose score is None (camera.evaluate: no alignment exists) counts in
+    ``clips_unscored``, not in the mean.  The three are None when no clip was scored."""
+    scored = [cam for cam in cams.values() if not any(cam[k] is None for k in CAMERA_KEYS)]
+    totals = dict(clips=len(scored), clips_unscored=len(cams) - len(scored))
+    return _mean_over_clips(CAMERA_KEYS, scored, totals, dist, device, none=None)
 
 
 def reduce_flow(flows, dist=None, device="cpu"):
-    """The "flow" block of the JSON line: every clip's numbers (flow.evaluate: pooled over its pairs), each averaged over
-    the clips where it is a number (a clip without a moving pixel has no EPE_moving; a one-frame clip has nothing);
-    ``pairs`` is the clips' total, ``clips`` those with a pair.  None where no clip has the number.  Over ranks by ONE more
-    small all-reduce(SUM) of (the seven sums, their seven counts, pairs, clips)."""
-    import math
-    from . import flow as FL
-    k = len(FLOW_KEYS)
-    sums, counts, pairs, clips = [0.0] * k, [0.0] * k, 0, 0
-    for fl in flows.values():
-        m = FL.evaluate(fl)
-        pairs += m["pairs"]
-        clips += 1 if m["pairs"] else 0
-        for j, key in enumerate(FLOW_KEYS):
-            if not math.isnan(m[key]):
-                sums[j] += m[key]
-                counts[j] += 1.0
-    vec = torch.tensor(sums + counts + [float(pairs), float(clips)], dtype=torch.float64, device=device)
-    if dist is not None and dist.is_initialized():
-        dist.all_reduce(vec, op=dist.ReduceOp.SUM)
-    v = vec.tolist()
-    out = {key: v[j] / v[k + j] if v[k + j] else None for j, key in enumerate(FLOW_KEYS)}
-    out["pairs"] = int(v[2 * k])
-    out["clips"] = int(v[2 * k + 1])
-    return out
+    """The "flow" block: every clip's numbers (flow.evaluate: pooled over its pairs), each averaged over the clips where
+    it is a number (a clip without a moving pixel has no EPE_moving; a one-frame clip has nothing); ``pairs`` is the
+    clips' total, ``clips`` those with a pair.  None where no clip has the number."""
+    ms = [FL.evaluate(fl) for fl in flows.values()]
+    totals = dict(pairs=sum(m["pairs"] for m in ms), clips=sum(1 for m in ms if m["pairs"]))
+    return _mean_over_clips(FLOW_KEYS, ms, totals, dist, device, none=None)
 
 
 def csv_metrics(out):
@@ -340,17 +280,50 @@ def stage_kwargs(c, frames, i, stage):
     raise ValueError(stage)
 
 
-def fit_clip(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, log=None, load_extr=True, keep=None,
-             async_snapshots=None, deterministic=None, track_queries=None, segment=False, recon=False, camera=False,
-             flow=False):
-    """Fit one clip; returns the metrics dict of this clip (PSNR summed over its frames; with ``cfg["traj_num"]`` > 0 also
-    ``"traj"``: the per-frame trajectory images and seed projections, host arrays -- what the reference's frame loop collects in
-    ``frames_sequence_traj / frames_sequence_traj_upon / sequence_traj``).
+def fit_clip(frames, device, cfg=None, fused=True, deterministic=None, **options):
+    """Fit one clip; returns the metrics dict of this clip.  ``options``: fit_clip_steps' (whose docstring names them all),
+    without ``chunk`` and ``cu_count``.  On a device the fit runs on a stream of its own, which the current stream waits
+    for."""
+    if deterministic and not fused:
+        raise ValueError("fit_clip(deterministic=True) needs fused=True: the operator path's alpha_blending backward has no "
+                         "deterministic implementation")
+    from .trainer import run_to_end
+    dev_ = torch.device(device)
+    g = fit_clip_steps(frames, device, cfg, fused=fused, deterministic=deterministic, chunk=None, cu_count=0, **options)
+
+    drive = lambda: run_to_end(g)
+    if dev_.type == "cuda" and torch.cuda.current_stream(dev_) == torch.cuda.default_stream(dev_):
+        # Never fit on the default stream: it is HIP's legacy NULL stream, which every other (blocking) stream
+        # synchronises with -- the snapshot copies on the copy stream then run BETWEEN the fit's launches instead of
+        # beside them (measured: the same 8-frame clip fit 0.95 s on a stream of its own, 1.09 s on the default stream).
+        key = dev_.index
+        if key not in _FIT_STREAMS:
+            _FIT_STREAMS[key] = torch.cuda.Stream(device=dev_)
+        fs = _FIT_STREAMS[key]
+        fs.wait_stream(torch.cuda.current_stream(dev_))
+        with torch.cuda.stream(fs):
+            out = drive()
+        torch.cuda.current_stream(dev_).wait_stream(fs)
+        return out
+    return drive()
+
+
+def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, log=None, load_extr=True, chunk=None,
+                   async_snapshots=True, keep=None, cu_count=0, deterministic=None, track_queries=None, segment=False,
+                   recon=False, camera=False, flow=False):
+    """fit_clip as a generator: yields after every ``chunk`` iterations of a stage (None: never) and returns the metrics
+    dict of the clip (PSNR summed over its frames; with ``cfg["traj_num"]`` > 0 also ``"traj"``: the per-frame trajectory
+    images and seed projections, host arrays -- what the reference's frame loop collects in
+    ``frames_sequence_traj / frames_sequence_traj_upon / sequence_traj``).  The caller owns the stream the work is enqueued
+    on (fit_clips_concurrent gives every clip its own; ``cu_count``: that stream is CU-masked to so many CUs).  The
+    options, which fit_clip and fit_clips_concurrent hand through:
     ``load_extr`` (default True, like the reference's flag): frames that carry a camera pose
     (``extr``, read from the sequence's camera files) load it before they are fitted
     (fit_video.py:115-116, :252-253).  ``keep``: a dict that receives the trainer (``keep["trainer"]``) and the
     per-frame PSNR as device scalars (``keep["psnr"]``) -- for tests and tools; with ``cfg["traj_num"]`` also the per-frame
     trajectory images and seed projections as they left for the host (``keep["traj"]``).
+    ``async_snapshots``: the snapshots of ``snapshot_interval`` are composed beside the next iterations (trainer.py), not
+    behind theirs.
     ``deterministic``: the same frames, cfg and seed give the same metrics, parameters and trajectory outputs bit for bit
     (SimpleGaussian(deterministic=)); None follows torch.are_deterministic_algorithms_enabled().  Needs
     ``fused=True``.
@@ -377,38 +350,6 @@ def fit_clip(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, 
     still, moving)); ``flow="maps"`` also keeps the maps: ``maps`` (T-1, H, W, 2) float32, frame i -> i + 1 on frame i's
     grid, and ``valid`` (T-1, H, W) bool.  A one-frame clip gives empty arrays.  ``keep["record_flow_inputs"] = True``: clones
     of each pair's kernel inputs (dicts) in ``keep["flow_inputs"]``."""
-    if deterministic and not fused:
-        raise ValueError("fit_clip(deterministic=True) needs fused=True: the operator path's alpha_blending backward has no "
-                         "deterministic implementation")
-    from .trainer import run_to_end
-    dev_ = torch.device(device)
-    g = fit_clip_steps(frames, device, cfg=cfg, seed=seed, snapshot_interval=snapshot_interval, fused=fused, log=log,
-                       load_extr=load_extr, chunk=None, keep=keep, deterministic=deterministic, track_queries=track_queries,
-                       segment=segment, recon=recon, camera=camera, flow=flow,
-                       **({} if async_snapshots is None else {"async_snapshots": async_snapshots}))
-
-    drive = lambda: run_to_end(g)
-    if dev_.type == "cuda" and torch.cuda.current_stream(dev_) == torch.cuda.default_stream(dev_):
-        # Never fit on the default stream: it is HIP's legacy NULL stream, which every other (blocking) stream
-        # synchronises with -- the snapshot copies on the copy stream then run BETWEEN the fit's launches instead of
-        # beside them (measured: the same 8-frame clip fit 0.95 s on a stream of its own, 1.09 s on the default stream).
-        key = dev_.index
-        if key not in _FIT_STREAMS:
-            _FIT_STREAMS[key] = torch.cuda.Stream(device=dev_)
-        fs = _FIT_STREAMS[key]
-        fs.wait_stream(torch.cuda.current_stream(dev_))
-        with torch.cuda.stream(fs):
-            out = drive()
-        torch.cuda.current_stream(dev_).wait_stream(fs)
-        return out
-    return drive()
-
-
-def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, log=None, load_extr=True, chunk=None,
-                   async_snapshots=True, keep=None, cu_count=0, deterministic=None, track_queries=None, segment=False,
-                   recon=False, camera=False, flow=False):
-    """fit_clip as a generator: yields after every ``chunk`` iterations of a stage (None: never) and returns the metrics
-    dict.  The caller owns the stream the work is enqueued on (fit_clips_concurrent gives every clip its own)."""
     from .trainer import SimpleGaussian
     c = dict(DEFAULTS)
     c.update(cfg or {})
@@ -417,31 +358,26 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
     f0 = frames[0]
     tracker = None
     if track_queries is not None:
-        from .tracking import Tracker
-        tracker = Tracker(track_queries, len(frames), device)        # (ValueError before anything is fitted)
+        tracker = TK.Tracker(track_queries, len(frames), device)     # (ValueError before anything is fitted)
     cam_rec = None
     if camera:
-        from .camera import CameraRecorder
         cam_gt = [fr["extr_gt"] if fr.get("extr_gt") is not None else fr.get("extr") for fr in frames]
         missing = [t for t, e in enumerate(cam_gt) if e is None]
         if missing:
             raise ValueError(f"fit_clip(camera=True): frames {missing} carry neither extr_gt nor extr")
-        cam_rec = CameraRecorder(len(frames))
+        cam_rec = CM.CameraRecorder(len(frames))
     tr = SimpleGaussian(f0["image"], f0["depth"], num_points=c["num_points"], background=c["background"],
                         device=device, seed=seed, fused=fused, deterministic=deterministic)
     tr.async_snapshots = bool(async_snapshots)       # (trainer.py: snapshots composed beside the next iterations, or behind theirs)
     tr.cu_count = int(cu_count)                      # (the caller's stream is CU-masked: fit_clips_concurrent(partition=True))
     if segment:
-        from .segmentation import MoveSegRecorder
-        tr.seg_recorder = MoveSegRecorder(len(frames), tr.H, tr.W, tr.device)
+        tr.seg_recorder = SG.MoveSegRecorder(len(frames), tr.H, tr.W, tr.device)
     recon_rec = None
     if recon:
-        from .quality import ReconRecorder
-        recon_rec = ReconRecorder(len(frames), tr.H, tr.W, tr.device)
+        recon_rec = QL.ReconRecorder(len(frames), tr.H, tr.W, tr.device)
     flow_rec = None
     if flow:
-        from .flow import FlowRecorder
-        flow_rec = FlowRecorder(len(frames), tr.H, tr.W, tr.device, keep_maps=flow == "maps")
+        flow_rec = FL.FlowRecorder(len(frames), tr.H, tr.W, tr.device, keep_maps=flow == "maps")
         if keep is not None and keep.get("record_flow_inputs"):
             flow_rec.inputs = keep.setdefault("flow_inputs", [])
     tr.load_camera(focal=f0["focal"], pp=f0["pp"])
@@ -461,6 +397,17 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
                               move_seg=traj,   # (the seeds' grid needs the first frame's hull mask: host work, once per clip)
                               **common)
     traj_rec = []                                        # per frame: where the seeds are, the camera, the scene's rgb image
+    final = []                                           # this frame's final_forward, once it has run (end_of_frame empties it)
+
+    def final_forward():
+        # The forward of THIS frame's final state on the second engine (fused path): run when the first of the frame's
+        # recorders asks for it, shared by those after it -- the frame is rasterised once more, not once per recorder.  (The
+        # trajectory recorder asks first and has the scene's images taken from it: see there.)
+        if not final:
+            final.append(tr._aux_forward())
+            final[0].watch_overflow()
+            tr.rasterisations_done += 1
+        return final[0]
 
     def record_trajectories():
         # fit_video.py:226-238 / 335-349 call trainer.eval + project_points here, after every frame.  What they need of THIS
@@ -471,29 +418,24 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
         with torch.no_grad():
             xyz_now = tr.get_attribute("xyz")[traj_index_t].detach().float().clone()
             extr_now = tr.get_extr().detach().clone()
-            aux = None
             if tr.engine_current:
+                # (the frame's forward, the snapshot of its images, then the overflow watch: final_forward's forward with
+                #  the snapshot in between, so it is handed to final_forward's readers)
                 rgb_u8 = tr._render_scene_fused()[0].clone()
-                aux = tr._aux
+                final.append(tr._aux)
             else:
                 from . import render as render_mod
                 rgb_u8 = render_mod.render2img_device(render_mod.render_multiple(tr._input_group(detach=True), ["rgb"])["rgb"])
             tr.rasterisations_done += 1
         traj_rec.append((xyz_now, extr_now, rgb_u8))
-        return aux
 
-    def record_tracks(i, shared):
-        # benchmark.py:98-139 for frame i, on the frame's final state: the uv / depth / depth_map of one forward -- the one
-        # record_trajectories has just run on the second engine (``shared``), or one of its own -- go to the tracker's two
-        # launches; nothing is read back
+    def record_tracks(i):
+        # benchmark.py:98-139 for frame i, on the frame's final state: the uv / depth / depth_map of one forward go to the
+        # tracker's two launches; nothing is read back
         with torch.no_grad():
             if tr.engine_current:
-                aux = shared
-                if aux is None:
-                    aux = tr._aux_forward()
-                    aux.watch_overflow()
-                    tr.rasterisations_done += 1
                 from .fused import REC
+                aux = final_forward()
                 n = aux.N
                 uv, uv_stride, depth, depth_stride, dm = aux.rec[:n, 0:2], REC, aux.rec[:n, 9], REC, aux.render[3]
             else:
@@ -506,23 +448,16 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
             tracker.frame(i, uv, uv_stride, depth, depth_stride, dm)
             if keep is not None and keep.get("record_track_inputs"):
                 keep.setdefault("track_inputs", []).append((uv.clone(), depth.clone(), dm.clone()))
-            return aux if tr.engine_current else None
 
-    def record_flow(i, shared):
-        # frame i's final records and sorted tile lists go to the flow recorder: those of the forward the trajectory recorder
-        # or the tracker has just run on the second engine (``shared``), or of one of its own; on the operator path the
-        # five operators' outputs, packed.  From frame 1 on one gfl_flow_pair for the pair (i - 1, i); nothing is read back
+    def record_flow(i):
+        # frame i's final records and sorted tile lists go to the flow recorder (on the operator path the five operators'
+        # outputs, packed).  From frame 1 on one gfl_flow_pair for the pair (i - 1, i); nothing is read back
         with torch.no_grad():
             if tr.engine_current:
-                aux = shared
-                if aux is None:
-                    aux = tr._aux_forward()
-                    aux.watch_overflow()
-                    tr.rasterisations_done += 1
+                aux = final_forward()
                 rec, n, ids, tile_range = aux.rec, aux.N, aux.ids, aux.tile_range
             else:
-                from .flow import operator_state
-                rec, n, ids, tile_range = operator_state(tr._input_group(detach=True))
+                rec, n, ids, tile_range = FL.operator_state(tr._input_group(detach=True))
                 tr.rasterisations_done += 1
             prev = frames[i - 1] if i else None
             flow_rec.frame(i, rec, n, ids, tile_range, prev["flow"] if prev else None, prev["move_mask"] if prev else None)
@@ -556,25 +491,37 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
                                                                for x in tr.last_traj_group])
         return torch.stack(imgs), torch.stack(uvs)
 
+    psnr_sum = None
+
+    def end_of_frame(i):
+        # what every frame ends with, once its stages are fitted: the recorders that read the frame's final state (which share
+        # final_forward's forward), its PSNR, the scores taken where the PSNR is
+        nonlocal psnr_sum
+        final.clear()
+        if traj:
+            record_trajectories()
+        if tracker is not None:
+            record_tracks(i)
+        if flow_rec is not None:
+            record_flow(i)
+        # (PSNR stays on the device and is read ONCE at the end of the clip: a float() per frame drained the queue between
+        #  two frames; with a log callback the caller asked for the numbers as they come)
+        p = tr.psnr()
+        psnr_sum = p.double() if psnr_sum is None else psnr_sum + p.double()
+        if recon_rec is not None or cam_rec is not None:
+            record_scores(i)
+        if keep is not None:
+            keep["psnr"].append(p)
+        if log:
+            log(f"frame {i}: psnr {float(p):.2f} dB, splats {tr.current_pts_num()}")
+
     if traj:
         traj_index, split_interval = select_traj_seeds(tr, int(c["traj_num"]), int(c["traj_offset"]))
         traj_index_t = torch.as_tensor(traj_index, device=tr.device).long()
-        shared = record_trajectories()
-    shared = shared if traj else None
-    if tracker is not None:
-        shared = record_tracks(0, shared) or shared
-    if flow_rec is not None:
-        record_flow(0, shared)
-    # (PSNR stays on the device and is read ONCE at the end of the clip: a float() per frame drained the queue between
-    #  two frames; with a log callback the caller asked for the numbers as they come)
-    psnr_sum = tr.psnr().double()
-    if recon_rec is not None or cam_rec is not None:
-        record_scores(0)
     if keep is not None:
-        keep["trainer"], keep["psnr"] = tr, [psnr_sum]
-    if log:
-        log(f"frame 0: psnr {float(psnr_sum):.2f} dB, splats {tr.current_pts_num()}")
-    for i, fr in enumerate(frames[1:], start=1):
+        keep["trainer"], keep["psnr"] = tr, []
+    end_of_frame(0)
+    for i in range(1, len(frames)):
         begin_frame(tr, frames, i, load_extr)
         if segment:
             tr.seg_recorder.frame = i
@@ -582,19 +529,7 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
             yield from tr.train_steps(**stage_kwargs(c, frames, i, "camera"), **common)
         if c["iterations_after"] > 0:                    # fit_video.py:288-315
             yield from tr.train_steps(**stage_kwargs(c, frames, i, "joint"), **common)
-        shared = record_trajectories() if traj else None
-        if tracker is not None:
-            shared = record_tracks(i, shared) or shared
-        if flow_rec is not None:
-            record_flow(i, shared)
-        p = tr.psnr()
-        psnr_sum = psnr_sum + p.double()
-        if recon_rec is not None or cam_rec is not None:
-            record_scores(i)
-        if keep is not None:
-            keep["psnr"].append(p)
-        if log:
-            log(f"frame {i}: psnr {float(p):.2f} dB, splats {tr.current_pts_num()}")
+        end_of_frame(i)
     if tr.engine is not None:
         tr.engine.check_overflow()
     if traj:
@@ -635,7 +570,6 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
         out["recon"] = recon_rec.result()             # (one copy of the (T, 2) sums)
     if cam_rec is not None:
         import numpy as np
-        from . import camera as CM
         extr = cam_rec.result()                       # (one stacked copy)
         gt = np.stack([torch.as_tensor(e).detach().cpu().double().numpy().reshape(3, 4) for e in cam_gt])
         out["camera"] = dict(extr=extr, **CM.evaluate(extr, gt))
@@ -650,9 +584,8 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
 NUMERIC_KEYS = ("psnr_sum", "frames", "iterations", "rasterisations", "clips", "splats_final", "void_iterations")
 
 
-def fit_clips_concurrent(clips, device, cfg=None, seeds=None, snapshot_interval=0, chunk=32, partition=False,
-                         deterministic=None, track_queries=None, segment=False, recon=False, camera=False, load_extr=True,
-                         flow=False):
+def fit_clips_concurrent(clips, device, cfg=None, seeds=None, chunk=32, partition=False, deterministic=None,
+                         track_queries=None, **options):
     """Fit several clips AT THE SAME TIME on ONE device, in one host thread: every clip has its own trainer, engine and
     STREAM, and the clips take turns enqueueing ``chunk`` iterations each (fit_clip_steps), so their graph launches
     interleave on the device.  One fit leaves the chip partly idle -- its kernels are a chain of dependent launches,
@@ -669,8 +602,8 @@ def fit_clips_concurrent(clips, device, cfg=None, seeds=None, snapshot_interval=
     on it (the schedule never enters a result).  Measured in bench.py's ``clips_per_gpu`` table.
     ``deterministic`` (None: torch's switch): every clip's result is bit for bit that of fit_clip(..., deterministic=True)
     with the same seed -- without ``partition``, which changes the number of tile queues (include/gflow_hip.h).
-    ``track_queries``: None, or one entry (fit_clip's ``track_queries``, or None) per clip.  ``segment``, ``recon``,
-    ``camera``, ``load_extr``, ``flow``: fit_clip's, for all clips."""
+    ``track_queries``: None, or one entry (fit_clip_steps' ``track_queries``, or None) per clip.  ``options``: fit_clip_steps'
+    other ones, for all clips (``async_snapshots`` and ``cu_count`` are set here)."""
     n = len(clips)
     if track_queries is not None and len(track_queries) != n:
         raise ValueError("fit_clips_concurrent: track_queries needs one entry per clip")
@@ -690,10 +623,9 @@ def fit_clips_concurrent(clips, device, cfg=None, seeds=None, snapshot_interval=
         s.wait_stream(cur)
     # (a lone fit takes its snapshots on a side stream; several fits already fill each other's gaps, and a side stream + shadow
     #  engine per clip cost them more than they give)
-    gens = [fit_clip_steps(clips[i], dev, cfg, seed=seeds[i], snapshot_interval=snapshot_interval, chunk=chunk,
-                           async_snapshots=n == 1, cu_count=shares[i][1] if shares else 0, deterministic=deterministic,
-                           track_queries=None if track_queries is None else track_queries[i], segment=segment,
-                           recon=recon, camera=camera, load_extr=load_extr, flow=flow)
+    gens = [fit_clip_steps(clips[i], dev, cfg, seed=seeds[i], chunk=chunk, async_snapshots=n == 1,
+                           cu_count=shares[i][1] if shares else 0, deterministic=deterministic,
+                           track_queries=None if track_queries is None else track_queries[i], **options)
             for i in range(n)]
     results = [None] * n
     live = list(range(n))
@@ -805,7 +737,6 @@ def main(argv=None):
     # point tracking: the ground truth of every clip, its first-visible queries (those whose frame is not fitted: dropped)
     gts, queries, dropped = {}, {}, 0
     if args.track:
-        from . import tracking as TK
         for ci in mine:
             h, w = clips[ci][0]["image"].shape[:2]
             if args.sequence:
@@ -823,67 +754,56 @@ def main(argv=None):
     t0 = time.perf_counter()
     c = max(1, args.clips_per_gpu)
     order = sorted(clips, key=lambda j: (-lengths[j], j))          # (clips of similar length share the GPU)
-    preds, segs, recons, cams, flows = {}, {}, {}, {}, {}
-    flow = ("maps" if args.flow_out else True) if args.flow else False
-    load_extr = not args.no_load_extr
+    options = dict(deterministic=det, segment=args.seg, recon=args.recon, camera=args.camera,
+                   flow=("maps" if args.flow_out else True) if args.flow else False, load_extr=not args.no_load_extr)
+    results = {}
     for g0 in range(0, len(order), c):
         group = order[g0:g0 + c]
         if len(group) == 1:
             ci = group[0]
-            res = [fit_clip(clips[ci], dev, cfg, seed=ci, deterministic=det, track_queries=queries.get(ci), segment=args.seg,
-                            recon=args.recon, camera=args.camera, load_extr=load_extr, flow=flow,
+            res = [fit_clip(clips[ci], dev, cfg, seed=ci, track_queries=queries.get(ci), **options,
                             log=(lambda s, ci=ci: print(f"[rank {rank} clip {ci}] {s}")) if args.verbose else None)]
         else:
-            res = fit_clips_concurrent([clips[ci] for ci in group], dev, cfg, seeds=group, deterministic=det,
-                                       track_queries=[queries.get(ci) for ci in group] if args.track else None,
-                                       segment=args.seg, recon=args.recon, camera=args.camera, load_extr=load_extr, flow=flow)
+            res = fit_clips_concurrent([clips[ci] for ci in group], dev, cfg, seeds=group,
+                                       track_queries=[queries.get(ci) for ci in group] if args.track else None, **options)
         for ci, m in zip(group, res):
             for k in METRIC_NAMES:
                 local[k] += m[k]
-            if "tracks" in m:
-                preds[ci] = m["tracks"]
-            if "segmentation" in m:
-                segs[ci] = m["segmentation"]
-            if "recon" in m:
-                recons[ci] = m["recon"]
-            if "camera" in m:
-                cams[ci] = m["camera"]
-            if "flow" in m:
-                flows[ci] = m["flow"]
+            results[ci] = m
     torch.cuda.synchronize()
-    out = reduce_metrics(local, time.perf_counter() - t0, dist, torch.device("cpu") if (world > 1 and shared) else dev,
-                         rank=rank, world=world)
+    wall = time.perf_counter() - t0
+    of = lambda key: {ci: m[key] for ci, m in results.items()}         # (a block that was asked for is in every clip's dict)
+    over_ranks = (dist, torch.device("cpu") if (world > 1 and shared) else dev)
+    out = reduce_metrics(local, wall, *over_ranks, rank=rank, world=world)
     if args.track:
-        out["tapvid"] = reduce_tapvid(preds, gts, {ci: len(clips[ci]) for ci in clips}, dropped, dist,
-                                      torch.device("cpu") if (world > 1 and shared) else dev)
+        preds = of("tracks")
+        out["tapvid"] = reduce_tapvid(preds, gts, {ci: len(clips[ci]) for ci in clips}, dropped, *over_ranks)
         if args.track_out:
             import numpy as np
             os.makedirs(args.track_out, exist_ok=True)
             for ci, p in preds.items():
                 np.savez(os.path.join(args.track_out, f"clip_{ci}.npz"), queries=queries[ci], **p)
     if args.seg:
-        out["davis"] = reduce_davis(segs, dist, torch.device("cpu") if (world > 1 and shared) else dev)
+        out["davis"] = reduce_davis(of("segmentation"), *over_ranks)
         if args.seg_out:
             from PIL import Image
-            for ci, seg in segs.items():
+            for ci, seg in of("segmentation").items():
                 d = os.path.join(args.seg_out, f"clip_{ci}")
                 os.makedirs(d, exist_ok=True)
                 for t in range(len(seg["masks"])):
                     if seg["valid"][t]:                      # (no file for a frame without a mask, like the reference)
                         Image.fromarray(seg["masks"][t]).save(os.path.join(d, f"move_mask_{t:05d}.png"))
     if args.recon:
-        out["recon"] = reduce_recon(recons, dist, torch.device("cpu") if (world > 1 and shared) else dev)
+        out["recon"] = reduce_recon(of("recon"), *over_ranks)
     if args.camera:
-        out["camera"] = reduce_camera(cams, dist, torch.device("cpu") if (world > 1 and shared) else dev)
+        out["camera"] = reduce_camera(of("camera"), *over_ranks)
     if args.flow:
-        out["flow"] = reduce_flow(flows, dist, torch.device("cpu") if (world > 1 and shared) else dev)
+        out["flow"] = reduce_flow(of("flow"), *over_ranks)
         if args.flow_out:
-            from .flow import write_flo_maps
-            for ci, fl in flows.items():
-                write_flo_maps(os.path.join(args.flow_out, f"clip_{ci}"), fl)
+            for ci, fl in of("flow").items():
+                FL.write_flo_maps(os.path.join(args.flow_out, f"clip_{ci}"), fl)
     if rank == 0 and args.metrics_csv:
-        from .quality import write_metrics_csv
-        write_metrics_csv(args.metrics_csv, csv_metrics(out))
+        QL.write_metrics_csv(args.metrics_csv, csv_metrics(out))
     if rank == 0:
         out["frames_per_s"] = out["frames"] / out["wall_s"]
         out["iterations_per_s"] = out["iterations"] / out["wall_s"]

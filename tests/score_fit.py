@@ -1,6 +1,7 @@
-"""What tests/test_gpu_recon.py and tests/test_gpu_camera.py share: ONE deterministic 8-frame 96 x 128 clip fit with
-``recon=True, camera=True`` (tests/test_gpu_seg.py's settings, trajectories and tracked queries on), computed on first use
-and left unchanged, and the two contracts a fit's ``out["recon"]`` and ``out["camera"]`` hold."""
+"""What the GPU tests of the clip fit's scores share.  The small clip they fit -- ``FIT``'s settings on 96 x 128 synthetic
+frames (``clip``) and its first-visible queries (``queries``).  For tests/test_gpu_recon.py and tests/test_gpu_camera.py ONE
+deterministic 8-frame fit of it with ``recon=True, camera=True`` (trajectories and tracked queries on), computed on first
+use and left unchanged, and the two contracts a fit's ``out["recon"]`` and ``out["camera"]`` hold."""
 import functools
 
 import numpy as np
@@ -9,13 +10,33 @@ import torch
 
 from tests import camera_ref as CR
 from tests import quality_ref as QR
-from tests.test_gpu_seg import FIT, H, T, W, _clip, _queries
 
 DEV = "cuda"
+FIT = dict(num_points=1500, iterations_first=60, iterations_after=40, iterations_camera=20, densify_interval=30,
+           densify_times=1, densify_interval_after=20, densify_times_after=1, lambda_depth=1e-2)
+H, W, T = 96, 128, 8
 # float64 on both sides over at most 1.3 M terms (n 2^-53 ~ 1.4e-10)
 SSE_REL, SSE_ABS_AT_ZERO, SSIM_ABS = 1e-9, 1e-12, 1e-9
 PSNR_DB = 1e-2                    # the bound the project already uses between its float32 PSNR sum and float64
 CAMERA_REL = 1e-6                 # the optimiser's stopping accuracy (tests/camera_ref.py)
+
+
+def clip(seed=0, n_frames=T, load_gt_pose=False):
+    """``load_gt_pose``: every frame carries its ground-truth camera as ``extr``, which the fit then loads"""
+    from gflow_amd import synthetic as S
+    frames = S.make_clip(n_frames, H, W, seed=seed)
+    if load_gt_pose:
+        for fr in frames:
+            fr["extr"] = fr["extr_gt"]
+    return frames
+
+
+def queries(n_frames=T, n=48, seed=0):
+    """(the clip's ground-truth tracks of ``n`` points, their first-visible queries)"""
+    from gflow_amd import synthetic as S
+    from gflow_amd import tracking as TK
+    g = S.make_clip_tracks(n_frames, H, W, seed=seed, n_queries=n, query_seed=0)
+    return g, TK.first_visible_queries(g["points"].astype(np.float32), g["occluded"], H, W)
 
 
 def fit(frames, on, fused=True, cfg=FIT, seed=0, q=None, **kw):
@@ -29,8 +50,8 @@ def fit(frames, on, fused=True, cfg=FIT, seed=0, q=None, **kw):
 @functools.lru_cache(maxsize=None)
 def scored_fit():
     """(frames, queries, out, keep) of the shared fit"""
-    frames = _clip()
-    q = _queries()
+    frames = clip()
+    _, q = queries()
     out, keep = fit(frames, True, cfg=dict(FIT, traj_num=50), q=q)
     return frames, q, out, keep
 

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from tests import score_fit as SF
-from tests.test_gpu_seg import FIT, H, W, _clip
+from tests.score_fit import FIT, H, W, clip
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -33,7 +33,7 @@ def test_scores_change_nothing_else():
 
 
 def test_operator_path_gives_the_same_contracts():
-    frames = _clip(n_frames=4)
+    frames = clip(n_frames=4)
     out, keep = SF.fit(frames, True, fused=False)
     SF.check_recon_contract(frames, out, keep)
     SF.check_camera_contract(frames, out, keep)
@@ -43,7 +43,7 @@ def test_loaded_poses_are_the_recorded_poses():
     # frames that carry ``extr`` and load it, a fit without camera stages: the recorded path is the loaded one, and ``extr``
     # is the ground truth where there is no ``extr_gt``
     frames = []
-    for fr in _clip(n_frames=3):
+    for fr in clip(n_frames=3):
         d = dict(fr)
         d["extr"] = d.pop("extr_gt")
         frames.append(d)
@@ -55,7 +55,7 @@ def test_loaded_poses_are_the_recorded_poses():
 
 def test_concurrent_clips_take_both_scores():
     from gflow_amd.fit_video import fit_clips_concurrent
-    clips = [_clip(seed=0, n_frames=3), _clip(seed=1, n_frames=3)]
+    clips = [clip(seed=0, n_frames=3), clip(seed=1, n_frames=3)]
     res = fit_clips_concurrent(clips, DEV, FIT, seeds=[0, 1], deterministic=True, recon=True, camera=True)
     for ci, r in enumerate(res):
         lone, _ = SF.fit(clips[ci], True, seed=ci)

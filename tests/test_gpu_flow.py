@@ -9,12 +9,10 @@ import pytest
 import torch
 
 from tests import flow_ref as R
+from tests.score_fit import FIT, H, T, W, clip
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-FIT = dict(num_points=1500, iterations_first=60, iterations_after=40, iterations_camera=20, densify_interval=30,
-           densify_times=1, densify_interval_after=20, densify_times_after=1, lambda_depth=1e-2)     # tests/test_gpu_tracking.py's
-H, W, T = 96, 128, 8
 SENTINEL = -12345.5
 
 
@@ -240,15 +238,6 @@ def test_the_extremes_of_the_valid_ranges_are_accepted():
 
 
 # ---------------------------------------------------------------------------------------------------- through the fit
-def _clip(seed=0, n_frames=T, load_gt_pose=True):
-    from gflow_amd import synthetic as S
-    frames = S.make_clip(n_frames, H, W, seed=seed)
-    if load_gt_pose:
-        for fr in frames:
-            fr["extr"] = fr["extr_gt"]
-    return frames
-
-
 def _fit(frames, fused=True, cfg=FIT, seed=0, flow="maps", record=True):
     from gflow_amd.fit_video import fit_clip
     keep = {"record_flow_inputs": True} if record else {}
@@ -258,7 +247,7 @@ def _fit(frames, fused=True, cfg=FIT, seed=0, flow="maps", record=True):
 
 @pytest.fixture(scope="module")
 def det_fit():
-    frames = _clip()
+    frames = clip(load_gt_pose=True)
     out, keep = _fit(frames)
     return frames, out, keep
 
@@ -287,14 +276,14 @@ def test_fit_flow_equals_the_restatement(det_fit):
 
 
 def test_fit_flow_equals_the_restatement_operator_path():
-    frames = _clip(n_frames=4)
+    frames = clip(n_frames=4, load_gt_pose=True)
     out, keep = _fit(frames, fused=False)
     _check_fit_against_restatement(frames, out, keep, 4)
 
 
 def test_flow_leaves_the_fit_unchanged():
     from gflow_amd.fit_video import fit_clip
-    frames = _clip(n_frames=4)
+    frames = clip(n_frames=4, load_gt_pose=True)
     cfg = dict(FIT, traj_num=50)
     a = fit_clip(frames, DEV, cfg, seed=0, deterministic=True)
     b = fit_clip(frames, DEV, cfg, seed=0, deterministic=True, flow=True)
@@ -315,7 +304,7 @@ def test_flow_leaves_the_fit_unchanged():
 
 def test_concurrent_fits_equal_the_lone_fits():
     from gflow_amd.fit_video import fit_clips_concurrent
-    clips = [_clip(seed=0, n_frames=4), _clip(seed=1, n_frames=4)]
+    clips = [clip(seed=s, n_frames=4, load_gt_pose=True) for s in (0, 1)]
     lone = [_fit(c, seed=s, record=False)[0] for s, c in enumerate(clips)]
     res = fit_clips_concurrent(clips, DEV, FIT, seeds=[0, 1], deterministic=True, flow="maps")
     for r, want in zip(res, lone):

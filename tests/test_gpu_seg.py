@@ -12,14 +12,12 @@ import pytest
 import torch
 
 from tests import seg_ref as R
+from tests.score_fit import FIT, H, W, clip, queries
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden", "davis_seg.npz")
-FIT = dict(num_points=1500, iterations_first=60, iterations_after=40, iterations_camera=20, densify_interval=30,
-           densify_times=1, densify_interval_after=20, densify_times_after=1, lambda_depth=1e-2)
-H, W, T = 96, 128, 8
 GARBAGE = 0x5EEDBEEF
 
 
@@ -127,18 +125,6 @@ def test_argument_errors():
 
 
 # ------------------------------------------------------------------------------------------------------------- fits
-def _clip(seed=0, n_frames=T):
-    from gflow_amd import synthetic as S
-    return S.make_clip(n_frames, H, W, seed=seed)
-
-
-def _queries(n_frames=T, n=48, seed=0):
-    from gflow_amd import synthetic as S
-    from gflow_amd import tracking as TK
-    g = S.make_clip_tracks(n_frames, H, W, seed=seed, n_queries=n, query_seed=0)
-    return TK.first_visible_queries(g["points"].astype(np.float32), g["occluded"], H, W)
-
-
 def _fit(frames, segment, fused=True, cfg=FIT, seed=0, q=None):
     from gflow_amd.fit_video import fit_clip
     keep = {"record_seg_inputs": True}
@@ -149,8 +135,8 @@ def _fit(frames, segment, fused=True, cfg=FIT, seed=0, q=None):
 
 @pytest.fixture(scope="module")
 def seg_fit():
-    frames = _clip()
-    q = _queries()
+    frames = clip()
+    _, q = queries()
     out, keep = _fit(frames, True, cfg=dict(FIT, traj_num=50), q=q)
     return frames, q, out, keep
 
@@ -223,14 +209,14 @@ def test_segment_changes_nothing_else(seg_fit):
 
 
 def test_operator_path_gives_the_same_contract():
-    frames = _clip(n_frames=4)
+    frames = clip(n_frames=4)
     out, keep = _fit(frames, True, fused=False)
     _check_contract(frames, out, keep)
 
 
 def test_concurrent_clips_take_segment():
     from gflow_amd.fit_video import fit_clips_concurrent
-    clips = [_clip(seed=0, n_frames=3), _clip(seed=1, n_frames=3)]
+    clips = [clip(seed=0, n_frames=3), clip(seed=1, n_frames=3)]
     res = fit_clips_concurrent(clips, DEV, FIT, seeds=[0, 1], deterministic=True, segment=True)
     for ci, r in enumerate(res):
         lone, _ = _fit(clips[ci], True, seed=ci)

@@ -13,13 +13,11 @@ import pytest
 import torch
 
 from tests import tracking_ref as R
+from tests.score_fit import FIT, H, T, W, clip, queries
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIT = dict(num_points=1500, iterations_first=60, iterations_after=40, iterations_camera=20, densify_interval=30,
-           densify_times=1, densify_interval_after=20, densify_times_after=1, lambda_depth=1e-2)
-H, W, T = 96, 128, 8
 
 
 def _anchor(uv, xy, stride=None):
@@ -150,19 +148,6 @@ def test_frame_kernel_matches_restatement():
     np.testing.assert_array_equal(tr[8, frame], np.float32(shift[8]))          # the culled row at (0, 0)
 
 
-def _queries(n_frames=T, n=96, seed=0):
-    from gflow_amd import synthetic as S
-    from gflow_amd import tracking as TK
-    g = S.make_clip_tracks(n_frames, H, W, seed=seed, n_queries=n, query_seed=0)
-    q = TK.first_visible_queries(g["points"].astype(np.float32), g["occluded"], H, W)
-    return g, q
-
-
-def _clip(seed=0, n_frames=T):
-    from gflow_amd import synthetic as S
-    return S.make_clip(n_frames, H, W, seed=seed)
-
-
 def _fit(frames, q, fused=True, deterministic=True, cfg=FIT, seed=0):
     from gflow_amd.fit_video import fit_clip
     keep = {"record_track_inputs": True}
@@ -173,8 +158,8 @@ def _fit(frames, q, fused=True, deterministic=True, cfg=FIT, seed=0):
 
 @pytest.fixture(scope="module")
 def det_fit():
-    frames = _clip()
-    g, q = _queries()
+    frames = clip()
+    g, q = queries(n=96)
     out, keep = _fit(frames, q)
     return frames, g, q, out, keep
 
@@ -202,8 +187,8 @@ def test_fit_tracks_equal_the_restatement(det_fit):
 
 
 def test_fit_tracks_equal_the_restatement_operator_path():
-    frames = _clip()
-    g, q = _queries()
+    frames = clip()
+    g, q = queries(n=96)
     out, keep = _fit(frames, q, fused=False)
     _check_against_restatement(q, out, keep)
 
@@ -214,8 +199,8 @@ def test_deterministic_fits_give_identical_tracks(det_fit):
     again, _ = _fit(frames, q)
     for k in ("tracks", "occluded", "anchor", "shift"):
         np.testing.assert_array_equal(again["tracks"][k], out["tracks"][k])
-    other = _clip(seed=1)
-    _, q1 = _queries(seed=1)
+    other = clip(seed=1)
+    _, q1 = queries(n=96, seed=1)
     lone1, _ = _fit(other, q1, seed=1)
     res = fit_clips_concurrent([frames, other], DEV, FIT, seeds=[0, 1], deterministic=True, track_queries=[q, q1])
     for r, want in zip(res, (out, lone1)):
@@ -225,8 +210,8 @@ def test_deterministic_fits_give_identical_tracks(det_fit):
 
 def test_queries_leave_trajectories_unchanged():
     from gflow_amd.fit_video import fit_clip
-    frames = _clip(n_frames=4)
-    _, q = _queries(n_frames=4)
+    frames = clip(n_frames=4)
+    _, q = queries(n_frames=4, n=96)
     cfg = dict(FIT, traj_num=50)
     a = fit_clip(frames, DEV, cfg, seed=0, deterministic=True)
     b = fit_clip(frames, DEV, cfg, seed=0, deterministic=True, track_queries=q)
@@ -264,9 +249,9 @@ def test_cli_tapvid_block_equals_in_process_evaluate(tmp_path):
     from gflow_amd import tracking as TK
     from gflow_amd.fit_video import fit_clip
     n = 5                                              # (the sequence convention fits n - 1 frames)
-    frames = _clip(n_frames=n)
+    frames = clip(n_frames=n)
     seq = gio.write_sequence(frames, str(tmp_path / "clip"))
-    g, _ = _queries(n_frames=n)
+    g, _ = queries(n_frames=n, n=96)
     pts, occ = g["points"].astype(np.float32), g["occluded"]
     TK.write_tapvid_pickle(os.path.join(seq, "tracking.pkl"), pts, occ)
     args = ["--sequence", seq, "--track", "--deterministic", "--num_points", "1500", "--iterations_first", "60",

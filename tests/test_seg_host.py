@@ -1,12 +1,16 @@
 """CPU: the numpy restatement of the DAVIS counts and scores (tests/seg_ref.py) and segmentation.scores_from_counts against
 J and F captured from the reference (tests/golden/davis_seg.npz, make_seg_golden.py); bound_pix; the recorder's carry-over
-and invalid-frame rules on hand-made inputs, with the device scoring replaced by the restatement."""
+and invalid-frame rules on hand-made inputs, with the device scoring replaced by the restatement; fit_video.reduce_davis
+on hand-written clip scores, alone and over a 2-rank gloo group."""
+import math
+import multiprocessing as mp
 import os
 
 import numpy as np
 import pytest
 import torch
 
+from gflow_amd import fit_video as FV
 from gflow_amd import segmentation as SG
 from tests import seg_ref as R
 
@@ -149,3 +153,49 @@ def test_recorder_marks_leading_frames_without_a_mask_invalid(monkeypatch):
     assert not empty["valid"].any() and SG.evaluate(empty)["frames_scored"] == 0 and np.isnan(SG.evaluate(empty)["J"])
     with pytest.raises(ValueError):
         rec.result(gts[:2])
+
+
+def _seg(J, F, valid=None):
+    J, F = np.asarray(J, np.float64), np.asarray(F, np.float64)
+    return dict(J=J, F=F, JF=(J + F) / 2, valid=np.ones(len(J), bool) if valid is None else np.asarray(valid, bool))
+
+
+# clip 0: J 0.625, F 0.375, J&F 0.5 over 2 frames; clip 2: no scored frame; clip 5: J 0.1875, F 0.5625, J&F 0.375 over 2
+SEGS = {0: _seg([0.5, 0.75], [0.25, 0.5]), 2: _seg([0.0, 0.0], [0.0, 0.0], valid=[False, False]),
+        5: _seg([0.875, 0.25, 0.125], [0.875, 0.75, 0.375], valid=[False, True, True])}
+DAVIS = {"J": (0.625 + 0.1875) / 2, "F": (0.375 + 0.5625) / 2, "J&F": (0.5 + 0.375) / 2, "frames_scored": 4, "clips": 2}
+
+
+def test_reduce_davis_averages_over_the_clips_with_a_scored_frame():
+    out = FV.reduce_davis(SEGS)
+    assert out == DAVIS and list(out) == ["J", "F", "J&F", "frames_scored", "clips"]
+    assert type(out["frames_scored"]) is int and type(out["clips"]) is int and type(out["J"]) is float
+    assert FV.reduce_davis({0: SEGS[0]}) == {"J": 0.625, "F": 0.375, "J&F": 0.5, "frames_scored": 2, "clips": 1}
+    for none in (FV.reduce_davis({}), FV.reduce_davis({2: SEGS[2]})):          # nothing to average: NaN, zero totals
+        assert none["frames_scored"] == 0 and none["clips"] == 0
+        assert all(type(none[k]) is float and math.isnan(none[k]) for k in ("J", "F", "J&F"))
+
+
+def _davis_worker(rank, world, port, q):
+    import torch.distributed as dist
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    dist.init_process_group(backend="gloo", rank=rank, world_size=world)
+    segs = {0: SEGS[0], 5: SEGS[5]} if rank == 0 else {2: SEGS[2]}             # rank 1 holds no scored clip
+    out = FV.reduce_davis(segs, dist, torch.device("cpu"))
+    dist.destroy_process_group()
+    q.put((rank, out))
+
+
+def test_reduce_davis_over_two_rank_gloo():
+    """the mean over the clips of all ranks (rank 1's own mean does not exist), the same dict on every rank"""
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = 33500 + (os.getpid() % 2000)
+    procs = [ctx.Process(target=_davis_worker, args=(r, 2, port, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    outs = dict(q.get(timeout=120) for _ in procs)
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    assert outs[0] == outs[1] == DAVIS == FV.reduce_davis(SEGS)

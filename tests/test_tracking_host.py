@@ -1,12 +1,14 @@
 """CPU: the TAP-Vid metric, the query extraction and the nearest-centre restatement against fixtures captured from the
 reference (tests/golden/tapvid.npz, make_tapvid_golden.py); the frame-loop restatement on a hand-worked case; the
-synthetic ground truth; query validation; the tracking.pkl round trip."""
+synthetic ground truth; query validation; the tracking.pkl round trip; fit_video.reduce_tapvid over clips."""
+import math
 import os
 
 import numpy as np
 import pytest
 import torch
 
+from gflow_amd import fit_video as FV
 from gflow_amd import synthetic as S
 from gflow_amd import tracking as TK
 from tests import tracking_ref as R
@@ -166,3 +168,31 @@ def test_evaluate_perfect_prediction_scores_one():
     m = TK.evaluate(pred, g["points"].astype(np.float32), g["occluded"], 96, 128, T)
     assert m["occlusion_accuracy"] == 1.0
     assert m["average_pts_within_thresh"] == 1.0 and m["average_jaccard"] == 1.0
+
+
+def test_reduce_tapvid_averages_over_clips():
+    H, W, n = 96, 128, 5
+    preds, gts, scores = {}, {}, {}
+    # clip 0: the ground truth itself; clip 3: 3 px off, every fourth flag flipped; clip 4: 20 px off, never occluded
+    for ci, (off, flip) in {0: (0.0, 0), 3: (3.0, 4), 4: (20.0, 0)}.items():
+        g = S.make_clip_tracks(n + 1, H, W, seed=ci, n_queries=40, query_seed=0)
+        pts, occ = g["points"].astype(np.float32), g["occluded"]
+        occluded = occ[:, :n].copy()
+        if flip:
+            occluded.reshape(-1)[::flip] ^= True
+        preds[ci] = dict(tracks=(g["points"][:, :n] * [W, H] + off).astype(np.float32),
+                         occluded=occluded if ci != 4 else np.zeros_like(occluded))
+        gts[ci] = (pts, occ, H, W)
+        scores[ci] = TK.evaluate(preds[ci], pts, occ, H, W, n)
+    frames = {ci: n for ci in preds}
+    out = FV.reduce_tapvid(preds, gts, frames, 7)
+    assert list(out) == list(FV.TAPVID_KEYS) + ["clips", "queries_dropped"]
+    assert out["clips"] == 3 and out["queries_dropped"] == 7 and type(out["clips"]) is int and type(out["queries_dropped"]) is int
+    for k in FV.TAPVID_KEYS:
+        assert out[k] == (scores[0][k] + scores[3][k] + scores[4][k]) / 3, k
+        assert scores[0][k] == 1.0 and scores[3][k] < 1.0 and scores[4][k] != scores[3][k]
+    one = FV.reduce_tapvid({3: preds[3]}, gts, frames, 0)
+    assert {k: one[k] for k in FV.TAPVID_KEYS} == {k: scores[3][k] for k in FV.TAPVID_KEYS} and one["clips"] == 1
+    none = FV.reduce_tapvid({}, {}, {}, 2)                                     # no clip: NaN, the dropped queries still counted
+    assert none["clips"] == 0 and none["queries_dropped"] == 2
+    assert all(type(none[k]) is float and math.isnan(none[k]) for k in FV.TAPVID_KEYS)
