@@ -151,20 +151,25 @@ using namespace gfl;
 
 extern "C" {
 
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// The operator binning workspace, described once: carved over `base`, only measured without one (Arena, gfl_common.hpp).
+struct BinWs { int32_t* cursor; unsigned long long* keys; char* tail; size_t bytes; };
+static BinWs bin_ws(void* base, int K_cap, int W, int H) {
+    Arena a{(char*)base};
+    // (tail: nobody's 256 bytes, part of the size this query has always answered)
+    return {a.take<int32_t>("cursor", tile_grid(W, H).tiles()), a.take<unsigned long long>("keys", (size_t)K_cap),
+            a.take<char>("tail", 256), a.off};
+}
 
 size_t gfl_bin_workspace_bytes(int N, int K_cap, int W, int H) {
     (void)N;
-    if (W <= 0 || H <= 0 || K_cap < 0) return 0;
-    const size_t T = (size_t)((W + GFL_TILE - 1) / GFL_TILE) * ((H + GFL_TILE - 1) / GFL_TILE);
-    return align_up(T * sizeof(int32_t), 256) + align_up((size_t)K_cap * sizeof(unsigned long long), 256) + 256;
+    return (W <= 0 || H <= 0 || K_cap < 0) ? 0 : bin_ws(nullptr, K_cap, W, H).bytes;
 }
 
 int gfl_bin_count(const float* uv, const int32_t* radius, const float* cutoff, int N, int W, int H,
                   int32_t* tile_offsets, gfl_stream_t stream) {
     if (N < 0 || W <= 0 || H <= 0 || !tile_offsets) return GFL_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    const int gx = (W + GFL_TILE - 1) / GFL_TILE, gy = (H + GFL_TILE - 1) / GFL_TILE, T = gx * gy;
+    const auto [gx, gy, T] = tile_grid(W, H);
     int rc = check(hipMemsetAsync(tile_offsets, 0, (size_t)(T + 1) * sizeof(int32_t), s));
     if (rc) return rc;
     if (N > 0) {
@@ -183,11 +188,9 @@ int gfl_bin_sort(const float* uv, const float* depth, const int32_t* radius, con
         return GFL_ERR_INVALID;
     if (workspace_bytes < gfl_bin_workspace_bytes(N, K_cap, W, H)) return GFL_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    const int gx = (W + GFL_TILE - 1) / GFL_TILE, gy = (H + GFL_TILE - 1) / GFL_TILE, T = gx * gy;
-    int32_t* cursor = (int32_t*)workspace;
-    unsigned long long* keys =
-        (unsigned long long*)((char*)workspace + align_up((size_t)T * sizeof(int32_t), 256));
-    int rc = check(hipMemsetAsync(cursor, 0, (size_t)T * sizeof(int32_t), s));
+    const auto [gx, gy, T] = tile_grid(W, H);
+    const BinWs ws = bin_ws(workspace, K_cap, W, H);
+    int rc = check(hipMemsetAsync(ws.cursor, 0, (size_t)T * sizeof(int32_t), s));
     if (rc) return rc;
     rc = check(hipMemsetAsync(overflow, 0, sizeof(int32_t), s));
     if (rc) return rc;
@@ -195,12 +198,12 @@ int gfl_bin_sort(const float* uv, const float* depth, const int32_t* radius, con
         if (!uv || !depth || !radius || (K_cap > 0 && !ids)) return GFL_ERR_INVALID;
         if (cutoff)
             bin_scatter_kernel<true><<<(N + 255) / 256, 256, 0, s>>>(uv, depth, radius, cutoff, N, gx, gy, tile_offsets,
-                                                                     cursor, K_cap, keys, overflow);
+                                                                     ws.cursor, K_cap, ws.keys, overflow);
         else
             bin_scatter_kernel<false><<<(N + 255) / 256, 256, 0, s>>>(uv, depth, radius, cutoff, N, gx, gy, tile_offsets,
-                                                                      cursor, K_cap, keys, overflow);
+                                                                      ws.cursor, K_cap, ws.keys, overflow);
     }
-    bin_tile_sort_kernel<<<T, SORT_THREADS, 0, s>>>(tile_offsets, K_cap, keys, ids, tile_range, gx, gy, nullptr, nullptr, nullptr, nullptr);
+    bin_tile_sort_kernel<<<T, SORT_THREADS, 0, s>>>(tile_offsets, K_cap, ws.keys, ids, tile_range, gx, gy, nullptr, nullptr, nullptr, nullptr);
     return check_launch();
 }
 
@@ -216,8 +219,8 @@ int gfl_tile_sort_only(const int32_t* tile_offsets, int T, int K_cap, void* keys
 int gfl_tile_sort_ordered(const int32_t* order, int W, int H, int K_cap, void* keys, int32_t* ids, int32_t* tile_range,
                           gfl_stream_t stream) {
     if (W <= 0 || H <= 0 || K_cap < 0 || !order || !keys || !tile_range || (K_cap > 0 && !ids)) return GFL_ERR_INVALID;
-    const int gx = (W + GFL_TILE - 1) / GFL_TILE, gy = (H + GFL_TILE - 1) / GFL_TILE;
-    bin_tile_sort_kernel<<<SORT_MAX_SPLIT + gx * gy, SORT_THREADS, 0, (hipStream_t)stream>>>(
+    const auto [gx, gy, T] = tile_grid(W, H);
+    bin_tile_sort_kernel<<<SORT_MAX_SPLIT + T, SORT_THREADS, 0, (hipStream_t)stream>>>(
         nullptr, K_cap, (unsigned long long*)keys, ids, tile_range, gx, gy,
         reinterpret_cast<const int4*>(order), nullptr, nullptr, nullptr);
     return check_launch();
@@ -227,8 +230,8 @@ int gfl_tile_sort_reserved(const int32_t* order, const int32_t* fill, int32_t* t
                            int K_cap, void* keys, int32_t* ids, int32_t* tile_range, gfl_stream_t stream) {
     if (W <= 0 || H <= 0 || K_cap < 0 || !order || !fill || !tile_counts || !keys || !tile_range || (K_cap > 0 && !ids))
         return GFL_ERR_INVALID;
-    const int gx = (W + GFL_TILE - 1) / GFL_TILE, gy = (H + GFL_TILE - 1) / GFL_TILE;
-    bin_tile_sort_kernel<<<SORT_MAX_SPLIT + gx * gy, SORT_THREADS, 0, (hipStream_t)stream>>>(
+    const auto [gx, gy, T] = tile_grid(W, H);
+    bin_tile_sort_kernel<<<SORT_MAX_SPLIT + T, SORT_THREADS, 0, (hipStream_t)stream>>>(
         nullptr, K_cap, (unsigned long long*)keys, ids, tile_range, gx, gy,
         reinterpret_cast<const int4*>(order), fill, tile_counts, void_words);
     return check_launch();

@@ -214,8 +214,8 @@ template <int C>
 static int launch_fwd(const float* uv, const float* conic, const float* opacity, const float* feature, int C_total,
                       int c0, const int32_t* ids, const int32_t* tile_range, float bg, int W, int H, float* out,
                       float* final_T, int32_t* n_contrib, hipStream_t s) {
-    const int gx = (W + GFL_TILE - 1) / GFL_TILE, gy = (H + GFL_TILE - 1) / GFL_TILE;
-    blend_fwd_kernel<C><<<gx * gy, 256, 0, s>>>(uv, conic, opacity, feature, C_total, c0, ids, tile_range, bg, W, H, gx,
+    const auto [gx, gy, T] = tile_grid(W, H);
+    blend_fwd_kernel<C><<<T, 256, 0, s>>>(uv, conic, opacity, feature, C_total, c0, ids, tile_range, bg, W, H, gx,
                                                 out, final_T, n_contrib);
     return check_launch();
 }
@@ -225,8 +225,8 @@ static int launch_bwd(const float* uv, const float* conic, const float* opacity,
                       int c0, const int32_t* ids, const int32_t* tile_range, float bg, int W, int H,
                       const float* final_T, const int32_t* n_contrib, const float* d_out, float* d_uv, float* d_conic,
                       float* d_opacity, float* d_feature, hipStream_t s) {
-    const int gx = (W + GFL_TILE - 1) / GFL_TILE, gy = (H + GFL_TILE - 1) / GFL_TILE;
-    blend_bwd_kernel<C><<<gx * gy, 256, 0, s>>>(uv, conic, opacity, feature, C_total, c0, ids, tile_range, bg, W, H, gx,
+    const auto [gx, gy, T] = tile_grid(W, H);
+    blend_bwd_kernel<C><<<T, 256, 0, s>>>(uv, conic, opacity, feature, C_total, c0, ids, tile_range, bg, W, H, gx,
                                                 final_T, n_contrib, d_out, d_uv, d_conic, d_opacity, d_feature);
     return check_launch();
 }

@@ -320,4 +320,34 @@ __global__ void __launch_bounds__(256) fold_partials_split_kernel(const float* _
 constexpr int REDUCE_BLOCK = 256;
 inline int reduce_rows(int N) { return (N + REDUCE_BLOCK - 1) / REDUCE_BLOCK; }
 
+// ---- host side: the tile grid of an image, and workspaces described once
+struct TileGrid {
+    int gx, gy, T;
+    size_t tiles() const { return (size_t)gx * gy; }      // (for sizes: no 32-bit product)
+};
+inline TileGrid tile_grid(int W, int H) {
+    const int gx = (W + GFL_TILE - 1) / GFL_TILE, gy = (H + GFL_TILE - 1) / GFL_TILE;
+    return {gx, gy, (int)((size_t)gx * gy)};
+}
+
+inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
+
+// A workspace is ONE walk that take()s its regions in address order: over a base pointer the walk carves, without one it
+// only counts (`off` ends as the size to ask for), and with a table it also lists the regions (gfl_fit_workspace_layout).
+// Every region starts on a 256-byte boundary.  Nothing is allocated; the names are literals.
+struct Arena {
+    char* base = nullptr;
+    size_t off = 0;
+    const char** names = nullptr; size_t* offsets = nullptr; size_t* bytes = nullptr;      // rows [0, max) are written,
+    int max = 0, n = 0;                                                                    // n counts every region
+    template <typename T>
+    T* take(const char* name, size_t count) {
+        if (n < max) { names[n] = name; offsets[n] = off; bytes[n] = count * sizeof(T); }
+        ++n;
+        T* p = base ? (T*)(base + off) : nullptr;
+        off += up256(count * sizeof(T));
+        return p;
+    }
+};
+
 }  // namespace gfl

@@ -1,6 +1,7 @@
 // Fused fit iteration, host side: the C entry points of include/gflow_hip.h for the iteration level (gfl_fit_*), the fused
-// differentiable operator (gfl_render_*) and the snapshot (gfl_fit_snapshot*) -- workspace carving, argument checks, the order
-// of the launches.  The kernels live in the stage files (gfl_fit_bin / _fwd / _bwd / _splat .hip) and are reached through
+// differentiable operator (gfl_render_*) and the snapshot (gfl_fit_snapshot*) -- the workspaces' layouts (fit_regions,
+// snap_ws: one walk each behind the size query, the carve and gfl_fit_workspace_layout), argument checks, the order of
+// the launches.  The kernels live in the stage files (gfl_fit_bin / _fwd / _bwd / _splat .hip) and are reached through
 // the launchers declared in gfl_fit.hpp; tile sort and loss kernels through their own C entry points (gfl_bin.hip,
 // gfl_ssim.hip).  Environment switches read here, once per process -- ALL the library has: GFL_EWA_MFMA, GFL_RESERVED,
 // GFL_FWD_SPLIT_MIN (include/gflow_hip.h).
@@ -10,21 +11,16 @@ using namespace gfl;
 
 extern "C" {
 
-static inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
 // other translation units
 size_t gfl_loss_workspace_bytes(int W, int H);
 
 static inline int fit_nblk(int N) { return (N + BIN_BLOCK - 1) / BIN_BLOCK; }
 
+// The environment switches: each read once per process (a function-local static: initialised once, thread-safe).
 // GFL_EWA_MFMA=1: the measured alternative for the J Sigma J^T contraction (fused_preprocess_fwd_kernel<true>)
 static bool ewa_on_mfma() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("GFL_EWA_MFMA");
-        v = (e && e[0] == '1') ? 1 : 0;
-    }
-    return v == 1;
+    static const bool on = [] { const char* e = getenv("GFL_EWA_MFMA"); return e && e[0] == '1'; }();
+    return on;
 }
 
 int gfl_ewa_on_mfma(void) { return ewa_on_mfma() ? 1 : 0; }
@@ -32,23 +28,24 @@ int gfl_ewa_on_mfma(void) { return ewa_on_mfma() ? 1 : 0; }
 // list length from which the forward blend walks a queue's first tile as four blocks (GFL_FWD_SPLIT_MIN overrides; scheduling
 // only: results do not depend on it)
 static int fwd_split_min() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("GFL_FWD_SPLIT_MIN");
-        v = e ? atoi(e) : FWD_SPLIT_MIN;
-    }
+    static const int v = [] { const char* e = getenv("GFL_FWD_SPLIT_MIN"); return e ? atoi(e) : FWD_SPLIT_MIN; }();
     return v;
+}
+
+// GFL_RESERVED=0 switches the reserved tile regions off (every iteration takes the exact binning path).
+static bool reserved_enabled() {
+    static const bool on = [] { const char* e = getenv("GFL_RESERVED"); return !(e && e[0] == '0'); }();
+    return on;
 }
 
 // one tile queue per CU (the dispatcher places workgroup b on CU b % CUs, tools/placement_probe.hip)
 static int device_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            cus = 256;
-    }
+    static const int cus = [] {
+        int dev = 0, n = 0;
+        const bool ok = hipGetDevice(&dev) == hipSuccess &&
+                        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0;
+        return ok ? n : 256;
+    }();
     return cus;
 }
 // (st->cu_count: the share of the device this state's stream may use -- a CU-masked stream, gfl_fit_state; a multiple of 8,
@@ -69,98 +66,103 @@ static int blend_grid(const gfl_fit_state* st, int T, int max_per_cu = BLEND_WG_
     return nq * per;
 }
 
+// The device-side counters of a fit: one 256-byte block of the workspace, zeroed with it.  The kernels get the members'
+// addresses one by one (FitWs); the words between them are padding that keeps counters of different launches apart.
+struct FitCounters {
+    int32_t pool_counter;   int32_t pad0[15];
+    int32_t sched_valid;    int32_t pad1[15];
+    int32_t regions_valid;  int32_t pad2[7];
+    int32_t extent;         int32_t pad3[7];
+    int32_t extent_next;    int32_t pad4[7];
+    int32_t stamp;          int32_t pad5;
+    int32_t snap_mm[2];     int32_t pad6[4];
+};
+static_assert(sizeof(FitCounters) == 256, "the counter block is one 256-byte region");
+static_assert(offsetof(FitCounters, pool_counter) == 0 * 4 && offsetof(FitCounters, sched_valid) == 16 * 4 &&
+              offsetof(FitCounters, regions_valid) == 32 * 4 && offsetof(FitCounters, extent) == 40 * 4 &&
+              offsetof(FitCounters, extent_next) == 48 * 4 && offsetof(FitCounters, stamp) == 56 * 4 &&
+              offsetof(FitCounters, snap_mm) == 58 * 4, "word offsets of the counters");
 
-size_t gfl_fit_workspace_bytes(int cap, int K_cap, int W, int H) {
-    if (cap < 0 || K_cap < 0 || W <= 0 || H <= 0) return 0;
-    const size_t T = (size_t)((W + GFL_TILE - 1) / GFL_TILE) * ((H + GFL_TILE - 1) / GFL_TILE);
-    return up256((size_t)fit_nblk(cap > 0 ? cap : 1) * T * sizeof(int32_t))      // hist / bases
-           + up256((size_t)K_cap * sizeof(unsigned long long))                      // keys
-           + up256((size_t)reduce_rows(cap > 0 ? cap : 1) * 12 * sizeof(float))    // extr partials
-           + up256(T * sizeof(int32_t))                                             // tile totals
-           + up256(((size_t)(cap > 0 ? cap : 1) * SLOT_MAX + (size_t)K_cap) * PG * sizeof(float))   // pair rows: SLOT_MAX per splat + the wide splats' runs
-           + up256((size_t)(cap > 0 ? cap : 1) * sizeof(int32_t))                   // a wide splat's run
-           + 256                                                                    // counters
-           + up256(4 * T * sizeof(int32_t))                                         // scheduler: work feedback per 8x8 block
-           + up256((size_t)SCHED_MAX_QUEUES * sched_queue_capacity((int)T, 64) * sizeof(int32_t))   // queue items
-           + 2 * up256(2 * SCHED_MAX_QUEUES * sizeof(int32_t))                      // queue lengths, pull counters
-           + up256((size_t)SCHED_MAX_QUEUES * (HEAVY_PARTS - 1) * 5 * 256 * sizeof(float))                  // heavy-tile checkpoints
-           + up256(4 * T * sizeof(int32_t)) + up256(T * sizeof(int32_t))            // forward schedule: work feedback; first_slot
-           + up256((size_t)SCHED_MAX_QUEUES * sched_queue_capacity((int)T, 64) * sizeof(int32_t))   // ... queue items
-           + up256(2 * SCHED_MAX_QUEUES * sizeof(int32_t))                          // ... queue lengths
-           + up256(gfl_loss_workspace_bytes(W, H)) + 256
-           + up256((size_t)6 * W * H * sizeof(float))                                  // SSIM statistics of the target
-           + up256((size_t)2 * fit_nblk(cap > 0 ? cap : 1) * sizeof(int32_t))          // rows of the scale term per 256 splats
-           + up256((T * 4 + SORT_ORDER_TRAILER) * sizeof(int32_t))                     // the tile sort's order (+ its split list)
-           + up256((T * 4 + SORT_ORDER_TRAILER) * sizeof(int32_t))                     // reserved tile regions: the next sort order,
-           + up256(T * sizeof(int4)) + up256(T * sizeof(int32_t))                       //   {start, capacity, position} per tile, fill counters
-           + up256((size_t)reduce_rows(cap > 0 ? cap : 1) * 4 * sizeof(float))         // gfl_render_bwd_cam: intr partials,
-           + up256((size_t)(cap > 0 ? cap : 1) * REC * sizeof(float));                  //   the rows its two launches hand over
+// THE description of the fit workspace: its regions in address order, each declared here and nowhere else.  The size query
+// walks it without a base, carve() over st->workspace, gfl_fit_workspace_layout with a table.  A new buffer is one line.
+// Returns the items each of the two queue lists holds.
+static size_t fit_regions(Arena& a, int cap_arg, int K_cap, int W, int H, FitWs& w) {
+    const size_t T = tile_grid(W, H).tiles();
+    const int cap = cap_arg > 0 ? cap_arg : 1;
+    const size_t queue_items = (size_t)SCHED_MAX_QUEUES * sched_queue_capacity((int)T, 64);
+    const size_t order_words = T * 4 + SORT_ORDER_TRAILER;                                   // order[T][4] + its split list
+    w.hist = a.take<int32_t>("hist", (size_t)fit_nblk(cap) * T);                             // per-block tile histogram / bases
+    w.keys = a.take<unsigned long long>("keys", (size_t)K_cap);
+    w.partial = a.take<float>("partial", (size_t)reduce_rows(cap) * 12);                     // extr partials
+    w.tile_counts = a.take<int32_t>("tile_counts", T);                                       // tile totals
+    w.pair_grad = a.take<float>("pair_grad", ((size_t)cap * SLOT_MAX + (size_t)K_cap) * PG); // pair rows: SLOT_MAX per splat + the wide splats' runs
+    w.wide_base = (long long)cap * SLOT_MAX;
+    w.wide_off = a.take<int32_t>("wide_off", (size_t)cap);                                   // a wide splat's run
+    if (FitCounters* c = a.take<FitCounters>("counters", 1)) {
+        w.pool_counter = &c->pool_counter; w.sched_valid = &c->sched_valid; w.regions_valid = &c->regions_valid;
+        w.extent = &c->extent; w.extent_next = &c->extent_next; w.stamp = &c->stamp; w.snap_mm = (unsigned*)c->snap_mm;
+    }
+    w.sched.work = a.take<int32_t>("sched_work", 4 * T);                                     // scheduler: work feedback per 8x8 block
+    w.sched.list = a.take<int32_t>("sched_list", queue_items);                               // queue items
+    w.sched.count = a.take<int32_t>("sched_count", 2 * SCHED_MAX_QUEUES);                    // queue lengths
+    w.sched.counters = a.take<int32_t>("sched_counters", 2 * SCHED_MAX_QUEUES);              // pull counters, forward then backward
+    w.ckpt = a.take<float>("ckpt", (size_t)SCHED_MAX_QUEUES * (HEAVY_PARTS - 1) * 5 * 256);  // heavy-tile checkpoints
+    w.sched_fwd.work = a.take<int32_t>("sched_fwd_work", 4 * T);                             // forward schedule: work feedback,
+    w.sched_fwd.list = a.take<int32_t>("sched_fwd_list", queue_items);                       //   queue items,
+    w.sched_fwd.count = a.take<int32_t>("sched_fwd_count", 2 * SCHED_MAX_QUEUES);            //   queue lengths
+    w.sched_fwd.counters = w.sched.counters;                                                 //   (one set of pull counters for both)
+    w.sched_fwd.first_slot = nullptr;
+    w.sched.first_slot = a.take<int32_t>("first_slot", T);                                   // the queue a tile is the first item of (backward)
+    w.loss_ws_bytes = up256(gfl_loss_workspace_bytes(W, H));
+    w.loss_ws = a.take<char>("loss_ws", w.loss_ws_bytes);
+    a.take<char>("loss_pad", 256);                                                           // nobody's: kept, every address behind depends on it
+    w.gt_stats = a.take<float>("gt_stats", (size_t)6 * W * H);                               // SSIM statistics of the target
+    w.scale_cnt = a.take<int32_t>("scale_cnt", (size_t)2 * fit_nblk(cap));                   // rows of the scale term per 256 splats
+    w.sort_order = (int4*)a.take<int32_t>("sort_order", order_words);                        // the tile sort's order
+    w.sort_order_next = (int4*)a.take<int32_t>("sort_order_next", order_words);              // reserved tile regions: the next sort order,
+    w.region = a.take<int4>("region", T);                                                    //   {start, capacity, position} per tile,
+    w.fill = a.take<int32_t>("fill", T);                                                     //   fill counters
+    w.partial_cam = a.take<float>("partial_cam", (size_t)reduce_rows(cap) * 4);              // gfl_render_bwd_cam: intr partials,
+    w.d_rec_cam = a.take<float>("d_rec_cam", (size_t)cap * REC);                             //   the rows its two launches hand over
+    return queue_items;
 }
 
+static int fit_layout(Arena& a, int cap, int K_cap, int W, int H) {          // the number of regions, < 0: invalid sizes
+    if (cap < 0 || K_cap < 0 || W <= 0 || H <= 0) return GFL_ERR_INVALID;
+    FitWs w;
+    fit_regions(a, cap, K_cap, W, H, w);
+    return a.n;
+}
+
+size_t gfl_fit_workspace_bytes(int cap, int K_cap, int W, int H) {
+    Arena a;
+    return fit_layout(a, cap, K_cap, W, H) < 0 ? 0 : a.off;
+}
+
+int gfl_fit_workspace_layout(int cap, int K_cap, int W, int H, const char** names, size_t* offsets, size_t* bytes, int max) {
+    if (max < 0 || (max > 0 && (!names || !offsets || !bytes))) return GFL_ERR_INVALID;
+    Arena a{nullptr, 0, names, offsets, bytes, max};
+    return fit_layout(a, cap, K_cap, W, H);
+}
+
+static bool fit_ws_fits(const gfl_fit_state* st) {
+    return st->workspace_bytes >= gfl_fit_workspace_bytes(st->cap, st->K_cap, st->W, st->H);
+}
 
 static FitWs carve(const gfl_fit_state* st) {
-    const size_t T = (size_t)((st->W + GFL_TILE - 1) / GFL_TILE) * ((st->H + GFL_TILE - 1) / GFL_TILE);
-    char* p = (char*)st->workspace;
+    Arena a{(char*)st->workspace};
     FitWs w;
-    w.hist = (int32_t*)p;
-    p += up256((size_t)fit_nblk(st->cap > 0 ? st->cap : 1) * T * sizeof(int32_t));
-    w.keys = (unsigned long long*)p;
-    p += up256((size_t)st->K_cap * sizeof(unsigned long long));
-    w.partial = (float*)p;
-    p += up256((size_t)reduce_rows(st->cap > 0 ? st->cap : 1) * 12 * sizeof(float));
-    w.tile_counts = (int32_t*)p;
-    p += up256(T * sizeof(int32_t));
-    w.pair_grad = (float*)p;
-    w.wide_base = (long long)(st->cap > 0 ? st->cap : 1) * SLOT_MAX;
-    p += up256(((size_t)(st->cap > 0 ? st->cap : 1) * SLOT_MAX + (size_t)st->K_cap) * PG * sizeof(float));
-    w.wide_off = (int32_t*)p;
-    p += up256((size_t)(st->cap > 0 ? st->cap : 1) * sizeof(int32_t));
-    w.pool_counter = (int32_t*)p;
-    w.stamp = w.pool_counter + 56;
-    w.snap_mm = (unsigned*)(w.pool_counter + 58);
-    w.sched_valid = w.pool_counter + 16;
-    w.regions_valid = w.pool_counter + 32;
-    w.extent = w.pool_counter + 40;
-    w.extent_next = w.pool_counter + 48;
-    p += 256;
-    w.sched.work = (int32_t*)p;
-    p += up256(4 * T * sizeof(int32_t));
-    w.sched.list = (int32_t*)p;
-    p += up256((size_t)SCHED_MAX_QUEUES * sched_queue_capacity((int)T, 64) * sizeof(int32_t));
-    w.sched.count = (int32_t*)p;
-    p += up256(2 * SCHED_MAX_QUEUES * sizeof(int32_t));
-    w.sched.counters = (int32_t*)p;
-    p += up256(2 * SCHED_MAX_QUEUES * sizeof(int32_t));
-    w.ckpt = (float*)p;
-    p += up256((size_t)SCHED_MAX_QUEUES * (HEAVY_PARTS - 1) * 5 * 256 * sizeof(float));
-    w.sched.nq = blend_queues(st);
-    // (the list is sized for 512 queues: with fewer queues each may hold more -- a band of the XCD-local schedule
-    //  can have many more tiles than T / 8)
-    w.sched.cap_q = (int)(((size_t)SCHED_MAX_QUEUES * sched_queue_capacity((int)T, 64)) / w.sched.nq);
+    const size_t queue_items = fit_regions(a, st->cap, st->K_cap, st->W, st->H, w);
+    for (Sched* s : {&w.sched, &w.sched_fwd}) {
+        s->nq = blend_queues(st);
+        // (the list is sized for 512 queues: with fewer queues each may hold more -- a band of the XCD-local schedule
+        //  can have many more tiles than T / 8)
+        s->cap_q = (int)(queue_items / s->nq);
+        s->xcd = 1;         // XCD-local bands + LPT in rounds wherever the grid allows it (sched_xcd_usable, next_sched_ok)
+        s->det = (st->flags & GFL_FIT_DETERMINISTIC) ? 1 : 0;     // ties of the tile order by tile index (gfl_sched.hpp)
+    }
     w.sched.split_min = 0;
-    w.sched.xcd = 1;         // XCD-local bands + LPT in rounds wherever the grid allows it (sched_xcd_usable, next_sched_ok)
-    w.sched.det = (st->flags & GFL_FIT_DETERMINISTIC) ? 1 : 0;     // ties of the tile order by tile index (gfl_sched.hpp)
-    w.sched_fwd = w.sched;
-    w.sched_fwd.work = (int32_t*)p;
-    p += up256(4 * T * sizeof(int32_t));
-    w.sched_fwd.list = (int32_t*)p;
-    p += up256((size_t)SCHED_MAX_QUEUES * sched_queue_capacity((int)T, 64) * sizeof(int32_t));
-    w.sched_fwd.count = (int32_t*)p;
-    p += up256(2 * SCHED_MAX_QUEUES * sizeof(int32_t));
-    w.sched.first_slot = (int32_t*)p;
-    p += up256(T * sizeof(int32_t));
-    w.sched_fwd.first_slot = nullptr;
     w.sched_fwd.split_min = fwd_split_min();
-    w.loss_ws = p;
-    w.loss_ws_bytes = up256(gfl_loss_workspace_bytes(st->W, st->H));
-    w.gt_stats = (float*)((char*)p + w.loss_ws_bytes + 256);
-    w.scale_cnt = (int32_t*)((char*)w.gt_stats + up256((size_t)6 * st->W * st->H * sizeof(float)));
-    w.sort_order = (int4*)((char*)w.scale_cnt + up256((size_t)2 * fit_nblk(st->cap > 0 ? st->cap : 1) * sizeof(int32_t)));
-    w.sort_order_next = (int4*)((char*)w.sort_order + up256((T * 4 + SORT_ORDER_TRAILER) * sizeof(int32_t)));
-    w.region = (int4*)((char*)w.sort_order_next + up256((T * 4 + SORT_ORDER_TRAILER) * sizeof(int32_t)));
-    w.fill = (int32_t*)((char*)w.region + up256(T * sizeof(int4)));
-    w.partial_cam = (float*)((char*)w.fill + up256(T * sizeof(int32_t)));
-    w.d_rec_cam = (float*)((char*)w.partial_cam + up256((size_t)reduce_rows(st->cap > 0 ? st->cap : 1) * 4 * sizeof(float)));
     return w;
 }
 
@@ -185,15 +187,6 @@ static NextSched next_sched(const FitWs& w, int rows, int T) {
     return ns;
 }
 
-// GFL_RESERVED=0 switches the reserved tile regions off (every iteration takes the exact binning path).
-static bool reserved_enabled() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("GFL_RESERVED");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v == 1;
-}
 // Reserved tile regions: grids of up to 4096 tiles (the region workgroup holds a tile's count in registers: 16 per lane on
 // REDUCE_BLOCK lanes; the binning kernel 8 per lane on BIN_BLOCK), the scheduling workgroups in the per-splat launch (the
 // region workgroup is the third of them).
@@ -220,7 +213,7 @@ static int fit_check(const gfl_fit_state* st, const gfl_fit_hyper* hp) {
     if (!st->params || !st->rec || !st->pose || !st->intr || !st->extr || !st->render || !st->final_T ||
         !st->n_contrib || !st->tile_offsets || !st->ids || !st->tile_range || !st->overflow || !st->workspace)
         return GFL_ERR_INVALID;
-    if (st->workspace_bytes < gfl_fit_workspace_bytes(st->cap, st->K_cap, st->W, st->H)) return GFL_ERR_WORKSPACE;
+    if (!fit_ws_fits(st)) return GFL_ERR_WORKSPACE;
     return GFL_OK;
 }
 
@@ -248,7 +241,7 @@ static int fit_forward_impl(const gfl_fit_state* st, const gfl_fit_hyper* hp, gf
     int rc = fit_check(st, hp);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const int gx = (st->W + GFL_TILE - 1) / GFL_TILE, gy = (st->H + GFL_TILE - 1) / GFL_TILE, T = gx * gy;
+    const auto [gx, gy, T] = tile_grid(st->W, st->H);
     const FitWs w = carve(st);
     const int nblk = fit_nblk(st->N > 0 ? st->N : 1);
     // tile grid too large for the LDS histogram: 64 KB less the scheduling workgroups' ~6 KB of static state (their block
@@ -339,10 +332,20 @@ int gfl_fit_forward(const gfl_fit_state* st, const gfl_fit_hyper* hp, gfl_stream
     return fit_forward_impl(st, hp, stream, 0);
 }
 
+// The snapshot workspace, described once (see fit_regions): carved over `base`, only measured without one.
+struct SnapWs { unsigned* mm; int32_t* pull; size_t head_bytes; float *img_dc, *img_c, *fT; int32_t* nc; size_t bytes; };
+static SnapWs snap_ws(void* base, int W, int H) {
+    Arena a{(char*)base};
+    const size_t P = (size_t)W * H;
+    // head of the workspace, cleared by ONE memset: the depth range's two words and a set of queue pull counters for each
+    // of the two composites (four memset launches of ~6 us each before: a snapshot every tenth iteration)
+    return {a.take<unsigned>("mm", 2), a.take<int32_t>("pull", 2 * SCHED_MAX_QUEUES), a.off,
+            a.take<float>("img_dc", 4 * P), a.take<float>("img_c", 4 * P), a.take<float>("final_T", P),
+            a.take<int32_t>("n_contrib", P), a.off};
+}
+
 size_t gfl_fit_snapshot_workspace_bytes(int N, int W, int H) {
-    if (N < 0 || W <= 0 || H <= 0) return 0;
-    return 256 + up256(2 * SCHED_MAX_QUEUES * sizeof(int32_t)) + 2 * up256((size_t)4 * W * H * sizeof(float)) +
-           up256((size_t)W * H * sizeof(float)) + up256((size_t)W * H * sizeof(int32_t));
+    return (N < 0 || W <= 0 || H <= 0) ? 0 : snap_ws(nullptr, W, H).bytes;
 }
 
 int gfl_fit_snapshot(const gfl_fit_state* st, const gfl_fit_hyper* hp, const float* lut, uint8_t* out_u8, void* workspace,
@@ -352,35 +355,25 @@ int gfl_fit_snapshot(const gfl_fit_state* st, const gfl_fit_hyper* hp, const flo
     if (!lut || !out_u8 || !workspace) return GFL_ERR_INVALID;
     if (workspace_bytes < gfl_fit_snapshot_workspace_bytes(st->N, st->W, st->H)) return GFL_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    const int gx = (st->W + GFL_TILE - 1) / GFL_TILE, gy = (st->H + GFL_TILE - 1) / GFL_TILE, T = gx * gy;
-    const int P = st->W * st->H;
+    const auto [gx, gy, T] = tile_grid(st->W, st->H);
     const FitWs w = carve(st);
-    char* p = (char*)workspace;
-    // head of the workspace, cleared by ONE memset: the depth range's two words and a set of queue pull counters for each
-    // of the two composites (four memset launches of ~6 us each before: a snapshot every tenth iteration)
-    unsigned* mm = (unsigned*)p;                 p += 256;
-    int32_t* pull = (int32_t*)p;                 p += up256(2 * SCHED_MAX_QUEUES * sizeof(int32_t));
-    const size_t head_bytes = (size_t)(p - (char*)workspace);
-    float* img_dc = (float*)p;                   p += up256((size_t)4 * P * sizeof(float));
-    float* img_c = (float*)p;                    p += up256((size_t)4 * P * sizeof(float));
-    float* fT = (float*)p;                       p += up256((size_t)P * sizeof(float));
-    int32_t* nc = (int32_t*)p;
-    rc = check(hipMemsetAsync(workspace, 0, head_bytes, s));
+    const SnapWs sw = snap_ws(workspace, st->W, st->H);
+    rc = check(hipMemsetAsync(workspace, 0, sw.head_bytes, s));
     if (rc) return rc;
-    if (st->N > 0) launch_rec_depth_range(st->rec, st->N, mm, s);
+    if (st->N > 0) launch_rec_depth_range(st->rec, st->N, sw.mm, s);
     // center first: a kernel of its own (gfl_fit_fwd.hip), short-lived workgroups.  On a side stream (trainer.py: _snapshot_async)
     // these launches run beside the NEXT iteration's binning and tile sort, and the persistent workgroups of the blend kernel
     // below hold every CU's registers for their ~50 us: the tile sort beside them took 44 us instead of 14
     // (tools/snapshot_gaps.py); behind this kernel they start when that iteration is past its sort.
-    launch_center_blend(st, hp->bg, gx, T, img_c, nullptr, s);
+    launch_center_blend(st, hp->bg, gx, T, sw.img_c, nullptr, s);
     {
         // depth_map_color: the blend kernel over the forward's queues (the iteration's own launch used up the engine's pull counters)
-        const TileQueue q = {w.sched_fwd.list, w.sched_fwd.count, pull, w.sched.nq, w.sched.cap_q};
+        const TileQueue q = {w.sched_fwd.list, w.sched_fwd.count, sw.pull, w.sched.nq, w.sched.cap_q};
         // (fewer workgroups per CU for this launch, so that it disturbs the fit's own kernels less, was measured in
         //  round 4: one per CU 0.871-0.886 s per 8-frame clip fit against 0.858-0.865 with five, three the same as five)
-        launch_blend_fwd(st, hp->bg, gx, blend_grid(st, T, FWD_WG_PER_CU), img_dc, fT, nc, q, w, 1, mm, lut, fwd_split_min(), s);
+        launch_blend_fwd(st, hp->bg, gx, blend_grid(st, T, FWD_WG_PER_CU), sw.img_dc, sw.fT, sw.nc, q, w, 1, sw.mm, lut, fwd_split_min(), s);
     }
-    launch_snapshot_u8(st->render, img_dc, img_c, P, out_u8, s);
+    launch_snapshot_u8(st->render, sw.img_dc, sw.img_c, st->W * st->H, out_u8, s);
     return check_launch();
 }
 
@@ -393,10 +386,8 @@ int gfl_fit_snapshot_stage(const gfl_fit_state* src, const gfl_fit_state* dst, g
         return GFL_ERR_INVALID;
     if (src->W != dst->W || src->H != dst->H || src->N != dst->N || dst->N > dst->cap || src->N > src->cap)
         return GFL_ERR_INVALID;
-    if (src->workspace_bytes < gfl_fit_workspace_bytes(src->cap, src->K_cap, src->W, src->H) ||
-        dst->workspace_bytes < gfl_fit_workspace_bytes(dst->cap, dst->K_cap, dst->W, dst->H))
-        return GFL_ERR_WORKSPACE;
-    const int gx = (src->W + GFL_TILE - 1) / GFL_TILE, gy = (src->H + GFL_TILE - 1) / GFL_TILE, T = gx * gy;
+    if (!fit_ws_fits(src) || !fit_ws_fits(dst)) return GFL_ERR_WORKSPACE;
+    const int T = tile_grid(src->W, src->H).T;
     const size_t P = (size_t)src->W * src->H;
     const FitWs a = carve(src), b = carve(dst);
     if (a.sched_fwd.nq != b.sched_fwd.nq || a.sched_fwd.cap_q != b.sched_fwd.cap_q) return GFL_ERR_INVALID;
@@ -424,7 +415,7 @@ int gfl_render_fwd(const gfl_fit_state* st, const gfl_fit_hyper* hp, gfl_stream_
         // dropped and this call schedules by its own list lengths (three small memsets).
         const int rc = fit_check(st, hp);
         if (rc) return rc;
-        const int T = ((st->W + GFL_TILE - 1) / GFL_TILE) * ((st->H + GFL_TILE - 1) / GFL_TILE);
+        const int T = tile_grid(st->W, st->H).T;
         const FitWs w = carve(st);
         hipStream_t s = (hipStream_t)stream;
         if (check(hipMemsetAsync(w.sched.work, 0, 4 * (size_t)T * sizeof(int32_t), s)) ||
@@ -439,7 +430,7 @@ int gfl_render_fwd(const gfl_fit_state* st, const gfl_fit_hyper* hp, gfl_stream_
 static int render_bwd_impl(const gfl_fit_state* st, const gfl_fit_hyper* hp, const float* d_render, const float* d_uv,
                            const float* d_depth, float* d_params, float* d_extr, float* d_intr, gfl_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
-    const int gx = (st->W + GFL_TILE - 1) / GFL_TILE, gy = (st->H + GFL_TILE - 1) / GFL_TILE, T = gx * gy;
+    const auto [gx, gy, T] = tile_grid(st->W, st->H);
     const FitWs w = carve(st);
     {
         StageScope p(ST_BLEND_BWD, s);
@@ -482,7 +473,7 @@ int gfl_fit_backward_step(const gfl_fit_state* st, const gfl_fit_hyper* hp, gfl_
         !st->depth_ab_v || !st->step || !st->gt_rgb || !st->d_render || !st->err_px || !st->sums || !st->d_extr)
         return GFL_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    const int gx = (st->W + GFL_TILE - 1) / GFL_TILE, gy = (st->H + GFL_TILE - 1) / GFL_TILE, T = gx * gy;
+    const auto [gx, gy, T] = tile_grid(st->W, st->H);
     const FitWs w = carve(st);
     const float *p_ssim = nullptr, *p_grad = nullptr;
     int n_ssim = 0, n_grad = 0;
@@ -543,7 +534,7 @@ int gfl_fit_iterations(const gfl_fit_state* st, const gfl_fit_hyper* hp, int cou
     if (count < 1 || (flags & ~GFL_ITER_RESERVED)) return GFL_ERR_INVALID;
     int rc = fit_check(st, hp);
     if (rc) return rc;
-    const int T = ((st->W + GFL_TILE - 1) / GFL_TILE) * ((st->H + GFL_TILE - 1) / GFL_TILE);
+    const int T = tile_grid(st->W, st->H).T;
     const FitWs w = carve(st);
     const bool res_ok = fit_reserved_ok(w, T) && st->N > 0;
     if ((flags & GFL_ITER_RESERVED) && !res_ok) return GFL_ERR_INVALID;
@@ -568,39 +559,38 @@ int gfl_fit_iteration_snapshot(const gfl_fit_state* st, const gfl_fit_hyper* hp,
 
 int gfl_fit_reserved_supported(const gfl_fit_state* st, const gfl_fit_hyper* hp) {
     if (fit_check(st, hp) || st->N <= 0) return 0;
-    const int T = ((st->W + GFL_TILE - 1) / GFL_TILE) * ((st->H + GFL_TILE - 1) / GFL_TILE);
+    const int T = tile_grid(st->W, st->H).T;
     return fit_reserved_ok(carve(st), T) ? 1 : 0;
 }
 
 int gfl_fit_prepare_targets(const gfl_fit_state* st, gfl_stream_t stream) {
     if (!st || st->W <= 0 || st->H <= 0 || !st->gt_rgb || !st->workspace) return GFL_ERR_INVALID;
-    if (st->workspace_bytes < gfl_fit_workspace_bytes(st->cap, st->K_cap, st->W, st->H)) return GFL_ERR_WORKSPACE;
+    if (!fit_ws_fits(st)) return GFL_ERR_WORKSPACE;
     const FitWs w = carve(st);
     return gfl_loss_prepare_gt(st->gt_rgb, st->keep, st->W, st->H, w.gt_stats, stream);
 }
 
+static int schedule_info(const gfl_fit_state* st, bool fwd, int* n_queues, int* queue_capacity, const int32_t** d_lists,
+                         const int32_t** d_counts) {
+    if (!st || !n_queues || !queue_capacity || !d_lists || !d_counts || !st->workspace) return GFL_ERR_INVALID;
+    if (!fit_ws_fits(st)) return GFL_ERR_WORKSPACE;
+    const FitWs w = carve(st);
+    const Sched& sc = fwd ? w.sched_fwd : w.sched;
+    *n_queues = sc.nq;
+    *queue_capacity = sc.cap_q;
+    *d_lists = sc.list;
+    *d_counts = sc.count;
+    return GFL_OK;
+}
+
 int gfl_fit_schedule_info(const gfl_fit_state* st, int* n_queues, int* queue_capacity, const int32_t** d_lists,
                           const int32_t** d_counts) {
-    if (!st || !n_queues || !queue_capacity || !d_lists || !d_counts || !st->workspace) return GFL_ERR_INVALID;
-    if (st->workspace_bytes < gfl_fit_workspace_bytes(st->cap, st->K_cap, st->W, st->H)) return GFL_ERR_WORKSPACE;
-    const FitWs w = carve(st);
-    *n_queues = w.sched.nq;
-    *queue_capacity = w.sched.cap_q;
-    *d_lists = w.sched.list;
-    *d_counts = w.sched.count;
-    return GFL_OK;
+    return schedule_info(st, false, n_queues, queue_capacity, d_lists, d_counts);
 }
 
 int gfl_fit_schedule_info_fwd(const gfl_fit_state* st, int* n_queues, int* queue_capacity, const int32_t** d_lists,
                               const int32_t** d_counts) {
-    if (!st || !n_queues || !queue_capacity || !d_lists || !d_counts || !st->workspace) return GFL_ERR_INVALID;
-    if (st->workspace_bytes < gfl_fit_workspace_bytes(st->cap, st->K_cap, st->W, st->H)) return GFL_ERR_WORKSPACE;
-    const FitWs w = carve(st);
-    *n_queues = w.sched_fwd.nq;
-    *queue_capacity = w.sched_fwd.cap_q;
-    *d_lists = w.sched_fwd.list;
-    *d_counts = w.sched_fwd.count;
-    return GFL_OK;
+    return schedule_info(st, true, n_queues, queue_capacity, d_lists, d_counts);
 }
 
 int gfl_fit_iteration(const gfl_fit_state* st, const gfl_fit_hyper* hp, gfl_stream_t stream) {

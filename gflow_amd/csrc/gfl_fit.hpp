@@ -326,12 +326,12 @@ struct NextSched {
     int n_pull;
 };
 
-// ------------------------------------------------- the carved workspace (gfl_fit.hip: carve)
+// ------------------------------------------------- the carved workspace (gfl_fit.hip: fit_regions declares the regions, carve fills this)
 struct FitWs {
     int32_t* hist;
     unsigned long long* keys;
     float* partial;
-    float* partial_cam;         // gfl_render_bwd_cam, the last two carves: partial rows of 4 (intr) and, when the state has no
+    float* partial_cam;         // gfl_render_bwd_cam, the last two regions: partial rows of 4 (intr) and, when the state has no
     float* d_rec_cam;           //   d_rec of its own, the rows [cap][12] the per-splat launch leaves for the intrinsics launch
     int32_t* tile_counts;
     float* pair_grad;

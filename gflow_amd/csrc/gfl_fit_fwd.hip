@@ -648,7 +648,7 @@ void launch_blend_fwd(const gfl_fit_state* st, float bg, int gx, int grid, float
                 (mode == 2 ? fused_blend_fwd_kernel<2> : fused_blend_fwd_kernel<3>));
     // mode 3: one more workgroup per tile behind the blend's own (footprint_tile)
     const FootArgs foot = {st->foot_flags, st->keep, grid};
-    const int T = gx * ((st->H + GFL_TILE - 1) / GFL_TILE);
+    const int T = tile_grid(st->W, st->H).T;
     kern<<<mode == 3 ? grid + T : grid, 256, 0, s>>>(st->rec, st->ids, st->tile_range, bg, st->W, st->H, gx, inv_of(gx), out, final_T,
                               n_contrib, q, w.ckpt, cmap_mm, cmap_lut, split_min, w.sched_fwd.work, w.sched.first_slot,
                               mode != 1 ? w.stamp : nullptr, snap_u8, foot);

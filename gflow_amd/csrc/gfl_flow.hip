@@ -162,8 +162,6 @@ __global__ void __launch_bounds__(256) flow_fold_kernel(const double* __restrict
     }
 }
 
-inline int flow_tiles(int W, int H) { return ((W + GFL_TILE - 1) / GFL_TILE) * ((H + GFL_TILE - 1) / GFL_TILE); }
-
 }  // namespace gfl
 
 using namespace gfl;
@@ -172,9 +170,9 @@ extern "C" {
 
 size_t gfl_flow_workspace_bytes(int W, int H) {
     if (W < 1 || H < 1) return 0;
-    const long long tiles = (long long)((W + GFL_TILE - 1) / GFL_TILE) * ((H + GFL_TILE - 1) / GFL_TILE);
-    if (tiles > FLOW_MAX_TILES) return 0;
-    return (size_t)tiles * FLOW_NV * sizeof(double);
+    const size_t tiles = tile_grid(W, H).tiles();
+    if (tiles > (size_t)FLOW_MAX_TILES) return 0;
+    return tiles * FLOW_NV * sizeof(double);
 }
 
 int gfl_flow_pair(const float* rec_a, int n_a, const int32_t* ids, const int32_t* tile_range, const float* uv_b,
@@ -192,7 +190,7 @@ int gfl_flow_pair(const float* rec_a, int n_a, const int32_t* ids, const int32_t
     if (((uintptr_t)rec_a & 15) || ((uintptr_t)gt_flow & 7) || ((uintptr_t)flow_out & 7) || ((uintptr_t)workspace & 7))
         return GFL_ERR_INVALID;                                                           // (rows are read as float4 + float2)
     hipStream_t s = (hipStream_t)stream;
-    const int gx = (W + GFL_TILE - 1) / GFL_TILE, tiles = flow_tiles(W, H);
+    const auto [gx, gy, tiles] = tile_grid(W, H);
     double* partial = (double*)workspace;
     flow_pair_kernel<<<tiles, 256, 0, s>>>(rec_a, n_a, ids, tile_range, uv_b, uv_b_stride, depth_b, depth_b_stride, n_b,
                                            gt_flow, move_mask, W, H, gx, min_weight, partial, flow_out, valid_out);

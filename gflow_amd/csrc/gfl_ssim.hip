@@ -456,14 +456,15 @@ using namespace gfl;
 
 extern "C" {
 
-static inline size_t align_up256(size_t v) { return (v + 255) / 256 * 256; }
-
-size_t gfl_loss_workspace_bytes(int W, int H) {
-    if (W <= 0 || H <= 0) return 0;
-    const size_t gx = (W + ST - 1) / ST, gy = (H + ST - 1) / ST;
-    return align_up256((size_t)9 * W * H * sizeof(float)) + align_up256(gx * gy * 3 * sizeof(float)) +
-           align_up256(gx * gy * 4 * sizeof(float));
+// The loss workspace, described once: carved over `base`, only measured without one (Arena, gfl_common.hpp).
+struct LossWs { float *dmaps, *p_ssim, *p_grad; size_t bytes; };
+static LossWs loss_ws(void* base, int W, int H) {
+    Arena a{(char*)base};
+    const size_t tiles = (size_t)((W + ST - 1) / ST) * ((H + ST - 1) / ST);
+    return {a.take<float>("dmaps", (size_t)9 * W * H), a.take<float>("p_ssim", tiles * 3), a.take<float>("p_grad", tiles * 4), a.off};
 }
+
+size_t gfl_loss_workspace_bytes(int W, int H) { return (W <= 0 || H <= 0) ? 0 : loss_ws(nullptr, W, H).bytes; }
 
 static int loss_launch(const float* render, const float* gt_rgb, const float* gt_depth, const uint8_t* keep,
                        const float* depth_ab, float lambda_rgb, float lambda_depth, int W, int H, float* d_render,
@@ -477,9 +478,7 @@ static int loss_launch(const float* render, const float* gt_rgb, const float* gt
         return GFL_ERR_INVALID;                                      // the kernels' 32-bit byte offsets
     hipStream_t s = (hipStream_t)stream;
     const int gx = (W + ST - 1) / ST, gy = (H + ST - 1) / ST;
-    float* dmaps = (float*)workspace;
-    float* p_ssim = (float*)((char*)workspace + align_up256((size_t)9 * W * H * sizeof(float)));
-    float* p_grad = (float*)((char*)p_ssim + align_up256((size_t)gx * gy * 3 * sizeof(float)));
+    const auto [dmaps, p_ssim, p_grad, ws_bytes] = loss_ws(workspace, W, H);
     static const Win win = make_window();
     const float hw = (float)W * (float)H;
     // L = lambda_rgb * (mean mse + 1 - mean S)  ->  dL/dS = -lambda_rgb / (3HW)

@@ -104,9 +104,9 @@ typedef enum gfl_status {
  * 305: gfl_fit_state.flags (was reserved_) and GFL_FIT_DETERMINISTIC, gfl_scan_f64.  306: gfl_track_anchor, gfl_track_frame.
  * 307: gfl_seg_score.  308: gfl_recon_frame.  309: the gradient of the intrinsics -- gfl_reduce_cam_workspace_bytes,
  * gfl_project_point_bwd_cam, gfl_ewa_bwd_cam, gfl_render_bwd_cam; the fit workspace is 12 floats per row of cap larger.
- * 310: gfl_flow_pair, gfl_flow_workspace_bytes.
+ * 310: gfl_flow_pair, gfl_flow_workspace_bytes.  311: gfl_fit_workspace_layout.
  * A binding checks gfl_version() >= GFL_VERSION of the header it was written for. */
-#define GFL_VERSION 310
+#define GFL_VERSION 311
 int gfl_version(void);
 /* out[10] = TILE, NEAREST, EXTENT, FOV_CLAMP, LOWPASS, EIG_FLOOR, RADIUS_SIGMA, ALPHA_MIN, ALPHA_MAX, T_MIN of this build */
 int gfl_constants(float* out10);
@@ -377,6 +377,11 @@ typedef struct gfl_fit_hyper {
 } gfl_fit_hyper;
 
 size_t gfl_fit_workspace_bytes(int cap, int K_cap, int W, int H);
+/* the regions of the fit workspace, in address order: returns their number (writes at most `max`), < 0 on invalid sizes.
+ * names: static strings; offsets: multiples of 256; bytes: a region's own size, before it is rounded up to 256.  Needs no
+ * device: the size query, the library's own carve and this table are one walk over one description. */
+int gfl_fit_workspace_layout(int cap, int K_cap, int W, int H,
+                             const char** names, size_t* offsets, size_t* bytes, int max);
 /* render only: fills rec, ids, tile_range, render, final_T, n_contrib, extr */
 int gfl_fit_forward(const gfl_fit_state* st, const gfl_fit_hyper* hp, gfl_stream_t stream);
 /* loss + backward + optimiser step on the state gfl_fit_forward left behind */
