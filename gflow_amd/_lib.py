@@ -23,7 +23,7 @@ _lib = None
 
 c_void_p, c_int, c_float, c_size_t, c_int64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_int64
 
-MIN_VERSION = 311          # GFL_VERSION of the include/gflow_hip.h this binding mirrors (gfl_fit_workspace_layout)
+MIN_VERSION = 312          # GFL_VERSION of the include/gflow_hip.h this binding mirrors (gfl_epi_fundamental, gfl_epi_mask)
 
 # name -> (restype, argtypes); mirrors include/gflow_hip.h one to one
 _P = c_void_p
@@ -96,6 +96,9 @@ SIGNATURES = {
     "gfl_flow_workspace_bytes": (c_size_t, [c_int, c_int]),
     "gfl_flow_pair": (c_int, [_P, c_int, _P, _P, _P, c_int, _P, c_int, c_int, _P, _P, c_int, c_int, c_float, c_int, c_int, _P,
                               _P, _P, _P, c_size_t, _P]),
+    "gfl_epi_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "gfl_epi_fundamental": (c_int, [_P, c_int, c_int, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "gfl_epi_mask": (c_int, [_P, c_int, c_int, _P, ctypes.c_double, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "gfl_abi_sizes": (c_int, [_P, _P]),
     "gfl_profile_enable": (c_int, [ctypes.c_uint]),
     "gfl_profile_read": (c_int, [_P, _P, c_int]),

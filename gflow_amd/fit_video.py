@@ -687,6 +687,9 @@ def main(argv=None):
     ap.add_argument("--no-load-extr", action="store_true",
                     help="do not load the frames' camera poses (extr): the camera-only stages estimate them, as the "
                          "reference's scripts/fit_video.sh runs")
+    ap.add_argument("--make-move-masks", action="store_true",
+                    help="with --sequence: compute every frame's move_mask from its forward flow on the device "
+                         "(gflow_amd.move_seg, before the clock starts) instead of reading <seq>_epipolar")
     ap.add_argument("--metrics-csv", default=None,
                     help="rank 0 writes the blocks that were asked for as key,value lines under the reference's "
                          "metrics.csv keys")
@@ -731,7 +734,8 @@ def main(argv=None):
     clips = {}
     for ci in mine:
         if args.sequence:
-            clips[ci] = gio.load_sequence(args.sequence[ci], resize=args.resize)
+            clips[ci] = gio.load_sequence(args.sequence[ci], resize=args.resize,
+                                          move_masks="epipolar" if args.make_move_masks else "files")
         else:
             clips[ci] = upload_clip(S.make_clip(lengths[ci], args.height, args.width, seed=ci, device=dev), dev)
     # point tracking: the ground truth of every clip, its first-visible queries (those whose frame is not fitted: dropped)

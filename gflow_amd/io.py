@@ -125,10 +125,16 @@ def sequence_paths(sequence_path, frame_start=0, frame_range=-1, skip_interval=1
     )
 
 
-def load_sequence(sequence_path, resize=None, frame_start=0, frame_range=-1, skip_interval=1, depth_offset=0.0):
+def load_sequence(sequence_path, resize=None, frame_start=0, frame_range=-1, skip_interval=1, depth_offset=0.0,
+                  move_masks="files"):
     """Frames in the dict form ``gflow_amd.fit_video.fit_clip`` takes.  Frame i carries the flow
     i -> i+1 (fit_video.py:249: frame i+1 is fitted with flow_paths[i]) and the occlusion mask that
-    fit_video.py:248 reads for it (img_occ_paths[i-1])."""
+    fit_video.py:248 reads for it (img_occ_paths[i-1]).
+    ``move_masks``: "files" reads ``<seq>_epipolar/*_open.png`` (a frame without a file gets zeros); "epipolar" ignores
+    that folder and computes the mask of every frame that has a flow file from that flow, on the device
+    (gflow_amd.move_seg.clip_move_masks; a frame without one gets zeros)."""
+    if move_masks not in ("files", "epipolar"):
+        raise ValueError(f"load_sequence: move_masks must be \"files\" or \"epipolar\", got {move_masks!r}")
     p = sequence_paths(sequence_path, frame_start, frame_range, skip_interval)
     focal, pp, poses = read_camera(p["camera"])
     frames = []
@@ -136,13 +142,17 @@ def load_sequence(sequence_path, resize=None, frame_start=0, frame_range=-1, ski
         fr = dict(image=image_path_to_tensor(ip, resize), focal=focal, pp=pp, name=os.path.basename(ip).split(".")[0])
         fr["depth"] = read_depth(p["depth"][i], resize, depth_offset=depth_offset).unsqueeze(-1)
         H, W = fr["image"].shape[:2]
-        fr["move_mask"] = read_mask(p["move"][i], resize) if i < len(p["move"]) else torch.zeros(H, W, dtype=torch.bool)
+        from_file = move_masks == "files" and i < len(p["move"])
+        fr["move_mask"] = read_mask(p["move"][i], resize) if from_file else torch.zeros(H, W, dtype=torch.bool)
         fr["flow"] = read_flow(p["flow"][i], resize) if i < len(p["flow"]) else torch.zeros(H, W, 2)
         if i >= 1 and i - 1 < len(p["occ"]):
             fr["occ_mask"] = image_path_to_tensor(p["occ"][i - 1], resize)
         if i < len(poses):
             fr["extr"] = torch.tensor(poses[i], dtype=torch.float32)
         frames.append(fr)
+    if move_masks == "epipolar":
+        from .move_seg import clip_move_masks
+        clip_move_masks(frames, n_flows=len(p["flow"]))
     return frames
 
 

@@ -104,9 +104,10 @@ typedef enum gfl_status {
  * 305: gfl_fit_state.flags (was reserved_) and GFL_FIT_DETERMINISTIC, gfl_scan_f64.  306: gfl_track_anchor, gfl_track_frame.
  * 307: gfl_seg_score.  308: gfl_recon_frame.  309: the gradient of the intrinsics -- gfl_reduce_cam_workspace_bytes,
  * gfl_project_point_bwd_cam, gfl_ewa_bwd_cam, gfl_render_bwd_cam; the fit workspace is 12 floats per row of cap larger.
- * 310: gfl_flow_pair, gfl_flow_workspace_bytes.  311: gfl_fit_workspace_layout.
+ * 310: gfl_flow_pair, gfl_flow_workspace_bytes.  311: gfl_fit_workspace_layout.  312: gfl_epi_fundamental, gfl_epi_mask,
+ * gfl_epi_workspace_bytes.
  * A binding checks gfl_version() >= GFL_VERSION of the header it was written for. */
-#define GFL_VERSION 311
+#define GFL_VERSION 312
 int gfl_version(void);
 /* out[10] = TILE, NEAREST, EXTENT, FOV_CLAMP, LOWPASS, EIG_FLOOR, RADIUS_SIGMA, ALPHA_MIN, ALPHA_MAX, T_MIN of this build */
 int gfl_constants(float* out10);
@@ -608,6 +609,48 @@ int gfl_flow_pair(const float* rec_a, int n_a, const int32_t* ids, const int32_t
                   int uv_b_stride, const float* depth_b, int depth_b_stride, int n_b, const float* gt_flow,
                   const uint8_t* move_mask, int W, int H, float min_weight, int pair, int n_pairs, double* sums,
                   float* flow_out, uint8_t* valid_out, void* workspace, size_t workspace_bytes, gfl_stream_t stream);
+
+/* ---- move masks from the flow (312; gflow_amd/move_seg.py, INTEGRATION.md "Move masks from the flow") ------------------
+ * What the reference's utility/move_seg.py makes of a forward flow: a fundamental matrix by least median of squares, the
+ * per-pixel Sampson error, its threshold and three morphological variants.  The LMedS is this library's own and
+ * deterministic -- UNPINNED against cv2.findFundamentalMat(FM_LMEDS), whose sampler and iteration rule cannot be observed
+ * here; the morphology is skimage's as recalled, UNPINNED against skimage as well.
+ * flow: [H][W][2] float32, the flow i -> i + 1 on frame i's grid, in pixels.  Pixel p = y W + x.
+ * Correspondences, in float32 with one rounding per operation (move_seg.py:185-203):
+ *   x1 = (2 (x + 0.5) / W - 1, 2 (y + 0.5) / H - 1),   x2 = x1 + (2 flow.x / (W - 1), 2 flow.y / (H - 1))
+ * Everything after that is float64.  A pixel is UNKNOWN if a component of x2 is not finite (a flow that is not finite, or
+ * so large that 2 flow overflows float32): it enters neither a median nor the maximum, its error is 0 and its mask is 0.
+ * Sampson error of F (row-major, move_seg.py:57-71) with h1 = (x1, 1), h2 = (x2, 1), sums from the left, every product and
+ * sum rounded on its own (no FMA):
+ *   d1 = F h1: d1x = (F0 x1 + F1 y1) + F2, ...;   d2 = F^T h2: d2x = (F0 x2 + F3 y2) + F6, d2y = (F1 x2 + F4 y2) + F7
+ *   z = (x2 d1x + y2 d1y) + d1z;   e = z z / (((d1x^2 + d1y^2) + d2x^2) + d2y^2), and e = 0 where that denominator is 0
+ *
+ * gfl_epi_fundamental: samples [K][8] int32, eight pixel indices per hypothesis, drawn by the caller.  Per hypothesis the
+ * Hartley-normalised 8-point fit: each side's centroid to 0 and mean distance to sqrt(2); the null vector of the 8 x 9
+ * design matrix (rows [x2 x1, x2 y1, x2, y2 x1, y2 y1, y2, x1, y1, 1]) by cyclic Jacobi on A^T A; rank 2 by zeroing the
+ * smallest singular value; F = T2^T Fn T1, scaled to ||F||_F = 1 with its entry of largest magnitude positive.  A
+ * hypothesis is DEGENERATE if an index is outside [0, H W) or repeated, a sampled pixel is unknown, or F is not finite: its
+ * row of F_all is zero and its median +inf.  The score of a hypothesis is the EXACT LOWER MEDIAN of e over the known pixels:
+ * the element (n - 1) / 2 of the sorted errors (radix selection on the bit patterns, which order like the values for
+ * e >= +0; the errors are recomputed per pass, not stored).
+ *   F_all [K][9], medians [K] float64: written, or NULL.   best [1] int32: the smallest median, the lowest index among
+ *   equals, -1 if every hypothesis is degenerate.   F_best [9] float64: row `best` of F_all, zeros for best = -1.
+ * gfl_epi_mask: F [9] float64 ON THE DEVICE (F_best).  err = e ((H + W) / 2)^2 (an error that is not finite counts as 0);
+ * r = err / max(err) over the known pixels; err_norm = (float)r; mask = r > threshold.  If the maximum is 0 or no pixel is
+ * known, every output is zero (the reference divides by zero there).  Morphology with the footprint
+ * disk(R) = {dx^2 + dy^2 <= R^2}: erosion counts pixels outside the image as set, dilation as unset;
+ *   open = dilation(erosion(mask, 2), 2),  erode = erosion(mask, 5),  dilate = dilation(mask, 3).
+ *   err_norm [H][W] float32; mask, open, erode, dilate [H][W] uint8, 0 or 255: each written for every pixel, or NULL.
+ * Both: GFL_ERR_INVALID for W or H < 2, H W < 8 or > 2^30, K < 1 or > 65535, a threshold that is not finite, a null pointer
+ * that is needed; GFL_ERR_WORKSPACE for workspace_bytes < gfl_epi_workspace_bytes(W, H, K) (0 for sizes that are refused;
+ * gfl_epi_mask uses the part that does not depend on K: any K >= 1 will do).  Integer atomics only (counts, and the maximum
+ * on its bit pattern), whose results do not depend on their order: the same inputs give the same bits on every call, in
+ * every mode.  No allocation, no host synchronisation, everything on `stream`. */
+size_t gfl_epi_workspace_bytes(int W, int H, int K);
+int gfl_epi_fundamental(const float* flow, int W, int H, const int32_t* samples, int K, double* F_all, double* medians,
+                        double* F_best, int32_t* best, void* workspace, size_t workspace_bytes, gfl_stream_t stream);
+int gfl_epi_mask(const float* flow, int W, int H, const double* F, double threshold, float* err_norm, uint8_t* mask,
+                 uint8_t* open, uint8_t* erode, uint8_t* dilate, void* workspace, size_t workspace_bytes, gfl_stream_t stream);
 
 /* sizeof(gfl_fit_state), sizeof(gfl_fit_hyper): lets an FFI binding verify its struct mirrors */
 int gfl_abi_sizes(int* sizeof_fit_state, int* sizeof_fit_hyper);
