@@ -99,6 +99,7 @@ SIGNATURES = {
     "gfl_epi_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "gfl_epi_fundamental": (c_int, [_P, c_int, c_int, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
     "gfl_epi_mask": (c_int, [_P, c_int, c_int, _P, ctypes.c_double, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "gfl_flow_occlusion": (c_int, [_P, _P, c_int, c_int, c_int, c_float, c_float, _P, _P, _P, _P, _P]),
     "gfl_abi_sizes": (c_int, [_P, _P]),
     "gfl_profile_enable": (c_int, [ctypes.c_uint]),
     "gfl_profile_read": (c_int, [_P, _P, c_int]),
@@ -127,7 +128,11 @@ def load():
                 "(or `make -C gflow_amd/csrc`).  gflow_amd has no CPU fallback.")
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)          # AttributeError if the ABI drifted
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:           # a stale build: entries are also added within a version (gfl_flow_occlusion)
+                raise RuntimeError(f"{LIB_PATH} has no {name}: it was built from older sources, rebuild the library "
+                                   "(make -C gflow_amd/csrc)") from None
             fn.restype = res
             fn.argtypes = args
         if lib.gfl_version() < MIN_VERSION:

@@ -690,6 +690,10 @@ def main(argv=None):
     ap.add_argument("--make-move-masks", action="store_true",
                     help="with --sequence: compute every frame's move_mask from its forward flow on the device "
                          "(gflow_amd.move_seg, before the clock starts) instead of reading <seq>_epipolar")
+    ap.add_argument("--make-occ-masks", action="store_true",
+                    help="with --sequence: compute every frame's occ_mask from its forward and backward flows "
+                         "(<seq>_flow_unimatch/*pred.flo, *pred_bwd.flo) on the device (gflow_amd.occlusion, before the clock "
+                         "starts) instead of reading *occ_bwd.png")
     ap.add_argument("--metrics-csv", default=None,
                     help="rank 0 writes the blocks that were asked for as key,value lines under the reference's "
                          "metrics.csv keys")
@@ -735,7 +739,8 @@ def main(argv=None):
     for ci in mine:
         if args.sequence:
             clips[ci] = gio.load_sequence(args.sequence[ci], resize=args.resize,
-                                          move_masks="epipolar" if args.make_move_masks else "files")
+                                          move_masks="epipolar" if args.make_move_masks else "files",
+                                          occ_masks="flow" if args.make_occ_masks else "files")
         else:
             clips[ci] = upload_clip(S.make_clip(lengths[ci], args.height, args.width, seed=ci, device=dev), dev)
     # point tracking: the ground truth of every clip, its first-visible queries (those whose frame is not fitted: dropped)

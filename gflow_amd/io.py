@@ -6,6 +6,7 @@ Mirrors ``gflow/utils/read.py`` and ``gflow/utils/conversion.py`` and the direct
     <seq>_depth_mast3r_s2/*.npy      per-frame depth                     (read.py:60-70)
     <seq>_flow_unimatch/*pred.flo    forward flow i -> i+1, Middlebury    (read.py:7-38)
     <seq>_flow_unimatch/*occ_bwd.png occlusion mask of frame i+1          (fit_video.py:88-89,248)
+    <seq>_flow_unimatch/*pred_bwd.flo backward flow i+1 -> i (optional; UniMatch's name as recalled: gflow_amd.occlusion)
     <seq>_epipolar/*_open.png        move mask                           (fit_video.py:96-97)
     <seq>_camera_mast3r_s2/*.json    {"focal", "pp", "pose"}              (read.py:72-89)
 
@@ -120,19 +121,26 @@ def sequence_paths(sequence_path, frame_start=0, frame_range=-1, skip_interval=1
         depth=cut(sorted(Path(sp + "_depth_mast3r_s2").glob("*.npy"))),
         occ=cut(sorted(flow_dir.glob("*occ_bwd.png")) + sorted(flow_dir.glob("*occ_bwd.jpg")), frame_range - 1),
         flow=cut(sorted(flow_dir.glob("*pred.flo"))),
+        flow_bwd=cut(sorted(flow_dir.glob("*pred_bwd.flo"))),
         move=cut(sorted(Path(sp + "_epipolar").glob("*_open.png"))),
         camera=cut(sorted(Path(sp + "_camera_mast3r_s2").glob("*.json"))),
     )
 
 
 def load_sequence(sequence_path, resize=None, frame_start=0, frame_range=-1, skip_interval=1, depth_offset=0.0,
-                  move_masks="files"):
+                  move_masks="files", occ_masks="files"):
     """Frames in the dict form ``gflow_amd.fit_video.fit_clip`` takes.  Frame i carries the flow
     i -> i+1 (fit_video.py:249: frame i+1 is fitted with flow_paths[i]) and the occlusion mask that
     fit_video.py:248 reads for it (img_occ_paths[i-1]).
     ``move_masks``: "files" reads ``<seq>_epipolar/*_open.png`` (a frame without a file gets zeros); "epipolar" ignores
     that folder and computes the mask of every frame that has a flow file from that flow, on the device
-    (gflow_amd.move_seg.clip_move_masks; a frame without one gets zeros)."""
+    (gflow_amd.move_seg.clip_move_masks; a frame without one gets zeros).
+    ``occ_masks``: "files" reads ``*occ_bwd.*``; "flow" ignores those files and computes the mask of frame i + 1 from the
+    flows i -> i + 1 and i + 1 -> i (``*pred_bwd.flo``) at the flows' NATIVE resolution, on the device
+    (gflow_amd.occlusion.clip_occ_masks), then resizes the mask as a mask file would be.  Either way a frame without its
+    file(s) gets no ``occ_mask``."""
+    if occ_masks not in ("files", "flow"):
+        raise ValueError(f"load_sequence: occ_masks must be \"files\" or \"flow\", got {occ_masks!r}")
     if move_masks not in ("files", "epipolar"):
         raise ValueError(f"load_sequence: move_masks must be \"files\" or \"epipolar\", got {move_masks!r}")
     p = sequence_paths(sequence_path, frame_start, frame_range, skip_interval)
@@ -145,7 +153,7 @@ def load_sequence(sequence_path, resize=None, frame_start=0, frame_range=-1, ski
         from_file = move_masks == "files" and i < len(p["move"])
         fr["move_mask"] = read_mask(p["move"][i], resize) if from_file else torch.zeros(H, W, dtype=torch.bool)
         fr["flow"] = read_flow(p["flow"][i], resize) if i < len(p["flow"]) else torch.zeros(H, W, 2)
-        if i >= 1 and i - 1 < len(p["occ"]):
+        if occ_masks == "files" and i >= 1 and i - 1 < len(p["occ"]):
             fr["occ_mask"] = image_path_to_tensor(p["occ"][i - 1], resize)
         if i < len(poses):
             fr["extr"] = torch.tensor(poses[i], dtype=torch.float32)
@@ -153,6 +161,13 @@ def load_sequence(sequence_path, resize=None, frame_start=0, frame_range=-1, ski
     if move_masks == "epipolar":
         from .move_seg import clip_move_masks
         clip_move_masks(frames, n_flows=len(p["flow"]))
+    if occ_masks == "flow":
+        from .occlusion import clip_occ_masks
+        n_pairs = min(len(frames) - 1, len(p["flow"]), len(p["flow_bwd"]))
+        # (the reference resizes a flow without rescaling its values: the check must not see fr["flow"] of a resized clip)
+        fwd = [frames[i]["flow"] if resize is None else read_flow(p["flow"][i]) for i in range(n_pairs)]
+        bwd = [read_flow(p["flow_bwd"][i]) for i in range(n_pairs)]
+        clip_occ_masks(frames, bwd, fwd_flows=fwd, resize=resize)
     return frames
 
 

@@ -155,6 +155,24 @@ class _Scene:
         return dict(image=img.float(), depth=depth.float().unsqueeze(-1), flow=flow.float(), move_mask=move, occ_mask=occ,
                     focal=f, pp=(round(W / 2), round(H / 2)), extr_gt=extr)
 
+    def backward_flow(self, k, device="cpu"):
+        """(H, W, 2) float32: the flow from frame k back to frame k - 1 on frame k's grid (k >= 1) -- where the surface point
+        of a background pixel was under the previous camera (``up`` of ``frame``'s occlusion block), the disc's step
+        backwards on the disc.  With ``frame(k - 1)["flow"]`` it is the pair gflow_amd.occlusion checks."""
+        if k < 1:
+            raise ValueError("backward_flow: frame 0 has no previous frame")
+        H, W, f = self.H, self.W, self.f
+        dt = dict(dtype=torch.float64, device=device)
+        v, u = torch.meshgrid(torch.arange(H, **dt), torch.arange(W, **dt), indexing="ij")
+        a = self.surface_param(u, v, k)
+        up = a - f * self.cam_step * (k - 1) / self.depth0(a, v)
+        ocx, ocy = self.obj_centre(k)
+        pcx, pcy = self.obj_centre(k - 1)
+        move = torch.sqrt((u - ocx) ** 2 + (v - ocy) ** 2) < self.obj_r_px
+        flow_bg = torch.stack([up - u, torch.zeros_like(up)], dim=-1)
+        flow_obj = torch.tensor([pcx - ocx, pcy - ocy], **dt).expand(H, W, 2)
+        return torch.where(move.unsqueeze(-1), flow_obj, flow_bg).float()
+
 
 def make_clip(n_frames, H=480, W=854, seed=0, device="cpu", cam_step=0.01):
     """Frames of one rigid synthetic clip (``_Scene``): frame k is the scene seen from a camera at (k cam_step, 0, 0).

@@ -105,7 +105,8 @@ typedef enum gfl_status {
  * 307: gfl_seg_score.  308: gfl_recon_frame.  309: the gradient of the intrinsics -- gfl_reduce_cam_workspace_bytes,
  * gfl_project_point_bwd_cam, gfl_ewa_bwd_cam, gfl_render_bwd_cam; the fit workspace is 12 floats per row of cap larger.
  * 310: gfl_flow_pair, gfl_flow_workspace_bytes.  311: gfl_fit_workspace_layout.  312: gfl_epi_fundamental, gfl_epi_mask,
- * gfl_epi_workspace_bytes.
+ * gfl_epi_workspace_bytes; gfl_flow_occlusion was added WITHIN 312 (an additive entry: nothing that existed changed, so the
+ * number stays; a binding that needs it looks the symbol up).
  * A binding checks gfl_version() >= GFL_VERSION of the header it was written for. */
 #define GFL_VERSION 312
 int gfl_version(void);
@@ -651,6 +652,34 @@ int gfl_epi_fundamental(const float* flow, int W, int H, const int32_t* samples,
                         double* F_best, int32_t* best, void* workspace, size_t workspace_bytes, gfl_stream_t stream);
 int gfl_epi_mask(const float* flow, int W, int H, const double* F, double threshold, float* err_norm, uint8_t* mask,
                  uint8_t* open, uint8_t* erode, uint8_t* dilate, void* workspace, size_t workspace_bytes, gfl_stream_t stream);
+
+/* ---- occlusion masks from the flows (added within 312; gflow_amd/occlusion.py, INTEGRATION.md "Occlusion masks from the
+ * flows") ----------------------------------------------------------------------------------------------------------------
+ * The forward-backward consistency check that UniMatch runs under --pred_bidir_flow --fwd_bwd_check
+ * (forward_backward_consistency_check), restated from memory: UNPINNED -- neither that code nor its defaults alpha = 0.01,
+ * beta = 0.5 can be observed here.
+ * fwd, bwd: [n_pairs][H][W][2] float32 in pixels, 8-byte aligned.  fwd[p] is the flow a -> b on a's grid, bwd[p] the flow
+ * b -> a on b's grid.  For pixel (x, y) of pair p, with a = fwd[p][y][x] and b = bwd[p][y][x], in float32:
+ *   |v| = sqrt(v.x v.x + v.y v.y);   thr = alpha (|a| + |b|) + beta      (both flows at the SAME pixel index; one threshold
+ *                                                                          for both directions)
+ *   d_f = |a + S(bwd[p], x + a.x, y + a.y)|,  occ_fwd = d_f > thr
+ *   d_b = |b + S(fwd[p], x + b.x, y + b.y)|,  occ_bwd = d_b > thr
+ * S is bilinear sampling in pixel coordinates where a corner outside the image contributes zero: torch's grid_sample(mode=
+ * "bilinear", padding_mode="zeros", align_corners=True).  The weights come from the flow's own fraction, which is exact in
+ * float32 (x + a.x is never formed): i = floor(a.x), t = a.x - i, columns x + i and x + i + 1 with weights 1 - t and t; the
+ * same in y; a corner's weight is the product of the two.  A flow component that is not of magnitude < 2^20 (NaN included)
+ * puts every corner outside: S = 0.  Every corner INSIDE the image enters the sum, so a NaN (or an infinity) there makes
+ * the sample NaN even at weight 0.
+ * A pixel whose d or thr is not finite is UNKNOWN in that direction: its difference is written as 0 and its mask as 0.
+ * (In float32 |v| overflows from a component of about 1.8e19 on: such a flow is unknown, and so is every pixel that samples
+ * it with a weight that keeps the product that large.)
+ *   diff_fwd, diff_bwd [n_pairs][H][W] float32; occ_fwd, occ_bwd [n_pairs][H][W] uint8, 0 or 255: each written for every
+ *   pixel, or NULL (all four NULL: GFL_OK, nothing is launched).
+ * GFL_ERR_INVALID, before anything is launched: W or H < 2, n_pairs < 1, n_pairs H W > 2^30, an alpha or beta that is not
+ * finite or is negative, a null or misaligned input.  ONE launch for all pairs and both directions, one lane per pixel; no
+ * workspace, no atomics, no allocation, no host synchronisation, everything on `stream`; the same inputs give the same bits. */
+int gfl_flow_occlusion(const float* fwd, const float* bwd, int n_pairs, int W, int H, float alpha, float beta,
+                       float* diff_fwd, float* diff_bwd, uint8_t* occ_fwd, uint8_t* occ_bwd, gfl_stream_t stream);
 
 /* sizeof(gfl_fit_state), sizeof(gfl_fit_hyper): lets an FFI binding verify its struct mirrors */
 int gfl_abi_sizes(int* sizeof_fit_state, int* sizeof_fit_hyper);
