@@ -90,6 +90,9 @@ SIGNATURES = {
     "gfl_track_anchor": (c_int, [_P, c_int, c_int, _P, c_int, _P, _P, _P, c_size_t, _P]),
     "gfl_track_frame": (c_int, [_P, c_int, _P, c_int, c_int, _P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_float, _P, _P,
                                 _P]),
+    "gfl_track_history": (c_int, [_P, c_int, _P, c_int, c_int, _P, c_int, c_int, c_float, _P, _P, _P]),
+    "gfl_track_backward_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "gfl_track_backward": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "gfl_seg_score": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     "gfl_recon_workspace_bytes": (c_size_t, [c_int, c_int]),
     "gfl_recon_frame": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),

@@ -22,6 +22,7 @@ import argparse
 import json
 import math
 import os
+import sys
 import time
 
 import torch
@@ -120,8 +121,9 @@ def _mean_over_clips(keys, scores, totals, dist=None, device="cpu", none=float("
 
 def reduce_tapvid(preds, gts, n_frames, dropped, dist=None, device="cpu"):
     """The "tapvid" block: every clip's TAP-Vid score (tracking.evaluate), averaged over the clips as benchmark.py averages
-    its videos; ``clips`` is their number, ``queries_dropped`` what the caller left out."""
-    ms = [TK.evaluate(p, *gts[ci], n_frames[ci]) for ci, p in preds.items()]
+    its videos; ``clips`` is their number, ``queries_dropped`` what the caller left out.  ``gts[ci]``: (points, occluded, H,
+    W), or with (queries, source) behind them for a query set other than the first-visible one (tracking.evaluate)."""
+    ms = [TK.evaluate(p, *gts[ci][:4], n_frames[ci], *gts[ci][4:]) for ci, p in preds.items()]
     return _mean_over_clips(TAPVID_KEYS, ms, dict(clips=len(ms), queries_dropped=dropped), dist, device)
 
 
@@ -310,7 +312,7 @@ def fit_clip(frames, device, cfg=None, fused=True, deterministic=None, **options
 
 def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, log=None, load_extr=True, chunk=None,
                    async_snapshots=True, keep=None, cu_count=0, deterministic=None, track_queries=None, segment=False,
-                   recon=False, camera=False, flow=False):
+                   recon=False, camera=False, flow=False, track_backward=False):
     """fit_clip as a generator: yields after every ``chunk`` iterations of a stage (None: never) and returns the metrics
     dict of the clip (PSNR summed over its frames; with ``cfg["traj_num"]`` > 0 also ``"traj"``: the per-frame trajectory
     images and seed projections, host arrays -- what the reference's frame loop collects in
@@ -331,6 +333,9 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
     a frame of the clip): every query is anchored at the end of its frame and tracked, with an occlusion flag, at the end of
     every later one; the dict then has ``"tracks"`` (Tracker.result()).  ``keep["record_track_inputs"] = True``: the
     per-frame (uv, depth, depth_map) the tracker read, cloned, in ``keep["track_inputs"]``.
+    ``track_backward`` (needs ``track_queries``, else ValueError): the frames before a query's frame are tracked too
+    (Tracker(backward=True); INTEGRATION.md, "Point tracking"): one more launch per frame on the forward the tracker already
+    reads (``rasterisations`` does not change), one pass at the end of the clip; ``"tracks"`` then has ``back_anchor``.
     ``segment``: also the moving region of every frame and its DAVIS score against the frame's ``move_mask``
     (gflow_amd.segmentation.MoveSegRecorder; INTEGRATION.md, "Moving-region segmentation"): the dict then has
     ``"segmentation"`` = dict(masks (T, H, W) uint8, valid (T,) bool, counts (T, 6) int64, J, F, JF (T,) float64).  Nothing
@@ -350,6 +355,8 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
     still, moving)); ``flow="maps"`` also keeps the maps: ``maps`` (T-1, H, W, 2) float32, frame i -> i + 1 on frame i's
     grid, and ``valid`` (T-1, H, W) bool.  A one-frame clip gives empty arrays.  ``keep["record_flow_inputs"] = True``: clones
     of each pair's kernel inputs (dicts) in ``keep["flow_inputs"]``."""
+    if track_backward and track_queries is None:
+        raise ValueError("fit_clip(track_backward=True) needs track_queries")
     from .trainer import SimpleGaussian
     c = dict(DEFAULTS)
     c.update(cfg or {})
@@ -358,7 +365,8 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
     f0 = frames[0]
     tracker = None
     if track_queries is not None:
-        tracker = TK.Tracker(track_queries, len(frames), device)     # (ValueError before anything is fitted)
+        # (ValueError before anything is fitted)
+        tracker = TK.Tracker(track_queries, len(frames), device, backward=bool(track_backward))
     cam_rec = None
     if camera:
         cam_gt = [fr["extr_gt"] if fr.get("extr_gt") is not None else fr.get("extr") for fr in frames]
@@ -585,7 +593,7 @@ NUMERIC_KEYS = ("psnr_sum", "frames", "iterations", "rasterisations", "clips", "
 
 
 def fit_clips_concurrent(clips, device, cfg=None, seeds=None, chunk=32, partition=False, deterministic=None,
-                         track_queries=None, **options):
+                         track_queries=None, track_backward=False, **options):
     """Fit several clips AT THE SAME TIME on ONE device, in one host thread: every clip has its own trainer, engine and
     STREAM, and the clips take turns enqueueing ``chunk`` iterations each (fit_clip_steps), so their graph launches
     interleave on the device.  One fit leaves the chip partly idle -- its kernels are a chain of dependent launches,
@@ -602,11 +610,14 @@ def fit_clips_concurrent(clips, device, cfg=None, seeds=None, chunk=32, partitio
     on it (the schedule never enters a result).  Measured in bench.py's ``clips_per_gpu`` table.
     ``deterministic`` (None: torch's switch): every clip's result is bit for bit that of fit_clip(..., deterministic=True)
     with the same seed -- without ``partition``, which changes the number of tile queues (include/gflow_hip.h).
-    ``track_queries``: None, or one entry (fit_clip_steps' ``track_queries``, or None) per clip.  ``options``: fit_clip_steps'
+    ``track_queries``: None, or one entry (fit_clip_steps' ``track_queries``, or None) per clip; ``track_backward``:
+    fit_clip_steps' for every clip that has queries (ValueError without ``track_queries``).  ``options``: fit_clip_steps'
     other ones, for all clips (``async_snapshots`` and ``cu_count`` are set here)."""
     n = len(clips)
     if track_queries is not None and len(track_queries) != n:
         raise ValueError("fit_clips_concurrent: track_queries needs one entry per clip")
+    if track_backward and track_queries is None:
+        raise ValueError("fit_clips_concurrent(track_backward=True) needs track_queries")
     seeds = list(range(n)) if seeds is None else seeds
     dev = torch.device(device)
     if dev.index is None:
@@ -625,7 +636,8 @@ def fit_clips_concurrent(clips, device, cfg=None, seeds=None, chunk=32, partitio
     #  engine per clip cost them more than they give)
     gens = [fit_clip_steps(clips[i], dev, cfg, seed=seeds[i], chunk=chunk, async_snapshots=n == 1,
                            cu_count=shares[i][1] if shares else 0, deterministic=deterministic,
-                           track_queries=None if track_queries is None else track_queries[i], **options)
+                           track_queries=None if track_queries is None else track_queries[i],
+                           track_backward=bool(track_backward) and track_queries[i] is not None, **options)
             for i in range(n)]
     results = [None] * n
     live = list(range(n))
@@ -666,6 +678,12 @@ def main(argv=None):
     ap.add_argument("--track", action="store_true",
                     help="track the first-visible query points of each clip's tracking.pkl (synthetic clips: their "
                          "make_clip_tracks) through the fit and score them with TAP-Vid (a \"tapvid\" block in the line)")
+    ap.add_argument("--track-backward", action="store_true",
+                    help="with --track: also track every query through the frames before its own (the \"tapvid\" block "
+                         "then carries \"backward\": true)")
+    ap.add_argument("--track-queries", choices=("first", "strided"), default="first",
+                    help="with --track: the query protocol -- each track's first visible frame, or TAP-Vid's strided one "
+                         "(every fifth frame where the track is visible; wants --track-backward)")
     ap.add_argument("--track-out", default=None, help="with --track: write each clip's predicted tracks to DIR/clip_<i>.npz")
     ap.add_argument("--seg", action="store_true",
                     help="keep every frame's moving-region mask and score it against the frame's move_mask with DAVIS J, F "
@@ -698,6 +716,11 @@ def main(argv=None):
                     help="rank 0 writes the blocks that were asked for as key,value lines under the reference's "
                          "metrics.csv keys")
     args = ap.parse_args(argv)
+    if args.track_backward and not args.track:
+        ap.error("--track-backward needs --track")
+    if args.track and args.track_queries == "strided" and not args.track_backward:
+        print("warning: --track-queries strided without --track-backward: every frame before a query is a miss",
+              file=sys.stderr)
     det = True if args.deterministic else None
     from . import synthetic as S
     rank = int(os.environ.get("RANK", "0"))
@@ -753,17 +776,22 @@ def main(argv=None):
             else:
                 g = S.make_clip_tracks(lengths[ci], args.height, args.width, seed=ci)
                 pts, occ = g["points"].astype("float32"), g["occluded"]
-            q = TK.first_visible_queries(pts, occ, h, w)
-            keep = q[:, 0] < len(clips[ci])
+            if args.track_queries == "strided":
+                q, src = TK.strided_queries(pts, occ, h, w)
+                keep = q[:, 0] < len(clips[ci])
+                gts[ci] = (pts, occ, h, w, q[keep], src[keep])
+            else:
+                q = TK.first_visible_queries(pts, occ, h, w)
+                keep = q[:, 0] < len(clips[ci])
+                gts[ci] = (pts[keep], occ[keep], h, w)
             dropped += int((~keep).sum())
-            gts[ci] = (pts[keep], occ[keep], h, w)
             queries[ci] = q[keep]
     t_load = time.perf_counter() - t_load
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     c = max(1, args.clips_per_gpu)
     order = sorted(clips, key=lambda j: (-lengths[j], j))          # (clips of similar length share the GPU)
-    options = dict(deterministic=det, segment=args.seg, recon=args.recon, camera=args.camera,
+    options = dict(track_backward=args.track_backward, deterministic=det, segment=args.seg, recon=args.recon, camera=args.camera,
                    flow=("maps" if args.flow_out else True) if args.flow else False, load_extr=not args.no_load_extr)
     results = {}
     for g0 in range(0, len(order), c):
@@ -787,6 +815,8 @@ def main(argv=None):
     if args.track:
         preds = of("tracks")
         out["tapvid"] = reduce_tapvid(preds, gts, {ci: len(clips[ci]) for ci in clips}, dropped, *over_ranks)
+        if args.track_backward:
+            out["tapvid"]["backward"] = True
         if args.track_out:
             import numpy as np
             os.makedirs(args.track_out, exist_ok=True)

@@ -106,7 +106,8 @@ typedef enum gfl_status {
  * gfl_project_point_bwd_cam, gfl_ewa_bwd_cam, gfl_render_bwd_cam; the fit workspace is 12 floats per row of cap larger.
  * 310: gfl_flow_pair, gfl_flow_workspace_bytes.  311: gfl_fit_workspace_layout.  312: gfl_epi_fundamental, gfl_epi_mask,
  * gfl_epi_workspace_bytes; gfl_flow_occlusion was added WITHIN 312 (an additive entry: nothing that existed changed, so the
- * number stays; a binding that needs it looks the symbol up).
+ * number stays; a binding that needs it looks the symbol up).  gfl_track_history, gfl_track_backward and
+ * gfl_track_backward_workspace_bytes were added WITHIN 312 in the same way.
  * A binding checks gfl_version() >= GFL_VERSION of the header it was written for. */
 #define GFL_VERSION 312
 int gfl_version(void);
@@ -540,6 +541,35 @@ int gfl_track_anchor(const float* uv, int uv_stride, int N, const double* query_
 int gfl_track_frame(const float* uv, int uv_stride, const float* depth, int depth_stride, int N, const float* depth_map,
                     int W, int H, const int32_t* anchor, const double* shift_xy, int n_anchored, int frame, int T,
                     float occ_threshold, float* tracks, uint8_t* occluded, gfl_stream_t stream);
+
+/* ---- backward point tracking (added within 312; gflow_amd/tracking.py, INTEGRATION.md "Point tracking") --------------
+ * The frames BEFORE a query's frame.  Rows are only ever appended, N_0 <= N_1 <= ...: a query [t, y, x] is carried back to
+ * frame i < t by a splat that frame i already had.  With uv_i the (u, v) of frame i and xy = (x, y):
+ *   b = back_anchor[q][i] = argmin over n < N_i of |uv_t[n] - xy|^2   -- positions of the query's OWN frame, candidates cut
+ *       to frame i's rows; gfl_track_anchor's key order (float64, products and sum rounded on their own, a NaN distance
+ *       first, the lowest index among equal minima).  Hence b == anchor[q] wherever anchor[q] < N_i.
+ *   tracks[q][i] = (float)((double)uv_i[b] + (xy - (double)uv_t[b]))
+ *   occluded[q][i] = gfl_track_frame's flag of row b in frame i
+ * gfl_track_history, once per frame, one lane per row: hist_uv[n] = (u, v) of row n (float32 [N][2]) and hist_occ[n] =
+ * |depth_map[rint(v)][rint(u)] - depth[n * depth_stride]| > occ_threshold (uint8 [N]; float32, rint half to even, a rounded
+ * pixel outside the image: 1) -- this frame's slice of the clip's history.  Strided inputs as gfl_track_frame's.  N == 0
+ * launches nothing.
+ * gfl_track_backward, once per clip: hist_uv / hist_occ are the frames' slices concatenated, row_start a DEVICE int64[T + 1]
+ * with N_i = row_start[i + 1] - row_start[i] (the caller guarantees N_i >= 1 and N_i <= N_{i+1}: the library cannot check a
+ * device array without reading it back; rows past a later frame's count are never read), query_frame a DEVICE int32[Q]
+ * (queries sorted by frame are fastest, any order is correct; a frame outside (0, T) leaves the query's row untouched),
+ * query_xy float64 [Q][2], hist_uv 8-byte aligned.  Writes ONLY the columns i < t of tracks [Q][T][2], occluded [Q][T] and
+ * back_anchor (int32 [Q][T]; may be NULL).  A row that does not exist (N_i == 0) gives a NaN track, occluded, back_anchor
+ * -1.  Three launches; deterministic by construction (a lexicographic minimum over (distance, index), no atomics).
+ * workspace: gfl_track_backward_workspace_bytes(Q, T) (callable without a device).
+ * All: no allocation, no host synchronisation; callable on the fit's stream.  GFL_ERR_INVALID before any launch for null
+ * pointers, T <= 0, Q < 0, N < 0, uv_stride < 2, depth_stride < 1; GFL_ERR_WORKSPACE for a workspace that is too small. */
+int gfl_track_history(const float* uv, int uv_stride, const float* depth, int depth_stride, int N, const float* depth_map,
+                      int W, int H, float occ_threshold, float* hist_uv, uint8_t* hist_occ, gfl_stream_t stream);
+size_t gfl_track_backward_workspace_bytes(int Q, int T);
+int gfl_track_backward(const float* hist_uv, const uint8_t* hist_occ, const int64_t* row_start, int T,
+                       const double* query_xy, const int32_t* query_frame, int Q, float* tracks, uint8_t* occluded,
+                       int32_t* back_anchor, void* workspace, size_t workspace_bytes, gfl_stream_t stream);
 
 /* ---- moving-region segmentation score (307; gflow_amd/segmentation.py, INTEGRATION.md "Moving-region segmentation") ----
  * The sums behind the reference's per-frame J and F (gflow/benchmark.py:244-285, utils/measures/jaccard.py:14-34,
