@@ -396,13 +396,15 @@ def assert_opacity_regime(sets, ref_grads=None, min_rows=None):
 REGIME_LAMBDAS = dict(lambda_rgb=1.0, lambda_depth=0.1, lambda_var=0.0)     # (with lambda_var = 10 the variance term is most of d_scale)
 
 
-def reference_fit(scene, pose, img, dep, dtype=torch.float32, lam=REGIME_LAMBDAS, bg=0.0):
+def reference_fit(scene, pose, img, dep, dtype=torch.float32, lam=REGIME_LAMBDAS, bg=0.0, ab=None):
     """One forward + backward of the oracle's fit iteration on the raw rows of ``scene``: the render (4, H, W), the
-    gradients by attribute (N, width), those of the pose and of the depth affine, the loss terms and the pair count."""
+    gradients by attribute (N, width), those of the pose and of the depth affine, the loss terms and the pair count.
+    ``ab``: the depth affine (2,) the iteration starts from ((1, 0) if None: a fresh engine's)."""
     from oracle import fit_oracle as FO
     rc = {k: v.detach().to(dtype).clone().requires_grad_(True) for k, v in scene["raw"].items()}
     p = pose.detach().to(dtype).clone().requires_grad_(True)
-    ab = torch.tensor([1.0, 0.0], dtype=dtype, requires_grad=True)
+    ab = torch.tensor([1.0, 0.0], dtype=dtype) if ab is None else ab.detach().to(dtype).clone()
+    ab.requires_grad_(True)
     frame = dict(image=img.to(dtype), depth=dep.to(dtype))
     loss, info = FO.fit_loss(rc, p, ab, scene["intr"].to(dtype), frame, bg, lam["lambda_rgb"], lam["lambda_depth"], lam["lambda_var"])
     loss.backward()
@@ -421,6 +423,103 @@ def regime_error(got, ref, rows):
     rel = (a - b).norm().item() / den if den > 0 else (0.0 if float(err.max()) == 0 else float("inf"))
     bad = (err > 5e-4 * b.abs().max().item() + 5e-3 * b.abs()).double().mean().item()
     return rel, bad
+
+
+# ------------------------------------------------------------------ a running engine: rows that change their pair-row layout
+# The fused backward keeps a pair's gradient row at (splat, index of the tile in the splat's tile rectangle): 32 rows of its
+# own for a splat of up to SLOT_MAX = 32 tiles, a run out of a pool for a wider one; rows are never cleared, a stamp says
+# which forward wrote them.  LAYOUT: 0 = at most 16 tiles, 1 = 17 .. 32, 2 = more than 32 (the pool).
+CLASS_RADII = (3, 7, 12, 20, 24, 28, 31, 33, 36, 40, 44, 48, 56, 70)
+CLASS_PER_RADIUS = 12
+N_CULLED = 6                  # the last class rows: behind the camera on odd steps of ``apply_transition``
+
+
+def layout_class(tiles):
+    """0 / 1 / 2 for a tile count of at most 16 / 17 .. 32 / more than 32 (-1 for a row in no tile)."""
+    t = tiles.reshape(-1).long()
+    return torch.where(t <= 0, -1, torch.where(t <= 16, 0, torch.where(t <= 32, 1, 2)))
+
+
+def transition_scene(W=168, H=120, seed=14, extr=None, n_base=1500):
+    """``CLASS_PER_RADIUS`` "class" rows per pixel radius of ``CLASS_RADII`` in front of (as rows: before) ``n_base`` ordinary
+    rows (random_scene seed 31, as raw rows).  A class row of wanted radius r has sigma = sqrt(((r - 0.5) / 3)^2 - 0.3) pixels
+    on its longest axis (the EWA radius is ceil(3 sqrt(lambda_max + 0.3))) and 0.8, 0.6 of that on the others under a random
+    rotation; centres uniform over the WHOLE image, so the tile rectangles are cut by all four borders and by the partial
+    right column / bottom row; depth 1 .. 4; opacity 0.05 .. 0.30: nothing saturates and the exact-disc test prunes the
+    corners of the rectangles.  ``extr`` (3, 4): the camera the class rows are placed for (the identity if None).
+    Returns the camera, ``raw`` and ``rows`` (the class rows' indices)."""
+    s = random_scene(n_base, W, H, seed=31, sigma_px=2.5, tilt=False)
+    base = raw_rows(s)
+    g = torch.Generator().manual_seed(seed)
+    f = float(s["intr"][0])
+    n = CLASS_PER_RADIUS * len(CLASS_RADII)
+    r = torch.tensor(CLASS_RADII, dtype=torch.float64).repeat_interleave(CLASS_PER_RADIUS)
+    r = r[torch.randperm(n, generator=g)]                                  # (the culled rows: the last six, of any radius)
+    sig = torch.sqrt(((r - 0.5) / 3.0) ** 2 - 0.3)
+    z = 1.0 + 3.0 * torch.rand(n, generator=g, dtype=torch.float64)
+    u = W * torch.rand(n, generator=g, dtype=torch.float64)
+    v = H * torch.rand(n, generator=g, dtype=torch.float64)
+    xyz = torch.stack([(u - W / 2) / f * z, (v - H / 2) / f * z, z], dim=1)
+    if extr is not None:
+        xyz = (xyz - extr[:, 3].double()) @ extr[:, :3].double()           # inverse of R x + t
+    scale = (sig / f * z).unsqueeze(1) * torch.tensor([1.0, 0.8, 0.6], dtype=torch.float64)
+    sign = torch.where(torch.rand(n, 3, generator=g) > 0.3, 1.0, -1.0).double()
+    rot = 1.7 * torch.nn.functional.normalize(torch.randn(n, 4, generator=g, dtype=torch.float64), dim=1)
+    o = 0.05 + 0.25 * torch.rand(n, 1, generator=g, dtype=torch.float64)
+    cls = dict(xyz=xyz, scale=scale * sign, rotate=rot, opacity=torch.logit(o) / 10.0,
+               rgb=torch.logit(0.02 + 0.96 * torch.rand(n, 3, generator=g, dtype=torch.float64)))
+    raw = {k: torch.cat([cls[k].float(), base[k]]).contiguous() for k in ATTRS}
+    return dict(raw=raw, rows=torch.arange(n), intr=s["intr"], extr=s["extr"], W=W, H=H)
+
+
+def apply_transition(raw, rows, step, f):
+    """Edits the class rows ``rows`` of ``raw`` (a dict of (N, k) tensors or of live views of an engine's rows, on any
+    device) IN PLACE.  Odd ``step``: raw scale x 1.25 on the even class rows and / 1.25 on the odd ones, every class row
+    9 pixels to the right (x += 9 / f |z|), and the last ``N_CULLED`` class rows behind the camera (z -> -z).  Even ``step``
+    (> 0): the inverse.  ``f``: the scene's focal length in pixels (``intr[0]``)."""
+    if step <= 0:
+        return
+    f = float(f)
+    rows = rows.to(raw["xyz"].device)
+    odd = step % 2 == 1
+    even_rows, odd_rows = rows[0::2], rows[1::2]
+    k = 1.25 if odd else 1.0 / 1.25
+    raw["scale"][even_rows] = raw["scale"][even_rows] * k
+    raw["scale"][odd_rows] = raw["scale"][odd_rows] / k
+    culled = rows[-N_CULLED:]
+    if not odd:
+        raw["xyz"][culled, 2] = -raw["xyz"][culled, 2]
+    raw["xyz"][rows, 0] = raw["xyz"][rows, 0] + (9.0 if odd else -9.0) / f * raw["xyz"][rows, 2].abs()
+    if odd:
+        raw["xyz"][culled, 2] = -raw["xyz"][culled, 2]
+
+
+def rect_facts(fe, W, H):
+    """Of the oracle front end ``fe``: per row, the tile count and whether its UNCLIPPED tile rectangle crosses the left,
+    right, top, bottom border of the tile grid (boolean (N,) each; rows in no tile: False)."""
+    from oracle import msplat_oracle as MO
+    gx, gy = MO.tile_grid(W, H)
+    r = fe["radius"].reshape(-1).to(fe["uv"].dtype)
+    u, v = fe["uv"][:, 0], fe["uv"][:, 1]
+    live = fe["tiles"].reshape(-1) > 0
+    return dict(tiles=fe["tiles"].reshape(-1).long(), left=live & (u - r < 0), top=live & (v - r < 0),
+                right=live & (torch.trunc((u + r + 15) / 16) > gx), bottom=live & (torch.trunc((v + r + 15) / 16) > gy))
+
+
+def pile_toggle_rows(sc, n=40):
+    """The ``n`` nearest rows of the capped pile (smallest raw z among the pile's rows)."""
+    return torch.argsort(sc["raw"]["xyz"][:sc["n_pile"], 2])[:n]
+
+
+def pile_phase(sc, phase, rows=None):
+    """The capped pile with its ``pile_toggle_rows`` invisible (phase "A": raw opacity -1.0, o = 4.5e-5 < 1/255) or as
+    committed (phase "B").  A copy; ``sc`` is left as it is."""
+    rows = pile_toggle_rows(sc) if rows is None else rows
+    out = dict(sc)
+    out["raw"] = {k: v.clone() for k, v in sc["raw"].items()}
+    if phase == "A":
+        out["raw"]["opacity"][rows] = -1.0
+    return out
 
 
 # ------------------------------------------------------------------ known answers at the cap and at the threshold
