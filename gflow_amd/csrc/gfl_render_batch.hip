@@ -1,0 +1,417 @@
+// Batched inference rasteriser: many (splat range, camera) jobs per call, uint8 written by the blend itself
+// (gfl_render_batch, include/gflow_hip.h -- the call sites it replaces are viewer.py:201-228 and render.py:6-108).
+//
+// A (job, tile) pair is a VIRTUAL TILE vt = job * T + tile; everything below is the single-image pipeline over J * T of them.
+// Six launches per call, whatever J, the row counts or the data are:
+//   setup      : the jobs' row ranges become record offsets (a prefix over the jobs), the virtual tiles' counters are cleared;
+//   preprocess : one lane per (job, row): projection, covariance, EWA, the 12-float record -- the device functions and the order
+//                of preprocess_block's op_mode (gfl_fit_bin.hip), with the camera of the ROW'S JOB -- and one integer add per
+//                (splat, tile) pair into the virtual tile's counter;
+//   scan       : one workgroup turns the counters into list offsets in (job, tile) order, cuts the pool at K_cap and flags the
+//                jobs that lost pairs;
+//   scatter    : the lanes of the preprocess walk their tiles again and write (depth bits << 32 | record row) keys;
+//   tile sort  : gfl_tile_sort_only over the J * T segments (gfl_tile_sort.hpp: unique keys, so arrival order is irrelevant);
+//   blend      : a workgroup per virtual tile, lanes = pixels, a wave per 8x8 block, records staged through LDS FB at a time,
+//                four sums per pixel -- center_blend_kernel's shape (gfl_fit_snap.hip) with the true records.  No checkpoints,
+//                no n_contrib / final_T, no queues: nothing here is for a backward.
+//
+// Truncation.  Lists are laid out in (job, tile) order.  A list that does not fit below K_cap WHOLE gets no room at all, and
+// neither does any list behind it: which keys of a cut list survive would depend on the order the scatter's lanes arrive in,
+// and an image must not.  So a truncated job is reproducible too, every job before the cut is untouched by it, and
+// overflow[j] = 1 exactly for the jobs that own a non-empty list at or behind the cut.
+#include "gfl_fit.hpp"
+
+namespace gfl {
+
+constexpr int RB_BLOCK = 256;
+constexpr int RB_CAM = 17;            // floats per job: fx fy cx cy | extr 3x4 | bg
+constexpr int RB_SCAN = 1024;
+constexpr int RB_VT_MAX = 1 << 28;    // virtual tiles per call
+
+__device__ __forceinline__ int rb_sat_add(int a, int b) {
+    const long long s = (long long)a + (long long)b;
+    return s > 0x7fffffffLL ? 0x7fffffff : (int)s;
+}
+
+// the job of record row v: the largest j with off[j] <= v (meta[j] = {record offset, first params row}; offsets do not decrease,
+// v < meta[J].x, so that job has v inside its range even when jobs of count 0 share its offset)
+__device__ __forceinline__ int rb_find_job(const int2* __restrict__ meta, int J, int v) {
+    int lo = 0, hi = J;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (meta[mid].x <= v) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// ---------------------------------------------------------------- setup
+// block 0: record offsets.  A range that leaves [0, R), or records beyond rows_total, are dropped and flagged 2.
+__global__ void __launch_bounds__(RB_BLOCK) rb_setup_kernel(const int32_t* __restrict__ job_rows, int J, int R, int rows_total,
+                                                            int2* __restrict__ meta, int32_t* __restrict__ overflow,
+                                                            int32_t* __restrict__ vt_count, int VT) {
+    for (int i = blockIdx.x * RB_BLOCK + threadIdx.x; i < VT; i += gridDim.x * RB_BLOCK) vt_count[i] = 0;
+    if (blockIdx.x != 0) return;
+    __shared__ int32_t s_sum[RB_BLOCK];
+    const int tid = threadIdx.x;
+    const int per = (J + RB_BLOCK - 1) / RB_BLOCK;
+    const int j0 = min(J, tid * per), j1 = min(J, j0 + per);
+    auto count_of = [&](int j, int& first) {
+        first = job_rows[2 * j];
+        const int cnt = job_rows[2 * j + 1];
+        const bool ok = first >= 0 && cnt >= 0 && first <= R && cnt <= R - first;
+        if (!ok) first = 0;
+        return ok ? cnt : -1;
+    };
+    int local = 0;
+    for (int j = j0; j < j1; ++j) {
+        int first;
+        local = rb_sat_add(local, max(count_of(j, first), 0));
+    }
+    s_sum[tid] = local;
+    __syncthreads();
+    int run = 0;
+    for (int t = 0; t < tid; ++t) run = rb_sat_add(run, s_sum[t]);
+    for (int j = j0; j < j1; ++j) {
+        int first;
+        const int cnt = count_of(j, first);
+        const int end = rb_sat_add(run, max(cnt, 0));
+        const int off_c = min(run, rows_total), end_c = min(end, rows_total);
+        meta[j] = make_int2(off_c, first);
+        overflow[j] = (cnt < 0 || end_c - off_c < cnt) ? 2 : 0;
+        run = end;
+    }
+    if (tid == RB_BLOCK - 1) meta[J] = make_int2(min(run, rows_total), 0);
+}
+
+// ---------------------------------------------------------------- preprocess
+// walks the tiles of a lane's splat (few tiles: the lane itself; many: the wave, 64 at a time) and calls f(virtual tile, the
+// splat's `own` word) for every hit
+template <typename F>
+__device__ __forceinline__ void rb_walk_tiles(float u, float v, float cutoff, int x0, int y0, int nx, int nt, int gx, int base,
+                                              unsigned long long own, F&& f) {
+    const bool wide = nt > WIDE_TILES;
+    if (nt > 0 && !wide) {
+        for (int q = 0; q < nt; ++q) {
+            const int tx = x0 + q % nx, ty = y0 + q / nx;
+            if (tile_hit2(u, v, cutoff, tx, ty)) f(base + ty * gx + tx, own);
+        }
+    }
+    const int lane = threadIdx.x & 63;
+    unsigned long long todo = __ballot(wide);
+    while (todo) {
+        const int src = (int)__builtin_ctzll(todo);
+        todo &= todo - 1;
+        const float su = __shfl(u, src), sv = __shfl(v, src), sc = __shfl(cutoff, src);
+        const int sx0 = __shfl(x0, src), sy0 = __shfl(y0, src), snx = __shfl(nx, src), snt = __shfl(nt, src);
+        const int sbase = __shfl(base, src);
+        const unsigned long long sown = ((unsigned long long)(unsigned)__shfl((int)(unsigned)(own >> 32), src) << 32) |
+                                        (unsigned long long)(unsigned)__shfl((int)(unsigned)own, src);
+        for (int q = lane; q < snt; q += 64) {
+            const int tx = sx0 + q % snx, ty = sy0 + q / snx;
+            if (tile_hit2(su, sv, sc, tx, ty)) f(sbase + ty * gx + tx, sown);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(RB_BLOCK) rb_preprocess_kernel(const float* __restrict__ params, const int2* __restrict__ meta,
+                                                                 const float* __restrict__ job_cam, int J, int W, int H, int gx,
+                                                                 int gy, float* __restrict__ rec, float* __restrict__ out_rec,
+                                                                 int32_t* __restrict__ vt_count) {
+    const int i = blockIdx.x * RB_BLOCK + threadIdx.x;
+    const int total = meta[J].x;
+    float u = 0.f, v = 0.f, cutoff = 0.f;
+    int x0 = 0, y0 = 0, nx = 0, nt = 0, base = 0;
+    if (i < total) {
+        const int job = rb_find_job(meta, J, i);
+        const int2 m = meta[job];
+        const float4* prow = reinterpret_cast<const float4*>(params + (size_t)(m.y + (i - m.x)) * ROW);
+        const float4 r0 = prow[0], r1 = prow[1], r2 = prow[2], r3 = prow[3];
+        const float* cam = job_cam + (size_t)job * RB_CAM;
+        const Cam c = load_cam(cam, cam + 4);
+        // ---- preprocess_block's op_mode, term for term
+        const Splat s = splat_from_row(r0, r1, r2, r3, true);
+        const Proj p = project_fwd(c, s.x, s.y, s.z, W, H, GFL_NEAREST, GFL_EXTENT);
+        float depth = 0.f, A = 0.f, B = 0.f, C = 0.f;
+        int rad = 0;
+        if (p.vis) {
+            float cov[6];
+            cov3d_fwd(s.s, s.q, cov);
+            u = p.u; v = p.v; depth = p.pz;
+            const Ewa e = ewa_fwd(c, p.px, p.py, p.pz, cov, W, H);
+            if (e.ok) {
+                const int r = ewa_radius(e);
+                int x1, y1;
+                tile_rect(u, v, r, gx, gy, x0, x1, y0, y1);
+                const int n = (x1 - x0) * (y1 - y0);
+                if (n > 0) {
+                    rad = r;
+                    A = e.c / e.det; B = -e.b / e.det; C = e.a / e.det;
+                    cutoff = alpha_cutoff(s.o, e.lam);
+                    nx = x1 - x0; nt = n;
+                }
+            }
+        }
+        base = job * (gx * gy);
+        const float4 q0 = make_float4(u, v, A, B), q1 = make_float4(C, s.o, s.c[0], s.c[1]),
+                     q2 = make_float4(s.c[2], depth, cutoff, __int_as_float(rad));
+        float4* r4 = reinterpret_cast<float4*>(rec + (size_t)i * REC);
+        r4[0] = q0; r4[1] = q1; r4[2] = q2;
+        if (out_rec) {
+            float4* o4 = reinterpret_cast<float4*>(out_rec + (size_t)i * REC);
+            o4[0] = q0; o4[1] = q1; o4[2] = q2;
+        }
+    }
+    // (integer adds: the counts do not depend on the order they arrive in)
+    rb_walk_tiles(u, v, cutoff, x0, y0, nx, nt, gx, base, 0ull, [&](int vt, unsigned long long) { atomicAdd(&vt_count[vt], 1); });
+}
+
+// ---------------------------------------------------------------- scan
+// counts -> offsets in (job, tile) order, cut at the last list that ends at or below K_cap; the counters become the scatter's
+// cursors (zero).  One workgroup: a lane owns a run of consecutive virtual tiles.
+__global__ void __launch_bounds__(RB_SCAN) rb_scan_kernel(int32_t* __restrict__ vt_count, int VT, int T, int K_cap,
+                                                          int32_t* __restrict__ vt_off, int32_t* __restrict__ overflow) {
+    __shared__ int32_t s_wave[RB_SCAN / 64];
+    __shared__ int32_t s_cut;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int per = (VT + RB_SCAN - 1) / RB_SCAN;
+    const int i0 = (int)min((long long)VT, (long long)tid * per), i1 = min(VT, i0 + per);
+    if (tid == 0) s_cut = 0;
+    int local = 0;
+    for (int i = i0; i < i1; ++i) local = rb_sat_add(local, vt_count[i]);
+    int sc = local;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int n = __shfl_up(sc, off);
+        if (lane >= off) sc = rb_sat_add(sc, n);
+    }
+    if (lane == 63) s_wave[wid] = sc;
+    __syncthreads();
+    int wprefix = 0;
+    for (int w = 0; w < wid; ++w) wprefix = rb_sat_add(wprefix, s_wave[w]);
+    const int prev = __shfl_up(sc, 1);
+    const int start = lane == 0 ? wprefix : rb_sat_add(wprefix, prev);
+    // the cut: the largest list end that is still <= K_cap (ends do not decrease: this lane's last such end)
+    {
+        int run = start, cut = start <= K_cap ? start : 0;
+        for (int i = i0; i < i1; ++i) {
+            run = rb_sat_add(run, vt_count[i]);
+            if (run <= K_cap) cut = run;
+        }
+        atomicMax(&s_cut, cut);
+    }
+    __syncthreads();
+    const int cut = s_cut;
+    int run = start;
+    for (int i = i0; i < i1; ++i) {
+        const int c = vt_count[i];
+        vt_off[i] = min(run, cut);
+        run = rb_sat_add(run, c);
+        if (c > 0 && run > K_cap) atomicOr(&overflow[i / T], 1);      // (the rare path: a list without room)
+        vt_count[i] = 0;
+    }
+    // (every lane whose run ends at VT holds the grand total in `run`: they write the same value)
+    if (i1 == VT) vt_off[VT] = min(run, cut);
+}
+
+// ---------------------------------------------------------------- scatter
+__global__ void __launch_bounds__(RB_BLOCK) rb_scatter_kernel(const float* __restrict__ rec, const int2* __restrict__ meta, int J,
+                                                              int gx, int gy, int32_t* __restrict__ cursor,
+                                                              const int32_t* __restrict__ vt_off,
+                                                              unsigned long long* __restrict__ keys) {
+    const int i = blockIdx.x * RB_BLOCK + threadIdx.x;
+    const int total = meta[J].x;
+    float u = 0.f, v = 0.f, cutoff = 0.f, depth = 0.f;
+    int x0 = 0, y0 = 0, nx = 0, nt = 0, base = 0;
+    if (i < total) {
+        const float4* r4 = reinterpret_cast<const float4*>(rec + (size_t)i * REC);
+        const float4 p0 = r4[0], p2 = r4[2];
+        const int rad = __float_as_int(p2.w);
+        u = p0.x; v = p0.y; cutoff = p2.z; depth = p2.y;
+        if (rad > 0) {
+            int x1, y1;
+            tile_rect(u, v, rad, gx, gy, x0, x1, y0, y1);
+            nx = x1 - x0; nt = nx * (y1 - y0);
+        }
+        base = rb_find_job(meta, J, i) * (gx * gy);
+    }
+    const unsigned long long own = ((unsigned long long)__float_as_uint(depth) << 32) | (unsigned long long)(unsigned)i;
+    rb_walk_tiles(u, v, cutoff, x0, y0, nx, nt, gx, base, own, [&](int vt, unsigned long long key) {
+        const int lo = vt_off[vt], hi = vt_off[vt + 1];
+        if (hi > lo) {                                     // (a list behind the cut has no room: nothing is written)
+            const int pos = lo + atomicAdd(&cursor[vt], 1);
+            if (pos < hi) keys[pos] = key;
+        }
+    });
+}
+
+// ---------------------------------------------------------------- blend
+// LDS per workgroup: 257 records x 48 B + 256 mask bytes + the tile's 16 x 48 uint8 image = 13.4 KB -> eleven workgroups per CU
+// by LDS; the register count allows eight, 32 waves per CU.
+__global__ void __launch_bounds__(256) rb_blend_kernel(const float* __restrict__ rec, const int32_t* __restrict__ ids,
+                                                       const int32_t* __restrict__ tile_range, const float* __restrict__ job_cam,
+                                                       int W, int H, int gx, int T, float* __restrict__ out_f32,
+                                                       uint8_t* __restrict__ out_u8) {
+    __shared__ RecLDS recs[FB + 1];          // recs[FB]: an all-zero record (opacity 0: never blends)
+    __shared__ unsigned char s_mask[FB];
+    __shared__ unsigned char s_img[GFL_TILE][GFL_TILE * 3];
+    if (threadIdx.x == 0) {
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        recs[FB].p0 = z; recs[FB].p1 = z; recs[FB].p2 = z;
+    }
+    // (neighbouring virtual tiles -- the tiles of one job -- on one XCD: they read the same records)
+    const int vt = xcd_logical_block((int)blockIdx.x, (int)gridDim.x);
+    const int job = vt / T, tile = vt - job * T;
+    const int tx = tile % gx, ty = tile / gx;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int lx = (wave & 1) * 8 + (lane & 7), ly = (wave >> 1) * 8 + (lane >> 3);
+    const int px = tx * GFL_TILE + lx, py = ty * GFL_TILE + ly;
+    const bool inside = px < W && py < H;
+    const float fx = pixf(px), fy = pixf(py);
+    const float bg = job_cam[(size_t)job * RB_CAM + 16];
+    const int start = tile_range[2 * vt], end = tile_range[2 * vt + 1];
+    float Tr = 1.f, Tw = inside ? 1.f : 0.f, a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    for (int base = start; base < end; base += FB) {
+        if (__syncthreads_and(Tw == 0.f)) break;
+        const int idx = base + tid;
+        unsigned char m = 0;
+        if (idx < end) {
+            const int g = ids[idx];
+            const float4* r4 = reinterpret_cast<const float4*>(rec + (size_t)g * REC);
+            const float4 p0 = r4[0], p1 = r4[1], p2 = r4[2];
+            recs[tid].p0 = p0; recs[tid].p1 = p1; recs[tid].p2 = p2;
+            m = (unsigned char)block_mask(p0, p1, p2.z, tx * GFL_TILE, ty * GFL_TILE);
+        }
+        s_mask[tid] = m;
+        __syncthreads();
+        const int cnt = min(FB, end - base);
+        for (int c0 = 0; c0 < cnt && !__all(Tw == 0.f); c0 += 64) {
+            const int slot = c0 + lane;
+            unsigned long long bits = __ballot(slot < cnt && ((s_mask[slot] >> wave) & 1));
+            // four hit splats per trip (the forward blend's whole-tile walk): records fetched and alphas evaluated together, only
+            // the T recurrence is serial; the arithmetic of a pixel is that kernel's, term for term
+            while (bits) {
+                int j[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    j[k] = bits ? c0 + (int)__builtin_ctzll(bits) : FB;      // (missing splats of the last trip: the null record)
+                    bits &= bits - 1;
+                }
+                float4 q0[4], q1[4];
+                float cb[4], cd[4], al[4];
+                bool val[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    q0[k] = recs[j[k]].p0; q1[k] = recs[j[k]].p1;
+                    cb[k] = recs[j[k]].p2.x; cd[k] = recs[j[k]].p2.y;
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    float G;
+                    val[k] = splat_alpha2(q0[k], q1[k], fx, fy, al[k], G);
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float a = val[k] ? al[k] : 0.f;
+                    const float test_T = Tw * (1.f - a);
+                    const bool stop = test_T < GFL_T_MIN;
+                    const float w = stop ? 0.f : a * Tw;
+                    a0 = fmaf(q1[k].z, w, a0); a1 = fmaf(q1[k].w, w, a1); a2 = fmaf(cb[k], w, a2); a3 = fmaf(cd[k], w, a3);
+                    Tr = stop ? Tr : test_T;
+                    Tw = stop ? 0.f : test_T;
+                }
+                if (__all(Tw == 0.f)) break;
+            }
+        }
+    }
+    const float o0 = fmaf(Tr, bg, a0), o1 = fmaf(Tr, bg, a1), o2 = fmaf(Tr, bg, a2), o3 = fmaf(Tr, bg, a3);
+    const size_t plane = (size_t)H * W;
+    if (out_f32 && inside) {
+        float* o = out_f32 + (size_t)job * 4 * plane + (size_t)py * W + px;
+        o[0] = o0; o[plane] = o1; o[2 * plane] = o2; o[3 * plane] = o3;
+    }
+    if (out_u8) {
+        // Three bytes per pixel, made wide: the tile's 16 rows of up to 48 bytes are assembled in LDS (the bytes of the very
+        // floats above), then sixteen lanes per row store the row's aligned middle as dwords -- up to twelve -- and the up to
+        // three bytes before and behind it one by one (a row starts at byte 3 (py W + 16 tx) of its image: any alignment).
+        s_img[ly][lx * 3 + 0] = img_u8(o0); s_img[ly][lx * 3 + 1] = img_u8(o1); s_img[ly][lx * 3 + 2] = img_u8(o2);
+        __syncthreads();
+        const int r = tid >> 4, k = tid & 15;
+        const int ry = ty * GFL_TILE + r;
+        if (ry < H) {
+            uint8_t* p = out_u8 + ((size_t)job * plane + (size_t)ry * W + (size_t)tx * GFL_TILE) * 3;
+            const int L = 3 * min(GFL_TILE, W - tx * GFL_TILE);
+            const int head = min((int)((4u - (unsigned)((uintptr_t)p & 3u)) & 3u), L);
+            const int ndw = (L - head) >> 2, tail = L - head - 4 * ndw;
+            const unsigned char* s = s_img[r];
+            if (k < ndw) {
+                const int o = head + 4 * k;
+                const uint32_t word = (uint32_t)s[o] | ((uint32_t)s[o + 1] << 8) | ((uint32_t)s[o + 2] << 16) | ((uint32_t)s[o + 3] << 24);
+                *reinterpret_cast<uint32_t*>(p + o) = word;
+            } else if (k >= 12 && k < 15) {
+                if (k - 12 < head) p[k - 12] = s[k - 12];
+            } else if (k == 15) {
+                for (int b = 0; b < tail; ++b) p[head + 4 * ndw + b] = s[head + 4 * ndw + b];
+            }
+        }
+    }
+}
+
+struct RbWs {
+    int2* meta; float* rec; int32_t* vt_count; int32_t* vt_off; int32_t* tile_range; unsigned long long* keys; int32_t* ids;
+    size_t bytes;
+};
+// (the pair pool -- keys, ids -- comes last: what lies behind the workspace lies behind the pool)
+static RbWs rb_ws(void* base, int J, int rows_total, int K_cap, int W, int H) {
+    Arena a{(char*)base};
+    const size_t VT = (size_t)J * tile_grid(W, H).tiles();
+    RbWs w;
+    w.meta = a.take<int2>("meta", (size_t)J + 1);
+    w.rec = a.take<float>("rec", (size_t)rows_total * REC);
+    w.vt_count = a.take<int32_t>("vt_count", VT);
+    w.vt_off = a.take<int32_t>("vt_off", VT + 1);
+    w.tile_range = a.take<int32_t>("tile_range", 2 * VT);
+    w.keys = a.take<unsigned long long>("keys", (size_t)K_cap);
+    w.ids = a.take<int32_t>("ids", (size_t)K_cap);
+    w.bytes = a.off;
+    return w;
+}
+
+}  // namespace gfl
+
+using namespace gfl;
+
+extern "C" {
+
+size_t gfl_render_batch_workspace_bytes(int J, int rows_total, int K_cap, int W, int H) {
+    if (J < 0 || rows_total < 0 || K_cap <= 0 || W <= 0 || H <= 0) return 0;
+    return rb_ws(nullptr, J, rows_total, K_cap, W, H).bytes;
+}
+
+int gfl_render_batch(const float* params, int R, const int32_t* job_rows, const float* job_cam, int J, int rows_total, int W,
+                     int H, int K_cap, float* out_f32, uint8_t* out_u8, float* out_rec, int32_t* overflow, void* workspace,
+                     size_t workspace_bytes, gfl_stream_t stream) {
+    if (J < 0 || R < 0 || rows_total < 0 || W <= 0 || H <= 0 || K_cap <= 0) return GFL_ERR_INVALID;
+    if (!out_f32 && !out_u8) return GFL_ERR_INVALID;
+    if (J == 0) return GFL_OK;
+    if (!job_rows || !job_cam || !overflow || !workspace || (rows_total > 0 && !params)) return GFL_ERR_INVALID;
+    const auto [gx, gy, T] = tile_grid(W, H);
+    if ((long long)J * T > (long long)RB_VT_MAX) return GFL_ERR_INVALID;
+    if (workspace_bytes < gfl_render_batch_workspace_bytes(J, rows_total, K_cap, W, H)) return GFL_ERR_INVALID;
+    const RbWs w = rb_ws(workspace, J, rows_total, K_cap, W, H);
+    hipStream_t s = (hipStream_t)stream;
+    const int VT = J * T;
+    const int row_blocks = max(1, (rows_total + RB_BLOCK - 1) / RB_BLOCK);
+    rb_setup_kernel<<<min(1024, 1 + (VT + 4 * RB_BLOCK - 1) / (4 * RB_BLOCK)), RB_BLOCK, 0, s>>>(job_rows, J, R, rows_total, w.meta,
+                                                                                               overflow, w.vt_count, VT);
+    rb_preprocess_kernel<<<row_blocks, RB_BLOCK, 0, s>>>(params, w.meta, job_cam, J, W, H, gx, gy, w.rec, out_rec, w.vt_count);
+    rb_scan_kernel<<<1, RB_SCAN, 0, s>>>(w.vt_count, VT, T, K_cap, w.vt_off, overflow);
+    rb_scatter_kernel<<<row_blocks, RB_BLOCK, 0, s>>>(w.rec, w.meta, J, gx, gy, w.vt_count, w.vt_off, w.keys);
+    int rc = check_launch();
+    if (rc) return rc;
+    rc = gfl_tile_sort_only(w.vt_off, VT, K_cap, w.keys, w.ids, w.tile_range, stream);
+    if (rc) return rc;
+    rb_blend_kernel<<<VT, 256, 0, s>>>(w.rec, w.ids, w.tile_range, job_cam, W, H, gx, T, out_f32, out_u8);
+    return check_launch();
+}
+
+}  // extern "C"

@@ -67,13 +67,16 @@ def _poll_overflow(eng):
 
 
 def check_overflow():
-    """Blocking: raises if ANY render of the fused operator so far dropped splat-tile pairs (the operator itself looks at
+    """Blocking: raises if ANY render of the fused operator -- or any batched call (render_views / render_jobs / render_block) --
+    so far dropped splat-tile pairs (the operator itself looks at
     the flag without stopping the host: at the backward of the same render, and at the next render on the same engine).
     Call it after the last render of a program whose result matters."""
     for engines in _POOL.values():
         for eng in engines:
             eng.ovf_event = None
             eng.check_overflow()
+    for ws in _BATCH_WS.values():
+        ws.check(blocking=True)
 
 
 def _watch_overflow(eng):
@@ -233,3 +236,236 @@ def render2img_device(rendered):
 def render2img(rendered):
     """(3,H,W) float -> (H,W,3) uint8 numpy (render.py:158-166)."""
     return render2img_device(rendered).cpu().numpy()
+
+
+# ------------------------------------------------------------ batched inference rasteriser
+# gfl_render_batch (include/gflow_hip.h): many (row range, camera) jobs per library call, no backward state, uint8 written by
+# the blend.  A long job list is split into calls; each call stays under these limits (module attributes: set them before a call):
+BATCH_MAX_JOBS = 256                 # jobs per library call
+BATCH_MAX_TILES = 1 << 20            # (job, tile) pairs per call: 647 jobs of 480 x 854
+BATCH_MAX_PAIRS = 1 << 28            # splat-tile pairs of a call's pool (12 bytes apiece: 3.2 GB)
+_BATCH_WS = {}                       # (W, H, device) -> _BatchWorkspace
+
+
+def batch_k_cap(n):
+    """splat-tile pairs a job of n rows gets by default: what a pooled engine of render() has (FitEngine: capacity
+    max(2 n, 65536), K_cap max(4 M, 8 x capacity))"""
+    return max(4_000_000, 8 * max(2 * int(n), 65536))
+
+
+class _BatchWorkspace:
+    """The library workspace of the batched calls on one (W, H, device): grows, never shrinks.  ``pending``: the overflow
+    flags of earlier calls, copied to pinned memory behind each call together with an event (what _watch_overflow /
+    _poll_overflow do per engine); ``captured``: the device flags of calls that were captured into a graph (nothing can be
+    copied to the host behind a replay: check_overflow() reads them)."""
+
+    def __init__(self, dev):
+        self.dev = dev
+        self.buf = None
+        self.pending = []
+        self.captured = []
+
+    def room(self, nbytes):
+        if self.buf is None or self.buf.numel() < nbytes:
+            self.buf = torch.empty(int(nbytes), dtype=torch.uint8, device=self.dev)
+        return self.buf
+
+    def watch(self, ovf, k_cap):
+        if torch.cuda.is_current_stream_capturing():
+            self.captured.append((ovf, k_cap))
+            return
+        host = torch.empty(ovf.shape, dtype=torch.int32, pin_memory=True)
+        host.copy_(ovf, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.pending.append((ev, host, k_cap))
+
+    def check(self, blocking=False):
+        """raises if a finished (blocking: any) earlier call dropped pairs or had a row range outside its block"""
+        if torch.cuda.is_current_stream_capturing():
+            return
+        keep, bad = [], None
+        for ev, host, k_cap in self.pending:
+            if blocking:
+                ev.synchronize()
+            elif not ev.query():
+                keep.append((ev, host, k_cap))
+                continue
+            if bad is None and bool(host.any()):
+                bad = (host.clone(), k_cap)
+        self.pending = keep
+        if blocking and bad is None:
+            for ovf, k_cap in self.captured:
+                flags = ovf.cpu()
+                if bool(flags.any()):
+                    ovf.zero_()
+                    bad = (flags, k_cap)
+                    break
+        if bad is not None:
+            flags, k_cap = bad
+            jobs = torch.nonzero(flags).reshape(-1).tolist()
+            if bool((flags == 2).any()):
+                raise RuntimeError(f"gflow_amd.render: jobs {jobs} of a batched call had a row range outside the row block")
+            raise RuntimeError(f"gflow_amd.render: jobs {jobs} of a batched call lost splat-tile pairs (the call's pool of "
+                               f"K_cap={k_cap} pairs was full); raise K_cap")
+
+
+def _batch_ws(W, H, dev):
+    key = (int(W), int(H), str(dev))
+    ws = _BATCH_WS.get(key)
+    if ws is None:
+        ws = _BATCH_WS[key] = _BatchWorkspace(dev)
+    return ws
+
+
+def rows_block(gaussians):
+    """One activated splat set (dict xyz, scale, rotate, opacity, rgb) as the [N][16] float32 row block the library reads
+    (xyz | scale | unit quaternion wxyz | opacity | rgb | pad pad).  Detached."""
+    n = gaussians["xyz"].shape[0]
+    f = lambda t, c: t.detach().float().reshape(n, c)
+    xyz = f(gaussians["xyz"], 3)
+    return torch.cat([xyz, f(gaussians["scale"], 3), f(gaussians["rotate"], 4), f(gaussians["opacity"], 1),
+                      f(gaussians["rgb"], 3), torch.zeros(n, 2, dtype=torch.float32, device=xyz.device)], dim=1)
+
+
+def _job_cams(J, intr, extr, bg, dev):
+    """[J][17] = intr | extr | bg, built on the device (inside a graph capture: from the caller's tensors at every replay)"""
+    intr = intr.detach().float().to(dev).reshape(-1, 4)
+    extr = extr.detach().float().to(dev).reshape(-1, 12)
+    if intr.shape[0] == 1 and J > 1:
+        intr = intr.expand(J, 4)
+    if torch.is_tensor(bg):
+        bgc = bg.detach().float().to(dev).reshape(-1, 1)
+    elif isinstance(bg, (int, float)):
+        bgc = torch.full((J, 1), float(bg), dtype=torch.float32, device=dev)
+    else:
+        vals = [float(b) for b in bg]
+        if len(set(vals)) == 1:
+            bgc = torch.full((J, 1), vals[0], dtype=torch.float32, device=dev)
+        else:
+            bgc = torch.tensor(vals, dtype=torch.float32).reshape(-1, 1).to(dev)
+    if intr.shape[0] != J or extr.shape[0] != J or bgc.shape[0] != J:
+        raise ValueError(f"gflow_amd.render: {J} jobs, but {intr.shape[0]} intrinsics, {extr.shape[0]} extrinsics, "
+                         f"{bgc.shape[0]} backgrounds")
+    return torch.cat([intr, extr, bgc], dim=1).contiguous()
+
+
+def render_block(block, ranges, intr, extr, bg, W, H, uint8=False, records=False, K_cap=None):
+    """The batched inference rasteriser on a row block.  block: [R][16] float32 ACTIVATED rows (rows_block); ranges: J pairs
+    (first row, row count) -- they may overlap or repeat --, or (J, 2) int32 on the device; intr (4,) or (J, 4); extr
+    (J, 3, 4); bg a float, a sequence or a tensor of J.  Returns dict(rgb (J,3,H,W), depth_map (J,1,H,W)), or with
+    ``uint8`` dict(img (J,H,W,3) uint8) = render2img of the rgb planes; with ``records`` also rec (sum of counts, 12), the
+    jobs' records one after the other (uv = columns 0:2, depth = column 9).  NOT differentiable.  Nothing here waits for
+    the device; dropped pairs raise at the next batched call or in check_overflow().  ``K_cap``: pairs per library call
+    (default: batch_k_cap(longest job) x jobs of the call)."""
+    L.need_device(block)
+    lib = L.load()
+    dev = block.device
+    W, H = int(W), int(H)
+    block = block.detach()
+    if block.dtype != torch.float32 or not block.is_contiguous() or block.dim() != 2 or block.shape[1] != 16:
+        raise ValueError("gflow_amd.render: the row block is [R][16] float32, contiguous")
+    if torch.is_tensor(ranges):
+        rows_dev = ranges.to(dev).to(torch.int32).reshape(-1, 2).contiguous()
+        counts = None                        # (device values: every job may be the whole block)
+        J = rows_dev.shape[0]
+    else:
+        counts = [int(c) for _, c in ranges]
+        J = len(counts)
+        rows_dev = None
+    ws = _batch_ws(W, H, dev)
+    ws.check()
+    img = torch.empty(J, H, W, 3, dtype=torch.uint8, device=dev) if uint8 else None
+    out = None if uint8 else torch.empty(J, 4, H, W, dtype=torch.float32, device=dev)
+    R = block.shape[0]
+    per_job = [R] * J if counts is None else counts
+    rec = torch.empty(max(sum(per_job), 1), 12, dtype=torch.float32, device=dev) if records else None
+    if J:
+        cams = _job_cams(J, intr, extr, bg, dev)
+        if rows_dev is None:
+            firsts = [int(a) for a, _ in ranges]
+            if len(set(firsts)) == 1 and len(set(counts)) == 1:      # (fills: nothing is copied from the host)
+                rows_dev = torch.zeros(J, 2, dtype=torch.int32, device=dev)
+                if firsts[0]:
+                    rows_dev[:, 0].fill_(firsts[0])
+                if counts[0]:
+                    rows_dev[:, 1].fill_(counts[0])
+            else:
+                host = torch.tensor([[a, c] for a, c in zip(firsts, counts)], dtype=torch.int32).pin_memory()
+                rows_dev = host.to(dev, non_blocking=True)
+        ovf = torch.empty(J, dtype=torch.int32, device=dev)
+        T = ((W + 15) // 16) * ((H + 15) // 16)
+        k_job = batch_k_cap(max(per_job))
+        step = max(1, min(int(BATCH_MAX_JOBS), int(BATCH_MAX_TILES) // T, int(BATCH_MAX_PAIRS) // k_job))
+        k_used = 0
+        rec_at = 0
+        for a in range(0, J, step):
+            b = min(J, a + step)
+            rows_total = sum(per_job[a:b])
+            k_cap = int(K_cap) if K_cap is not None else k_job * (b - a)
+            k_used = max(k_used, k_cap)
+            buf = ws.room(lib.gfl_render_batch_workspace_bytes(b - a, rows_total, k_cap, W, H))
+            L.check(lib.gfl_render_batch(L.ptr(block), R, L.ptr(rows_dev[a:b]), L.ptr(cams[a:b]), b - a, rows_total, W, H, k_cap,
+                                         L.ptr(out[a:b]) if out is not None else None,
+                                         L.ptr(img[a:b]) if img is not None else None,
+                                         L.ptr(rec[rec_at:]) if rec is not None else None,
+                                         L.ptr(ovf[a:b]), L.ptr(buf), buf.numel(), L.stream()), "render_batch")
+            rec_at += rows_total
+        ws.watch(ovf, k_used)
+    res = {"img": img} if uint8 else {"rgb": out[:, :3], "depth_map": out[:, 3:4]}
+    if records:
+        res["rec"] = rec[:sum(per_job)]
+    return res
+
+
+def _stack_cameras(cameras):
+    """cameras: a list of dict(intr, extr) plus W, H in each (or in the first), or a dict of stacked tensors intr (V, 4) /
+    (4,), extr (V, 3, 4), W, H.  Returns intr, extr (V, 3, 4), W, H."""
+    if isinstance(cameras, dict):
+        extr = cameras["extr"]
+        return cameras["intr"], extr.reshape(-1, 3, 4), int(cameras["W"]), int(cameras["H"])
+    if not len(cameras):
+        raise ValueError("gflow_amd.render: no cameras")
+    W, H = int(cameras[0]["W"]), int(cameras[0]["H"])
+    return (torch.stack([c["intr"].detach().float().reshape(4) for c in cameras]),
+            torch.stack([c["extr"].detach().float().reshape(3, 4) for c in cameras]), W, H)
+
+
+def render_views(gaussians, cameras, bg=0.0, uint8=False, records=False, K_cap=None):
+    """ONE activated splat set (as render() takes it) from V cameras in batched library calls.  cameras: a list of
+    dict(intr, extr, W, H) or dict(intr (V,4) or (4,), extr (V,3,4), W, H).  Returns dict(rgb (V,3,H,W), depth_map
+    (V,1,H,W)); with ``uint8`` dict(img (V,H,W,3) uint8 on the device) = render2img of rgb; with ``records`` also uv (V,N,2)
+    and depth (V,N,1).  Per camera the numbers are render()'s.  NOT differentiable: inputs are detached -- render() is the
+    differentiable operator.  A call with stacked camera tensors can be captured into a graph on one stream (run it once
+    before, so that the workspace exists): a replay reads the camera tensors as they are then."""
+    intr, extr, W, H = _stack_cameras(cameras)
+    V = extr.shape[0]
+    block = rows_block(gaussians)
+    n = block.shape[0]
+    res = render_block(block, [(0, n)] * V, intr, extr, bg, W, H, uint8=uint8, records=records, K_cap=K_cap)
+    if records:
+        rec = res.pop("rec").reshape(V, n, 12)
+        res["uv"], res["depth"] = rec[:, :, 0:2], rec[:, :, 9:10]
+    return res
+
+
+def render_jobs(sets, cameras, bg=0.0, uint8=False, records=False, K_cap=None):
+    """The ragged form: a list of activated splat sets with one camera each (cameras as render_views takes them), ``bg`` a
+    float or one per job.  Returns what render_views returns, stacked over the jobs; with ``records`` uv and depth are LISTS
+    of (N_j, 2) and (N_j, 1).  NOT differentiable: inputs are detached."""
+    intr, extr, W, H = _stack_cameras(cameras)
+    if extr.shape[0] != len(sets):
+        raise ValueError(f"gflow_amd.render: {len(sets)} splat sets, {extr.shape[0]} cameras")
+    blocks = [rows_block(g) for g in sets]
+    ranges, at = [], 0
+    for b in blocks:
+        ranges.append((at, b.shape[0]))
+        at += b.shape[0]
+    dev = blocks[0].device if blocks else torch.device("cuda")
+    block = torch.cat(blocks) if blocks else torch.zeros(0, 16, dtype=torch.float32, device=dev)
+    res = render_block(block, ranges, intr, extr, bg, W, H, uint8=uint8, records=records, K_cap=K_cap)
+    if records:
+        rec = res.pop("rec")
+        res["uv"] = [rec[a:a + c, 0:2] for a, c in ranges]
+        res["depth"] = [rec[a:a + c, 9:10] for a, c in ranges]
+    return res

@@ -430,6 +430,32 @@ int gfl_render_bwd(const gfl_fit_state* st, const gfl_fit_hyper* hp, const float
  * writes d_rec -- the state's, or rows in the workspace); a second small launch over the splats reduces d_intr from them. */
 int gfl_render_bwd_cam(const gfl_fit_state* st, const gfl_fit_hyper* hp, const float* d_render, const float* d_uv,
                        const float* d_depth, float* d_params, float* d_extr, float* d_intr, gfl_stream_t stream);
+/* ---- batched inference rasteriser (additive within 312): many (row range, camera) jobs per call -----------------
+ * What viewer.py:201-228 does per displayed image and render.py:6-108 per call -- render_multiple(input_group, ["rgb", "uv",
+ * "depth", "depth_map"]) followed by render2img -- for J jobs at once, without anything a backward would need.
+ *   params   [R][16]  ACTIVATED rows, gfl_render_fwd's column layout
+ *   job_rows [J][2]   device: first row, row count (ranges may overlap or repeat)
+ *   job_cam  [J][17]  device: intr fx fy cx cy | extr 3x4 row-major | bg
+ *   rows_total        room for records: the sum of the counts must not exceed it
+ *   out_f32  [J][4][H][W] rgb planes + depth_map, or NULL;  out_u8 [J][H][W][3] = render2img of the very floats of the rgb planes,
+ *   or NULL (one of the two is required);  out_rec [sum of counts][12] records in job order (uv = cols 0:2, depth = col 9), or NULL
+ *   overflow [J]      device: 1 = the job lost splat-tile pairs, 2 = its row range leaves [0, R) or its records rows_total
+ *                     (such rows are not rendered), 0 otherwise
+ * Per job the result is gfl_render_fwd's -- same cull set, EWA, radius, tile rectangles, (tile, depth bits, id) order, alpha floor
+ * and cap, stop rule and background term, the compile-time constants above -- and a function of the job's own rows and camera
+ * only: the same bits alone, first, last or between other jobs, run after run (nothing is added in arrival order).
+ * The job tables are read on the device, nothing is read back or allocated, and the call is six launches whatever J, the counts
+ * or the data are: it can be captured into a graph on one stream, and a replay renders what the tables hold THEN.
+ * The pool of K_cap pairs is shared by the jobs and filled in (job, tile) order; a list that does not fit whole gets no room,
+ * nor does any list behind it (a cut list's survivors would depend on arrival order): jobs before the cut have the bytes of a
+ * call with enough room, jobs with a non-empty list behind it are flagged.  J == 0 succeeds and writes nothing; a job without
+ * rows, or with every row culled, is the background image.  GFL_ERR_INVALID, before anything touches a device: J, R or rows_total
+ * < 0, W, H or K_cap <= 0, both images NULL, a required pointer NULL, more than 2^28 (job, tile) pairs, a workspace smaller than
+ * gfl_render_batch_workspace_bytes (0 for arguments it rejects). */
+size_t gfl_render_batch_workspace_bytes(int J, int rows_total, int K_cap, int W, int H);
+int gfl_render_batch(const float* params, int R, const int32_t* job_rows, const float* job_cam, int J, int rows_total, int W,
+                     int H, int K_cap, float* out_f32, uint8_t* out_u8, float* out_rec, int32_t* overflow, void* workspace,
+                     size_t workspace_bytes, gfl_stream_t stream);
 /* The three snapshot images GFlow keeps every 10th iteration (trainer.py:573-582) in one call, entirely on the
  * device: rgb of the last forward, the turbo-coloured depth map and the centre blobs (render.py:76-106; both composites
  * of the same lists, the per-splat values are derived while the records are staged), each clamped, scaled by 255 and
