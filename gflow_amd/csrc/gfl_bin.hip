@@ -16,7 +16,7 @@
 
 namespace gfl {
 
-
+// (not tile_hit2 of gfl_fit.hpp: this one is compiled WITHOUT fp contract(off) -- merging them would change these kernels' bits)
 __device__ __forceinline__ bool tile_hit(float u, float v, float cutoff, int tx, int ty) {
     // exact-disc test: distance from the splat centre to the tile's pixel-centre
     // box [16tx, 16tx+15] x [16ty, 16ty+15]

@@ -43,10 +43,8 @@ __global__ void __launch_bounds__(256) blend_fwd_kernel(const float* __restrict_
     __shared__ SplatRec recs[BLEND_BATCH];
     const int tile = blockIdx.x;
     const int tx = tile % gx, ty = tile / gx;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int px = tx * GFL_TILE + (wave & 1) * 8 + (lane & 7);
-    const int py = ty * GFL_TILE + (wave >> 1) * 8 + (lane >> 3);
-    const bool inside = px < W && py < H;
+    const int tid = threadIdx.x;
+    const auto [lx, ly, px, py, inside] = tile_pixel(tx, ty, W, H);
     const float fx = pixf(px), fy = pixf(py);
     const int start = tile_range[2 * tile], end = tile_range[2 * tile + 1];
 
@@ -109,10 +107,8 @@ __global__ void __launch_bounds__(256) blend_bwd_kernel(const float* __restrict_
     __shared__ int32_t rec_id[BLEND_BATCH];
     const int tile = blockIdx.x;
     const int tx = tile % gx, ty = tile / gx;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int px = tx * GFL_TILE + (wave & 1) * 8 + (lane & 7);
-    const int py = ty * GFL_TILE + (wave >> 1) * 8 + (lane >> 3);
-    const bool inside = px < W && py < H;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const auto [lx, ly, px, py, inside] = tile_pixel(tx, ty, W, H);
     const float fx = pixf(px), fy = pixf(py);
     const int start = tile_range[2 * tile], end = tile_range[2 * tile + 1];
     const int total = end - start;

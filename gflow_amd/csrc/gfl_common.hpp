@@ -39,6 +39,16 @@ __host__ __device__ __forceinline__ float gridf(float u) {
     if constexpr (PIXEL_CENTER != 0.0f) return u - PIXEL_CENTER;
     return u;
 }
+// the pixel of the calling lane when the 256 lanes of a workgroup are the pixels of tile (tx, ty): a wave owns an 8x8 block
+struct TilePixel { int lx, ly, px, py; bool inside; };       // (lx, ly): inside the tile; inside: of the W x H image
+__device__ __forceinline__ TilePixel tile_pixel(int tx, int ty, int W, int H) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    TilePixel p;
+    p.lx = (wave & 1) * 8 + (lane & 7); p.ly = (wave >> 1) * 8 + (lane >> 3);
+    p.px = tx * GFL_TILE + p.lx; p.py = ty * GFL_TILE + p.ly;
+    p.inside = p.px < W && p.py < H;
+    return p;
+}
 // tile sort: lists longer than SORT_SPLIT_MIN keys are cut at a pivot and sorted by two workgroups; at most SORT_MAX_SPLIT
 // tiles per launch (gfl_tile_sort.hpp; the list of such tiles is the trailer of the sort's order: gfl_fused.hip build_sort_order)
 #ifndef GFL_SORT_SPLIT_MIN

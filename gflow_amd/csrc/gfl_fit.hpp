@@ -1,6 +1,6 @@
 // Fused fit iteration -- what the stage files (gfl_fit_bin / _fwd / _bwd / _splat .hip) and the host file (gfl_fit.hip)
 // share: the data layout's constants, the device functions more than one stage inlines (camera from pose, activations, the
-// culling disc, the alpha test), the argument structs of the kernels, the carved workspace, and the launchers through which
+// culling disc, a splat's walk over its tiles, the alpha test, the plain tile composite), the argument structs of the kernels, the carved workspace, and the launchers through which
 // the host file reaches a stage's kernels (a kernel is launched from the translation unit that defines it).
 //
 // The whole of gflow/trainer.py:387-558 (activations, render, losses, backward, gradient masking, Adam) is ~6-9 kernel
@@ -135,6 +135,60 @@ __device__ __forceinline__ bool tile_hit2(float u, float v, float cutoff, int tx
     return ddx * ddx + ddy * ddy <= cutoff;
 }
 
+// ------------------------------------------------------------------ a splat walks its tiles
+// The ONE walk behind every count and every key of the fit's binning (gfl_fit_bin.hip) and the batched rasteriser's
+// (gfl_render_batch.hip): a lane walks a rectangle of at most WIDE_TILES tiles itself, a larger one -- which would keep its lane,
+// and so its wave, busy for ~100 trips -- is walked by the whole wave, 64 tiles a trip.  Both halves visit a rectangle row-major
+// and call f for every tile the disc test (tile_hit2) keeps.  The halves are two calls so that a caller can put its phase mark
+// between them; fused_preprocess_bin_kernel keeps a lane walk of its own (four tiles per trip, measured there).
+
+// the sort key of a (splat, tile) pair: unique per record row, so a tile's sorted list does not depend on arrival order
+__device__ __forceinline__ unsigned long long pair_key(float depth, int row) {
+    return ((unsigned long long)__float_as_uint(depth) << 32) | (unsigned long long)(unsigned)row;
+}
+
+struct TileSpan {        // what tile_rect gives: nx x ny tiles from (x0, y0); {} = none
+    int x0, y0, nx, ny;
+    __device__ __forceinline__ int nt() const { return nx * ny; }
+};
+__device__ __forceinline__ TileSpan tile_span(float u, float v, int radius, int gx, int gy) {
+    int x0, x1, y0, y1;
+    tile_rect(u, v, radius, gx, gy, x0, x1, y0, y1);
+    return {x0, y0, x1 - x0, y1 - y0};
+}
+
+// f(tile)
+template <typename F>
+__device__ __forceinline__ void walk_tiles_lane(float u, float v, float cutoff, const TileSpan& s, int gx, F&& f) {
+    for (int ty = s.y0; ty < s.y0 + s.ny; ++ty)
+        for (int tx = s.x0; tx < s.x0 + s.nx; ++tx)
+            if (tile_hit2(u, v, cutoff, tx, ty)) f(ty * gx + tx);
+}
+
+// what the walking lanes need of the SOURCE lane beyond its geometry: the key, and (batched rasteriser) the first virtual tile
+// of the source lane's job.  A member the caller's f does not read costs nothing: its shuffle is dead code.
+struct WalkTag { unsigned long long key; int base; };
+
+// Every lane of the wave calls this; `wide` marks the lanes whose rectangle the wave walks.  f(tile, the source lane's tag)
+template <typename F>
+__device__ __forceinline__ void walk_tiles_wave(bool wide, float u, float v, float cutoff, const TileSpan& s, int gx,
+                                                const WalkTag& tag, F&& f) {
+    const int lane = threadIdx.x & 63;
+    const int nt = s.nt();
+    unsigned long long todo = __ballot(wide);
+    while (todo) {
+        const int src = (int)__builtin_ctzll(todo);
+        todo &= todo - 1;
+        const float su = __shfl(u, src), sv = __shfl(v, src), sc = __shfl(cutoff, src);
+        const int sx0 = __shfl(s.x0, src), sy0 = __shfl(s.y0, src), snx = __shfl(s.nx, src), snt = __shfl(nt, src);
+        const WalkTag stag = {__shfl(tag.key, src), __shfl(tag.base, src)};
+        for (int q = lane; q < snt; q += 64) {
+            const int tx = sx0 + q % snx, ty = sy0 + q / snx;
+            if (tile_hit2(su, sv, sc, tx, ty)) f(ty * gx + tx, stag);
+        }
+    }
+}
+
 // rows of the scale term (trainer.py:495-502): the reference's `within_index` ALIASES valid_uv_index, which is
 // narrowed in place to the still (camera-only stage) / moving (joint stage) rows at trainer.py:467-471, so
 // scale and 1/depth are both taken over: inside the image AND (unlabelled OR still / moving by stage).
@@ -249,6 +303,85 @@ __device__ __forceinline__ bool splat_alpha2(const float4& p0, const float4& p1,
     G = __expf(fminf(power, 0.f));
     alpha = fminf(GFL_ALPHA_MAX, p1.y * G);
     return (power <= 0.f) & (alpha >= GFL_ALPHA_MIN);
+}
+
+// ------------------------------------------------------------------ a workgroup composites its tile, plainly
+// The whole-tile walk without anything for a backward: 256 lanes = the tile's pixels (tile_pixel), list entries [start, end) of
+// ids staged through LDS FB at a time -- stage(g, p0, p1, p2) fills the record of entry g: as it is (rb_blend_kernel,
+// gfl_render_batch.hip) or with the unit blob substituted (center_blend_kernel, gfl_fit_snap.hip) -- then every wave takes the
+// staged records that reach its 8x8 block (block_mask) four a trip: records fetched and alphas evaluated together, only the T
+// recurrence is serial.  Leaves T and the NSUM sums of the features p1.z, p1.w, p2.x, p2.y; the caller owns the LDS arrays
+// (recs[FB + 1]: the last one is the null record written here; s_mask[FB]), which tile this is, bg and where the pixel goes.
+// The fit's forward (fused_blend_fwd_kernel, gfl_fit_fwd.hip) keeps ITS OWN copy of the four-record step on purpose: its walk
+// carries `last`, work units, checkpoints and the depth sums at a register budget that has spilled before.  A change to the
+// stop rule or to the arithmetic of a pixel is made in both.
+template <int NSUM, typename Stage>
+__device__ __forceinline__ void plain_tile_blend(const int32_t* __restrict__ ids, int start, int end, int tx, int ty, float fx,
+                                                 float fy, bool inside, RecLDS* recs, unsigned char* s_mask, Stage&& stage,
+                                                 float& T, float (&acc)[NSUM]) {
+    static_assert(NSUM == 3 || NSUM == 4, "rgb, or rgb and depth");
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    if (tid == 0) {
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        recs[FB].p0 = z; recs[FB].p1 = z; recs[FB].p2 = z;      // (opacity 0: never blends)
+    }
+    T = 1.f;
+    float Tw = inside ? 1.f : 0.f;
+#pragma unroll
+    for (int n = 0; n < NSUM; ++n) acc[n] = 0.f;
+    for (int base = start; base < end; base += FB) {
+        if (__syncthreads_and(Tw == 0.f)) break;
+        const int idx = base + tid;
+        unsigned char m = 0;
+        if (idx < end) {
+            float4 p0, p1, p2;
+            stage(ids[idx], p0, p1, p2);
+            recs[tid].p0 = p0; recs[tid].p1 = p1; recs[tid].p2 = p2;
+            m = (unsigned char)block_mask(p0, p1, p2.z, tx * GFL_TILE, ty * GFL_TILE);
+        }
+        s_mask[tid] = m;
+        __syncthreads();
+        const int cnt = min(FB, end - base);
+        for (int c0 = 0; c0 < cnt && !__all(Tw == 0.f); c0 += 64) {
+            const int slot = c0 + lane;
+            unsigned long long bits = __ballot(slot < cnt && ((s_mask[slot] >> wave) & 1));
+            while (bits) {
+                int j[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    j[k] = bits ? c0 + (int)__builtin_ctzll(bits) : FB;      // (missing records of the last trip: the null record)
+                    bits &= bits - 1;
+                }
+                float4 q0[4], q1[4];
+                float f23[4][2], al[4];
+                bool val[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    q0[k] = recs[j[k]].p0; q1[k] = recs[j[k]].p1;
+                    f23[k][0] = recs[j[k]].p2.x;
+                    f23[k][1] = NSUM > 3 ? recs[j[k]].p2.y : 0.f;
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    float G;
+                    val[k] = splat_alpha2(q0[k], q1[k], fx, fy, al[k], G);
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float a = val[k] ? al[k] : 0.f;
+                    const float test_T = Tw * (1.f - a);
+                    const bool stop = test_T < GFL_T_MIN;
+                    const float w = stop ? 0.f : a * Tw;
+                    const float feat[4] = {q1[k].z, q1[k].w, f23[k][0], f23[k][1]};
+#pragma unroll
+                    for (int n = 0; n < NSUM; ++n) acc[n] = fmaf(feat[n], w, acc[n]);
+                    T = stop ? T : test_T;
+                    Tw = stop ? 0.f : test_T;
+                }
+                if (__all(Tw == 0.f)) break;
+            }
+        }
+    }
 }
 
 // a float image value as render2img stores it (render.py:158-166): clamp to [0, 1], x 255, truncate

@@ -10,7 +10,8 @@
 // Every iteration that follows a full iteration takes "reserved tile regions" instead -- preprocess, column scan and scatter in
 // ONE launch, with one returning global atomic per (block, tile): fused_preprocess_bin_kernel below.  (The 258k atomics above
 // were one per PAIR on counters nobody had arranged; 118 blocks x 26 wave-level atomics on dense counters cost 2 us,
-// tools/atomic_probe.hip.)
+// tools/atomic_probe.hip.)  Every count and every key comes off ONE walk of a splat's tiles, walk_tiles_lane / walk_tiles_wave
+// and pair_key (gfl_fit.hpp), which the batched rasteriser shares.
 #include "gfl_fit_order.hpp"
 
 namespace gfl {
@@ -31,7 +32,7 @@ __device__ __forceinline__ void preprocess_block(const PreArgs& a, const float4 
         extr_out[8] = c.r20; extr_out[9] = c.r21; extr_out[10] = c.r22; extr_out[11] = c.t2;
     }
     float u = 0.f, v = 0.f, cutoff = 0.f;
-    int wx0 = 0, wy0 = 0, wnx = 0, wnt = 0;      // rectangle of a "wide" splat (walked by the wave below)
+    TileSpan wspan = {};                         // rectangle of a "wide" splat (walked by the wave below)
     bool in_scale_rows = false;
     Splat s = {};
     Proj p = {};
@@ -58,20 +59,13 @@ __device__ __forceinline__ void preprocess_block(const PreArgs& a, const float4 
             if (!EWA_MFMA) e = ewa_fwd(c, p.px, p.py, p.pz, cov, W, H);
             if (e.ok) {
                 const int r = ewa_radius(e);
-                int x0, x1, y0, y1;
-                tile_rect(u, v, r, gx, gy, x0, x1, y0, y1);
-                const int nt = (x1 - x0) * (y1 - y0);
-                if (nt > 0) {
+                const TileSpan span = tile_span(u, v, r, gx, gy);
+                if (span.nt() > 0) {
                     rad = r;
                     A = e.c / e.det; B = -e.b / e.det; C = e.a / e.det;
                     cutoff = alpha_cutoff(s.o, e.lam);
-                    if (nt > WIDE_TILES) {
-                        wx0 = x0; wy0 = y0; wnx = x1 - x0; wnt = nt;
-                    } else {
-                        for (int ty = y0; ty < y1; ++ty)
-                            for (int tx = x0; tx < x1; ++tx)
-                                if (tile_hit2(u, v, cutoff, tx, ty)) atomicAdd(&hist[ty * gx + tx], 1);
-                    }
+                    if (span.nt() > WIDE_TILES) wspan = span;
+                    else walk_tiles_lane(u, v, cutoff, span, gx, [&](int t) { atomicAdd(&hist[t], 1); });
                 }
             }
         }
@@ -81,7 +75,7 @@ __device__ __forceinline__ void preprocess_block(const PreArgs& a, const float4 
         r4[2] = make_float4(s.c[2], depth, cutoff, __int_as_float(rad));
         if (BINNED) { po->u = u; po->v = v; po->cutoff = cutoff; po->depth = depth; po->rad = rad; }
         in_scale_rows = a.scale_rows_mode && scale_row(u, v, W, H, own_flags, a.scale_rows_mode);
-        if (wnt > SLOT_MAX) {
+        if (const int wnt = wspan.nt(); wnt > SLOT_MAX) {
             // too many tiles for the splat's own SLOT_MAX pair rows: a run of wnt rows behind them (FitWs.wide_off)
             const int off = atomicAdd(a.pool_counter, wnt);
             a.wide_off[i] = off + wnt <= a.pool_cap ? off : -1;      // (-1: no rows -- and the lists' overflow flag: they must grow)
@@ -89,21 +83,8 @@ __device__ __forceinline__ void preprocess_block(const PreArgs& a, const float4 
         }
     }
     if (PHASES) GFL_PHASE(0, 4);
-    {
-        // splats covering many tiles: the whole wave counts their tiles, 64 at a time
-        const int lane = threadIdx.x & 63;
-        unsigned long long todo = __ballot(wnt > 0);
-        while (todo) {
-            const int src = (int)__builtin_ctzll(todo);
-            todo &= todo - 1;
-            const float su = __shfl(u, src), sv = __shfl(v, src), sc = __shfl(cutoff, src);
-            const int sx0 = __shfl(wx0, src), sy0 = __shfl(wy0, src), snx = __shfl(wnx, src), snt = __shfl(wnt, src);
-            for (int q = lane; q < snt; q += 64) {
-                const int tx = sx0 + q % snx, ty = sy0 + q / snx;
-                if (tile_hit2(su, sv, sc, tx, ty)) atomicAdd(&hist[ty * gx + tx], 1);
-            }
-        }
-    }
+    // splats covering many tiles: the whole wave counts their tiles
+    walk_tiles_wave(wspan.nt() > 0, u, v, cutoff, wspan, gx, WalkTag{}, [&](int t, const WalkTag&) { atomicAdd(&hist[t], 1); });
     if (a.scale_rows_mode) {
         // (no atomics on global memory: one partial per block, folded by every block of the backward kernel)
         const int wcnt = __popcll(__ballot(in_scale_rows));
@@ -227,15 +208,14 @@ __global__ void __launch_bounds__(RBIN_BLOCK) fused_preprocess_bin_kernel(const 
     GFL_PHASE(1, 4);
     // ---- keys (the scatter launch's walk, with the cursors above)
     const float u = o.u, v = o.v, cutoff = o.cutoff, depth = o.depth;
-    int x0 = 0, x1 = 0, y0 = 0, y1 = 0;
-    if (o.rad > 0) tile_rect(u, v, o.rad, a.gx, a.gy, x0, x1, y0, y1);
-    const int gx = a.gx, nx = x1 - x0, nt = nx * (y1 - y0);
+    const TileSpan span = o.rad > 0 ? tile_span(u, v, o.rad, a.gx, a.gy) : TileSpan{};
+    const int gx = a.gx, x0 = span.x0, y0 = span.y0, nx = span.nx, nt = span.nt();
     const bool wide = nt > WIDE_TILES;
+    const unsigned long long key = pair_key(depth, i);
     if (nt > 0 && !wide) {
-        // Four tiles per trip: the cursor's LDS add returns the key's position, and a lane that waits for one add per trip
-        // spends the walk waiting (4.3 us of the launch's 17, tools/phase_trace.py; two waves per SIMD hide nothing).  Lanes
-        // without a hit add to a cursor of their own behind the limits, so that the four adds are straight-line code.
-        const unsigned long long key = ((unsigned long long)__float_as_uint(depth) << 32) | (unsigned long long)(unsigned)i;
+        // Four tiles per trip, not walk_tiles_lane: the cursor's LDS add returns the key's position, and a lane that waits for one
+        // add per trip spends the walk waiting (4.3 us of the launch's 17, tools/phase_trace.py; two waves per SIMD hide nothing).
+        // Lanes without a hit add to a cursor of their own behind the limits, so that the four adds are straight-line code.
         const int dummy = 2 * T + (tid & 63);
         int cx = 0, cy = 0;
         for (int q0 = 0; q0 < nt; q0 += 4) {
@@ -259,23 +239,10 @@ __global__ void __launch_bounds__(RBIN_BLOCK) fused_preprocess_bin_kernel(const 
         }
     }
     GFL_PHASE(1, 5);
-    const int lane = tid & 63;
-    unsigned long long todo = __ballot(wide);
-    while (todo) {
-        const int src = (int)__builtin_ctzll(todo);
-        todo &= todo - 1;
-        const float su = __shfl(u, src), sv = __shfl(v, src), sc = __shfl(cutoff, src);
-        const int sx0 = __shfl(x0, src), sy0 = __shfl(y0, src), snx = __shfl(nx, src), snt = __shfl(nt, src);
-        const unsigned long long key =
-            ((unsigned long long)__float_as_uint(__shfl(depth, src)) << 32) | (unsigned long long)(unsigned)__shfl(i, src);
-        for (int q = lane; q < snt; q += 64) {
-            const int tx = sx0 + q % snx, ty = sy0 + q / snx;
-            if (!tile_hit2(su, sv, sc, tx, ty)) continue;
-            const int t = ty * gx + tx;
-            const int pos = atomicAdd(&hist[t], 1);
-            if (pos < lim[t]) __hip_atomic_store(&b.keys[pos], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    walk_tiles_wave(wide, u, v, cutoff, span, gx, WalkTag{key, 0}, [&](int t, const WalkTag& src) {
+        const int pos = atomicAdd(&hist[t], 1);
+        if (pos < lim[t]) __hip_atomic_store(&b.keys[pos], src.key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    });
     GFL_PHASE(1, 6);
 }
 
@@ -456,41 +423,18 @@ __global__ void __launch_bounds__(BIN_BLOCK) fused_scatter_kernel(const float* _
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     GFL_PHASE(2, 4);
 #endif
-    int x0 = 0, x1 = 0, y0 = 0, y1 = 0;
-    if (rad > 0) tile_rect(u, v, rad, gx, gy, x0, x1, y0, y1);
-    const int nx = x1 - x0, nt = nx * (y1 - y0);
-    // a splat covering many tiles would keep its lane (and so its wave) busy for ~100 trips:
-    // such splats are walked by the whole wave instead, 64 tiles at a time
-    const bool wide = nt > WIDE_TILES;
-    if (nt > 0 && !wide) {
-        const unsigned long long key = ((unsigned long long)__float_as_uint(depth) << 32) | (unsigned long long)(unsigned)i;
-        for (int ty = y0; ty < y1; ++ty)
-            for (int tx = x0; tx < x1; ++tx) {
-                if (!tile_hit2(u, v, cutoff, tx, ty)) continue;
-                const int pos = atomicAdd(&cursor[ty * gx + tx], 1);
-                // scattered 8-byte stores: write-through (sc1)
-                if (pos < K_cap) __hip_atomic_store(&keys[pos], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                else *overflow = 1;
-            }
-    }
+    const TileSpan span = rad > 0 ? tile_span(u, v, rad, gx, gy) : TileSpan{};
+    const WalkTag own = {pair_key(depth, i), 0};
+    auto put = [&](int t, const WalkTag& src) {
+        const int pos = atomicAdd(&cursor[t], 1);
+        // scattered 8-byte stores: write-through (sc1)
+        if (pos < K_cap) __hip_atomic_store(&keys[pos], src.key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else *overflow = 1;
+    };
+    const bool wide = span.nt() > WIDE_TILES;
+    if (!wide) walk_tiles_lane(u, v, cutoff, span, gx, [&](int t) { put(t, own); });
     GFL_PHASE(2, 5);
-    const int lane = threadIdx.x & 63;
-    unsigned long long todo = __ballot(wide);
-    while (todo) {
-        const int src = (int)__builtin_ctzll(todo);
-        todo &= todo - 1;
-        const float su = __shfl(u, src), sv = __shfl(v, src), sc = __shfl(cutoff, src);
-        const int sx0 = __shfl(x0, src), sy0 = __shfl(y0, src), snx = __shfl(nx, src), snt = __shfl(nt, src);
-        const unsigned long long key =
-            ((unsigned long long)__float_as_uint(__shfl(depth, src)) << 32) | (unsigned long long)(unsigned)__shfl(i, src);
-        for (int q = lane; q < snt; q += 64) {
-            const int tx = sx0 + q % snx, ty = sy0 + q / snx;
-            if (!tile_hit2(su, sv, sc, tx, ty)) continue;
-            const int pos = atomicAdd(&cursor[ty * gx + tx], 1);
-            if (pos < K_cap) __hip_atomic_store(&keys[pos], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else *overflow = 1;
-        }
-    }
+    walk_tiles_wave(wide, u, v, cutoff, span, gx, own, put);
     GFL_PHASE(2, 6);
 }
 

@@ -103,12 +103,10 @@ __device__ __forceinline__ void footprint_tile(const float* __restrict__ rec, co
                                                unsigned char* s_mask) {
     const int tx = tile % gx, ty = tile / gx;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int px = tx * GFL_TILE + (wave & 1) * 8 + (lane & 7);
-    const int py = ty * GFL_TILE + (wave >> 1) * 8 + (lane >> 3);
-    const bool inside = px < W && py < H;
+    const auto [lx, ly, px, py, inside] = tile_pixel(tx, ty, W, H);
     const float fx = pixf(px), fy = pixf(py);
     const int start = tile_range[2 * tile], end = tile_range[2 * tile + 1];
-    bool marked = !inside;                               // nothing left to find for this lane
+    bool marked = !inside;                              // nothing left to find for this lane
     for (int base = start; base < end; base += FB) {
         if (__syncthreads_and(marked)) break;
         const int idx = base + tid;
@@ -558,6 +556,7 @@ __global__ void __launch_bounds__(256, mode == 2 ? FWD_WG_PER_CU - 1 : FWD_WG_PE
             // loop control (two: 52 us; four at 72 VGPRs, six workgroups per CU: 48 us; four at the
             // 64-VGPR budget of eight workgroups spill and gain nothing; requesting the next
             // records a trip ahead was slower: LDS returns in order, the wait covers them too).
+            // (plain_tile_blend, gfl_fit.hpp, is this step without `last`, units and the DC sums: a change here goes there too.)
             while (bits) {
                 units += min((int)__popcll(bits), FWD_UNITS);
                 int j[FWD_UNITS];            // missing splats of the last trip: the null record

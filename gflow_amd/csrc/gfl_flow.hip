@@ -42,9 +42,7 @@ __global__ void __launch_bounds__(256) flow_pair_kernel(
     const int tile = blockIdx.x;
     const int tx = tile % gx, ty = tile / gx;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int px = tx * GFL_TILE + (wave & 1) * 8 + (lane & 7);
-    const int py = ty * GFL_TILE + (wave >> 1) * 8 + (lane >> 3);
-    const bool inside = px < W && py < H;
+    const auto [lx, ly, px, py, inside] = tile_pixel(tx, ty, W, H);
     const float fx = pixf(px), fy = pixf(py);
     int start = 0, end = 0;
     if (n_a > 0) {

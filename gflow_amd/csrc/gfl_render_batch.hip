@@ -6,14 +6,14 @@
 //   setup      : the jobs' row ranges become record offsets (a prefix over the jobs), the virtual tiles' counters are cleared;
 //   preprocess : one lane per (job, row): projection, covariance, EWA, the 12-float record -- the device functions and the order
 //                of preprocess_block's op_mode (gfl_fit_bin.hip), with the camera of the ROW'S JOB -- and one integer add per
-//                (splat, tile) pair into the virtual tile's counter;
+//                (splat, tile) pair into the virtual tile's counter: the fit's tile walk (walk_tiles_lane / _wave, gfl_fit.hpp);
 //   scan       : one workgroup turns the counters into list offsets in (job, tile) order, cuts the pool at K_cap and flags the
 //                jobs that lost pairs;
-//   scatter    : the lanes of the preprocess walk their tiles again and write (depth bits << 32 | record row) keys;
+//   scatter    : the lanes of the preprocess walk their tiles again and write the keys pair_key(depth, record row);
 //   tile sort  : gfl_tile_sort_only over the J * T segments (gfl_tile_sort.hpp: unique keys, so arrival order is irrelevant);
-//   blend      : a workgroup per virtual tile, lanes = pixels, a wave per 8x8 block, records staged through LDS FB at a time,
-//                four sums per pixel -- center_blend_kernel's shape (gfl_fit_snap.hip) with the true records.  No checkpoints,
-//                no n_contrib / final_T, no queues: nothing here is for a backward.
+//   blend      : a workgroup per virtual tile: the plain tile composite (plain_tile_blend, gfl_fit.hpp -- center_blend_kernel's,
+//                gfl_fit_snap.hip) over the true records, four sums per pixel.  No checkpoints, no n_contrib / final_T, no
+//                queues: nothing here is for a backward.
 //
 // Truncation.  Lists are laid out in (job, tile) order.  A list that does not fit below K_cap WHOLE gets no room at all, and
 // neither does any list behind it: which keys of a cut list survive would depend on the order the scatter's lanes arrive in,
@@ -84,35 +84,6 @@ __global__ void __launch_bounds__(RB_BLOCK) rb_setup_kernel(const int32_t* __res
 }
 
 // ---------------------------------------------------------------- preprocess
-// walks the tiles of a lane's splat (few tiles: the lane itself; many: the wave, 64 at a time) and calls f(virtual tile, the
-// splat's `own` word) for every hit
-template <typename F>
-__device__ __forceinline__ void rb_walk_tiles(float u, float v, float cutoff, int x0, int y0, int nx, int nt, int gx, int base,
-                                              unsigned long long own, F&& f) {
-    const bool wide = nt > WIDE_TILES;
-    if (nt > 0 && !wide) {
-        for (int q = 0; q < nt; ++q) {
-            const int tx = x0 + q % nx, ty = y0 + q / nx;
-            if (tile_hit2(u, v, cutoff, tx, ty)) f(base + ty * gx + tx, own);
-        }
-    }
-    const int lane = threadIdx.x & 63;
-    unsigned long long todo = __ballot(wide);
-    while (todo) {
-        const int src = (int)__builtin_ctzll(todo);
-        todo &= todo - 1;
-        const float su = __shfl(u, src), sv = __shfl(v, src), sc = __shfl(cutoff, src);
-        const int sx0 = __shfl(x0, src), sy0 = __shfl(y0, src), snx = __shfl(nx, src), snt = __shfl(nt, src);
-        const int sbase = __shfl(base, src);
-        const unsigned long long sown = ((unsigned long long)(unsigned)__shfl((int)(unsigned)(own >> 32), src) << 32) |
-                                        (unsigned long long)(unsigned)__shfl((int)(unsigned)own, src);
-        for (int q = lane; q < snt; q += 64) {
-            const int tx = sx0 + q % snx, ty = sy0 + q / snx;
-            if (tile_hit2(su, sv, sc, tx, ty)) f(sbase + ty * gx + tx, sown);
-        }
-    }
-}
-
 __global__ void __launch_bounds__(RB_BLOCK) rb_preprocess_kernel(const float* __restrict__ params, const int2* __restrict__ meta,
                                                                  const float* __restrict__ job_cam, int J, int W, int H, int gx,
                                                                  int gy, float* __restrict__ rec, float* __restrict__ out_rec,
@@ -120,7 +91,8 @@ __global__ void __launch_bounds__(RB_BLOCK) rb_preprocess_kernel(const float* __
     const int i = blockIdx.x * RB_BLOCK + threadIdx.x;
     const int total = meta[J].x;
     float u = 0.f, v = 0.f, cutoff = 0.f;
-    int x0 = 0, y0 = 0, nx = 0, nt = 0, base = 0;
+    TileSpan span = {};
+    int base = 0;                                 // the first virtual tile of the row's job
     if (i < total) {
         const int job = rb_find_job(meta, J, i);
         const int2 m = meta[job];
@@ -140,14 +112,12 @@ __global__ void __launch_bounds__(RB_BLOCK) rb_preprocess_kernel(const float* __
             const Ewa e = ewa_fwd(c, p.px, p.py, p.pz, cov, W, H);
             if (e.ok) {
                 const int r = ewa_radius(e);
-                int x1, y1;
-                tile_rect(u, v, r, gx, gy, x0, x1, y0, y1);
-                const int n = (x1 - x0) * (y1 - y0);
-                if (n > 0) {
+                const TileSpan sp = tile_span(u, v, r, gx, gy);
+                if (sp.nt() > 0) {
                     rad = r;
                     A = e.c / e.det; B = -e.b / e.det; C = e.a / e.det;
                     cutoff = alpha_cutoff(s.o, e.lam);
-                    nx = x1 - x0; nt = n;
+                    span = sp;
                 }
             }
         }
@@ -162,7 +132,10 @@ __global__ void __launch_bounds__(RB_BLOCK) rb_preprocess_kernel(const float* __
         }
     }
     // (integer adds: the counts do not depend on the order they arrive in)
-    rb_walk_tiles(u, v, cutoff, x0, y0, nx, nt, gx, base, 0ull, [&](int vt, unsigned long long) { atomicAdd(&vt_count[vt], 1); });
+    const bool wide = span.nt() > WIDE_TILES;
+    if (!wide) walk_tiles_lane(u, v, cutoff, span, gx, [&](int t) { atomicAdd(&vt_count[base + t], 1); });
+    walk_tiles_wave(wide, u, v, cutoff, span, gx, WalkTag{0ull, base},
+                    [&](int t, const WalkTag& src) { atomicAdd(&vt_count[src.base + t], 1); });
 }
 
 // ---------------------------------------------------------------- scan
@@ -221,27 +194,28 @@ __global__ void __launch_bounds__(RB_BLOCK) rb_scatter_kernel(const float* __res
     const int i = blockIdx.x * RB_BLOCK + threadIdx.x;
     const int total = meta[J].x;
     float u = 0.f, v = 0.f, cutoff = 0.f, depth = 0.f;
-    int x0 = 0, y0 = 0, nx = 0, nt = 0, base = 0;
+    TileSpan span = {};
+    int base = 0;
     if (i < total) {
         const float4* r4 = reinterpret_cast<const float4*>(rec + (size_t)i * REC);
         const float4 p0 = r4[0], p2 = r4[2];
         const int rad = __float_as_int(p2.w);
         u = p0.x; v = p0.y; cutoff = p2.z; depth = p2.y;
-        if (rad > 0) {
-            int x1, y1;
-            tile_rect(u, v, rad, gx, gy, x0, x1, y0, y1);
-            nx = x1 - x0; nt = nx * (y1 - y0);
-        }
+        if (rad > 0) span = tile_span(u, v, rad, gx, gy);
         base = rb_find_job(meta, J, i) * (gx * gy);
     }
-    const unsigned long long own = ((unsigned long long)__float_as_uint(depth) << 32) | (unsigned long long)(unsigned)i;
-    rb_walk_tiles(u, v, cutoff, x0, y0, nx, nt, gx, base, own, [&](int vt, unsigned long long key) {
+    const WalkTag own = {pair_key(depth, i), base};
+    auto put = [&](int t, const WalkTag& src) {
+        const int vt = src.base + t;
         const int lo = vt_off[vt], hi = vt_off[vt + 1];
         if (hi > lo) {                                     // (a list behind the cut has no room: nothing is written)
             const int pos = lo + atomicAdd(&cursor[vt], 1);
-            if (pos < hi) keys[pos] = key;
+            if (pos < hi) keys[pos] = src.key;
         }
-    });
+    };
+    const bool wide = span.nt() > WIDE_TILES;
+    if (!wide) walk_tiles_lane(u, v, cutoff, span, gx, [&](int t) { put(t, own); });
+    walk_tiles_wave(wide, u, v, cutoff, span, gx, own, put);
 }
 
 // ---------------------------------------------------------------- blend
@@ -251,79 +225,23 @@ __global__ void __launch_bounds__(256) rb_blend_kernel(const float* __restrict__
                                                        const int32_t* __restrict__ tile_range, const float* __restrict__ job_cam,
                                                        int W, int H, int gx, int T, float* __restrict__ out_f32,
                                                        uint8_t* __restrict__ out_u8) {
-    __shared__ RecLDS recs[FB + 1];          // recs[FB]: an all-zero record (opacity 0: never blends)
+    __shared__ RecLDS recs[FB + 1];
     __shared__ unsigned char s_mask[FB];
     __shared__ unsigned char s_img[GFL_TILE][GFL_TILE * 3];
-    if (threadIdx.x == 0) {
-        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-        recs[FB].p0 = z; recs[FB].p1 = z; recs[FB].p2 = z;
-    }
     // (neighbouring virtual tiles -- the tiles of one job -- on one XCD: they read the same records)
     const int vt = xcd_logical_block((int)blockIdx.x, (int)gridDim.x);
     const int job = vt / T, tile = vt - job * T;
     const int tx = tile % gx, ty = tile / gx;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int lx = (wave & 1) * 8 + (lane & 7), ly = (wave >> 1) * 8 + (lane >> 3);
-    const int px = tx * GFL_TILE + lx, py = ty * GFL_TILE + ly;
-    const bool inside = px < W && py < H;
-    const float fx = pixf(px), fy = pixf(py);
+    const int tid = threadIdx.x;
+    const auto [lx, ly, px, py, inside] = tile_pixel(tx, ty, W, H);
     const float bg = job_cam[(size_t)job * RB_CAM + 16];
-    const int start = tile_range[2 * vt], end = tile_range[2 * vt + 1];
-    float Tr = 1.f, Tw = inside ? 1.f : 0.f, a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    for (int base = start; base < end; base += FB) {
-        if (__syncthreads_and(Tw == 0.f)) break;
-        const int idx = base + tid;
-        unsigned char m = 0;
-        if (idx < end) {
-            const int g = ids[idx];
-            const float4* r4 = reinterpret_cast<const float4*>(rec + (size_t)g * REC);
-            const float4 p0 = r4[0], p1 = r4[1], p2 = r4[2];
-            recs[tid].p0 = p0; recs[tid].p1 = p1; recs[tid].p2 = p2;
-            m = (unsigned char)block_mask(p0, p1, p2.z, tx * GFL_TILE, ty * GFL_TILE);
-        }
-        s_mask[tid] = m;
-        __syncthreads();
-        const int cnt = min(FB, end - base);
-        for (int c0 = 0; c0 < cnt && !__all(Tw == 0.f); c0 += 64) {
-            const int slot = c0 + lane;
-            unsigned long long bits = __ballot(slot < cnt && ((s_mask[slot] >> wave) & 1));
-            // four hit splats per trip (the forward blend's whole-tile walk): records fetched and alphas evaluated together, only
-            // the T recurrence is serial; the arithmetic of a pixel is that kernel's, term for term
-            while (bits) {
-                int j[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    j[k] = bits ? c0 + (int)__builtin_ctzll(bits) : FB;      // (missing splats of the last trip: the null record)
-                    bits &= bits - 1;
-                }
-                float4 q0[4], q1[4];
-                float cb[4], cd[4], al[4];
-                bool val[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    q0[k] = recs[j[k]].p0; q1[k] = recs[j[k]].p1;
-                    cb[k] = recs[j[k]].p2.x; cd[k] = recs[j[k]].p2.y;
-                }
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    float G;
-                    val[k] = splat_alpha2(q0[k], q1[k], fx, fy, al[k], G);
-                }
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float a = val[k] ? al[k] : 0.f;
-                    const float test_T = Tw * (1.f - a);
-                    const bool stop = test_T < GFL_T_MIN;
-                    const float w = stop ? 0.f : a * Tw;
-                    a0 = fmaf(q1[k].z, w, a0); a1 = fmaf(q1[k].w, w, a1); a2 = fmaf(cb[k], w, a2); a3 = fmaf(cd[k], w, a3);
-                    Tr = stop ? Tr : test_T;
-                    Tw = stop ? 0.f : test_T;
-                }
-                if (__all(Tw == 0.f)) break;
-            }
-        }
-    }
-    const float o0 = fmaf(Tr, bg, a0), o1 = fmaf(Tr, bg, a1), o2 = fmaf(Tr, bg, a2), o3 = fmaf(Tr, bg, a3);
+    float Tr, a[4];
+    plain_tile_blend<4>(ids, tile_range[2 * vt], tile_range[2 * vt + 1], tx, ty, pixf(px), pixf(py), inside, recs, s_mask,
+                        [&](int g, float4& p0, float4& p1, float4& p2) {
+                            const float4* r4 = reinterpret_cast<const float4*>(rec + (size_t)g * REC);
+                            p0 = r4[0]; p1 = r4[1]; p2 = r4[2];
+                        }, Tr, a);
+    const float o0 = fmaf(Tr, bg, a[0]), o1 = fmaf(Tr, bg, a[1]), o2 = fmaf(Tr, bg, a[2]), o3 = fmaf(Tr, bg, a[3]);
     const size_t plane = (size_t)H * W;
     if (out_f32 && inside) {
         float* o = out_f32 + (size_t)job * 4 * plane + (size_t)py * W + px;

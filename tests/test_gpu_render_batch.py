@@ -265,6 +265,79 @@ def test_a_full_pair_pool_truncates_the_last_job_only():
     assert torch.equal(again["u8"], tight["u8"]), "a truncated job is reproducible too"
 
 
+def wide_walk_jobs():
+    """The transition scene (168 x 120, 11 x 8 tiles, 168 class rows in front of 1500 ordinary ones) under the pose of
+    tests/test_gpu_fused.py as two jobs of one call, rows (0, 1668) and (5, 163), and the float32 oracle's tile count of every
+    RECORD row of the call (job 0's rows, then job 1's)."""
+    from oracle import loss_oracle as LO
+    from tests.scenes import oracle_front_end, rect_facts, transition_scene
+    from tests.test_gpu_fused import POSE
+    extr = LO.pose_to_extr(POSE)
+    sc = transition_scene(extr=extr)
+    w, h = sc["W"], sc["H"]
+    block = _block(dict(zip(NAMES, FO.activate({k: v.float() for k, v in sc["raw"].items()}))))
+    ranges = [(0, 1668), (5, 163)]
+    cams = [_cam(sc["intr"], extr, 0.33), _cam(sc["intr"], extr, 1.0)]
+    tiles = rect_facts(oracle_front_end(sc, POSE, torch.float32), w, h)["tiles"]
+    return dict(block=block, ranges=ranges, cams=cams, w=w, h=h, tiles=torch.cat([tiles[f:f + c] for f, c in ranges]))
+
+
+def _pairs_of(rec, w, h):
+    """The (splat, tile) pairs of record rows as the kernels count them: the tiles of a row's rectangle (tile_rect) that its
+    alpha >= 1/255 disc reaches (tile_hit2) -- float32, one rounding per operation, as both are compiled."""
+    gx, gy = MO.tile_grid(w, h)
+    rad = rec[:, 11].contiguous().view(torch.int32)
+    x0, x1, y0, y1 = (t.unsqueeze(1) for t in MO.tile_rect(rec[:, 0:2], rad, w, h))
+    tx, ty = torch.arange(gx).repeat(gy).unsqueeze(0), torch.arange(gy).repeat_interleave(gx).unsqueeze(0)
+    in_rect = (rad > 0).unsqueeze(1) & (tx >= x0) & (tx < x1) & (ty >= y0) & (ty < y1)
+    tx, ty, cutoff = tx.float(), ty.float(), rec[:, 10:11]
+    gu, gv = rec[:, 0:1] - MO.PIXEL_CENTER, rec[:, 1:2] - MO.PIXEL_CENTER
+    ddx = torch.maximum(torch.maximum(tx * 16.0 - gu, gu - (tx * 16.0 + 15.0)), torch.zeros(1))
+    ddy = torch.maximum(torch.maximum(ty * 16.0 - gv, gv - (ty * 16.0 + 15.0)), torch.zeros(1))
+    return int((in_rect & (ddx * ddx + ddy * ddy <= cutoff)).sum())
+
+
+def test_rectangles_the_whole_wave_walks():
+    """Splats of more than 16 tiles are walked by their wave, 64 tiles a trip (walk_tiles_wave, gfl_fit.hpp); every other scene
+    of this file stays at 3 x 3 tiles.  A (splat, tile) pair the walk loses moves up to 256 of the 20 160 pixels by up to 0.3."""
+    wj = wide_walk_jobs()
+    block, ranges, cams, w, h, tiles = (wj[k] for k in ("block", "ranges", "cams", "w", "h", "tiles"))
+    # ---- what the scene has to hold for this test to test anything, from the oracle alone
+    assert (w, h, block.shape[0], tiles.numel()) == (168, 120, 1668, 1831)
+    assert bool((tiles == 16).any()) and bool(((tiles >= 17) & (tiles <= 32)).any()) and bool((tiles > 32).any())
+    row = torch.arange(tiles.numel())
+    wide = tiles > 16
+    assert bool((wide & (row % 64 == 0)).any()), "no wave-walked row on the first lane of a wave"
+    assert bool((wide & (row % 64 == 63)).any()), "no wave-walked row on the last lane of a wave"
+    assert int(torch.bincount(row[wide] // 64).max()) >= 2, "no wave walks two rectangles"
+    # ---- the device
+    got = run_batch(block, ranges, cams, w=w, h=h)
+    assert got["rc"] == 0 and got["overflow"].tolist() == [0, 0]
+    bits = lambda t: t.contiguous().view(torch.int32)
+    for j, ((f, c), cam) in enumerate(zip(ranges, cams)):
+        ref = _oracle(block[f:f + c], cam, w, h)
+        tag = f"render_batch, wave-walked rectangles, job {j}: "
+        close_frac(got["f32"][j, :3], ref["rgb"], 1e-4, 1e-5, bad_frac=3e-4, hard=2e-2, what=tag + "rgb")
+        close_frac(got["f32"][j, 3:4], ref["depth_map"], 1e-4, 1e-5, bad_frac=3e-4, hard=2e-2, what=tag + "depth_map")
+        rec = _rec_rows(got, ranges, j)
+        close_frac(rec[:, 0:2], ref["uv"], 1e-5, 1e-3, what=tag + "uv")
+        close_frac(rec[:, 9:10], ref["depth"], 1e-6, 1e-6, what=tag + "depth")
+        solo = run_batch(block, [ranges[j]], [cam], w=w, h=h)
+        assert solo["rc"] == 0
+        assert torch.equal(bits(solo["f32"][0]), bits(got["f32"][j])), f"job {j} alone"
+        assert torch.equal(solo["u8"][0], got["u8"][j])
+        assert torch.equal(bits(solo["rec"]), bits(rec))
+    # ---- a pair pool one pair short: the cut falls inside job 1
+    total = _pairs_of(got["rec"], w, h)
+    exact = run_batch(block, ranges, cams, w=w, h=h, K_cap=total)
+    assert exact["rc"] == 0 and exact["overflow"].tolist() == [0, 0], f"the call has more than {total} pairs"
+    tight = run_batch(block, ranges, cams, w=w, h=h, K_cap=total - 1)
+    assert tight["rc"] == 0 and tight["overflow"].tolist() == [0, 1], f"the call has fewer than {total} pairs"
+    assert torch.equal(bits(tight["f32"][0]), bits(got["f32"][0])) and torch.equal(tight["u8"][0], got["u8"][0])
+    again = run_batch(block, ranges, cams, w=w, h=h, K_cap=total - 1)
+    assert torch.equal(bits(again["f32"]), bits(tight["f32"])) and torch.equal(again["u8"], tight["u8"]), "a truncated job is reproducible too"
+
+
 def test_a_captured_call_renders_what_the_camera_tensor_holds_at_the_replay():
     import gflow_amd.render as R
     a = random_scene(3000, W, H, seed=11, sigma_px=2.5)
