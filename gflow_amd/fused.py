@@ -12,6 +12,7 @@ import ctypes
 import torch
 
 from . import _lib as L
+from .pinned import DeferredRead
 
 ROW = 16
 REC = 12
@@ -80,6 +81,87 @@ import threading as _threading
 _GRAPH_LOCK = _threading.RLock()
 
 
+class GraphCache:
+    """The captured hipGraphs of one engine.  ``live``: graph key -> graph, all captured under the state ``key`` (the bytes of the
+    two structs); ``trash``: graph sets of earlier states, waiting for ``reap``.  The only place that takes _GRAPH_LOCK."""
+
+    def __init__(self, dev):
+        self.dev, self.stream = dev, None            # (the stream graphs are captured on)
+        self.live, self.key, self.trash = {}, None, []
+
+    def __del__(self):
+        try:
+            self.retire()
+            self.reap()
+        except Exception:                            # interpreter shutdown
+            pass
+
+    def lookup(self, state_key, gkey):
+        """The graph ``gkey`` of the state ``state_key``, or None; the graphs of another state are retired."""
+        if self.key != state_key:
+            self.retire()                            # (the old graphs: destroyed once the device is done with them)
+            self.key = state_key
+        return self.live.get(gkey)
+
+    def capture(self, gkey, launch):
+        """``launch()`` captured on the side stream, as the graph ``gkey`` of the current state.
+        capture_begin / capture_end directly: the torch.cuda.graph() context manager synchronises the device,
+        runs the Python garbage collector and empties the allocator's cache on entry -- a full stop of the fit,
+        ~60 times per 8-frame clip (the graphs are re-captured whenever N or a hyper-parameter changes) -- to
+        protect allocations inside the capture; the library allocates nothing.  "thread_local": a capture
+        in one host thread must not fail because another thread (another clip on the same device,
+        fit_video.fit_clips_concurrent) reads a value back at that moment."""
+        if self.stream is None:
+            self.stream = torch.cuda.Stream(device=self.dev)
+        side, cur = self.stream, torch.cuda.current_stream()
+        with _GRAPH_LOCK:
+            gc_on = _gc.isenabled()
+            _gc.disable()                            # (a cycle collection inside the capture could destroy an old engine's graphs)
+            try:
+                g = torch.cuda.CUDAGraph()
+                side.wait_stream(cur)
+                with torch.cuda.stream(side):
+                    g.capture_begin(capture_error_mode="thread_local")
+                    try:
+                        launch()
+                    finally:
+                        g.capture_end()
+                cur.wait_stream(side)
+            finally:
+                if gc_on:
+                    _gc.enable()
+        self.live[gkey] = g
+        return g
+
+    def retire(self):
+        """The captured graphs belong to a state that has changed (new stage, new splat count).  Destroying a graph BLOCKS the
+        host until the device is idle (hipGraphExecDestroy: not just until that graph's own replays are done -- destroying
+        graphs whose event had long passed still cost the host the whole lead it had over the device, ~5 ms at the first
+        iteration of every joint stage: tools/host_lead.py, round 6).  So they are only set aside here; ``reap`` destroys
+        them where the host has just waited for the device anyway (a densification's read, a blocking look at the overflow
+        words, the end of a clip)."""
+        if self.live:
+            self.trash.append(self.live)
+            self.live = {}
+        if len(self.trash) > 256:                    # (a caller that never reaches a reaping point)
+            self.reap()
+
+    def reap(self):
+        """Destroy the graphs set aside by ``retire`` -- call where the device is idle (see there).  Under the lock,
+        never while a capture runs (_GRAPH_LOCK)."""
+        if self.trash:
+            with _GRAPH_LOCK:
+                for gs in self.trash:
+                    gs.clear()
+            self.trash = []
+
+    def clear(self):
+        """Destroy the live graphs now (the caller has drained the stream): what they point at is being replaced."""
+        with _GRAPH_LOCK:
+            self.live.clear()
+        self.key = None
+
+
 def set_profile(mask):
     """Enable the library's per-stage HIP-event timing (bit i = stage i, include/gflow_hip.h)."""
     PROFILE["mask"] = int(mask)
@@ -141,48 +223,19 @@ class FitEngine:
         self._K_grown = False          # an overflow has doubled the pair lists: _alloc never goes below that again
         self.params = self.d_rec = self._state = None
         self.want_d_rec = False        # allocate ``d_rec`` (an optional output) with the rows
-        self._graphs, self._graph_key, self._graph_trash = {}, None, []
+        self.graphs = GraphCache(self.dev)
         self._reserved_sup = (None, 0)                   # (W, H, K_cap) the library was asked about, its answer (_reserved_flag)
         self.regions_outgrown = self.pairs_grown = 0     # void iterations made up for; times the pair lists were doubled
-        self._pend_event = self._pend_host = self._ovf_event = self._ovf_host = None     # watch_pending, watch_overflow
+        self._pend, self._ovf = DeferredRead(5), DeferredRead(1)     # watch_pending, watch_overflow
         self._snap_ring = self._snap_ring_done = None    # snapshot_ring / snapshot_ring_copied
-        # the image buffer of iteration(snapshot=True), snapshot()'s workspace, the stream graphs are captured on
-        self._snap_out = self._snap_ws = self._capture_stream = None
+        self._snap_out = self._snap_ws = None            # the image buffer of iteration(snapshot=True), snapshot()'s workspace
         self._launched = False
         self._reserved_N = -1          # N of the last full iteration whose last launch reserved the next one's tile regions
-        self.busy = False              # checked out by the differentiable operator (gflow_amd.render)
         self._alloc(int(capacity))
 
-    def __del__(self):
-        try:
-            with _GRAPH_LOCK:
-                self._graphs.clear()
-                for gs in getattr(self, "_graph_trash", []):
-                    gs.clear()
-        except Exception:                            # interpreter shutdown
-            pass
-
-    def _retire_graphs(self):
-        """The captured graphs belong to a state that has changed (new stage, new splat count).  Destroying a graph BLOCKS the
-        host until the device is idle (hipGraphExecDestroy: not just until that graph's own replays are done -- destroying
-        graphs whose event had long passed still cost the host the whole lead it had over the device, ~5 ms at the first
-        iteration of every joint stage: tools/host_lead.py, round 6).  So they are only set aside here; ``reap_graphs`` destroys
-        them where the host has just waited for the device anyway (a densification's read, a blocking look at the overflow
-        words, the end of a clip)."""
-        if self._graphs:
-            self._graph_trash.append(self._graphs)
-            self._graphs = {}
-        if len(self._graph_trash) > 256:         # (a caller that never reaches a reaping point)
-            self.reap_graphs()
-
     def reap_graphs(self):
-        """Destroy the graphs set aside by ``_retire_graphs`` -- call where the device is idle (see there).  Under the lock,
-        never while a capture runs (_GRAPH_LOCK)."""
-        if self._graph_trash:
-            with _GRAPH_LOCK:
-                for gs in self._graph_trash:
-                    gs.clear()
-            self._graph_trash = []
+        """Destroy the graphs of earlier states -- call where the device is idle (GraphCache.retire)."""
+        self.graphs.reap()
 
     # ------------------------------------------------------------------ storage
     def _alloc(self, cap):
@@ -392,58 +445,20 @@ class FitEngine:
             snap_args = (L.ptr(lut("turbo", self.dev)), L.ptr(self._snap_out))
         # (reserved=False: the first iteration of the call takes the exact binning path whatever came before)
         reserved = 0 if (flags or reserved is False or snapshot) else self._reserved_flag()      # (a snapshot iteration bins exactly)
-        gkey = ("snap", count, reserved) if snapshot else (count, reserved)
+        st, hp = self.state(), self.hp
+        fn, args, what = ((self.lib.gfl_fit_iteration_snapshot, snap_args, "snapshot iteration") if snapshot else
+                          (self.lib.gfl_fit_iterations, (count, int(flags) | reserved), "fit iterations"))
+        launch = lambda: L.check(fn(ctypes.byref(st), ctypes.byref(hp), *args, L.stream()), what)     # (eager, or inside a capture)
         if use_graph and not PROFILE["mask"] and self._launched and not flags:
-            key = bytes(self.state()) + bytes(self.hp)
-            if self._graph_key != key:
-                self._retire_graphs()                # (the old graphs: destroyed once the device is done with them)
-                self._graph_key = key
-            g = self._graphs.get(gkey)
+            gkey = ("snap", count, reserved) if snapshot else (count, reserved)
+            g = self.graphs.lookup(bytes(st) + bytes(hp), gkey)
             if g is None:
-                # capture_begin / capture_end directly: the torch.cuda.graph() context manager synchronises the device,
-                # runs the Python garbage collector and empties the allocator's cache on entry -- a full stop of the fit,
-                # ~60 times per 8-frame clip (the graphs are re-captured whenever N or a hyper-parameter changes) -- to
-                # protect allocations inside the capture; the library allocates nothing.  "thread_local": a capture
-                # in one host thread must not fail because another thread (another clip on the same device,
-                # fit_video.fit_clips_concurrent) reads a value back at that moment.
-                if self._capture_stream is None:
-                    self._capture_stream = torch.cuda.Stream(device=self.dev)
-                side = self._capture_stream
-                cur = torch.cuda.current_stream()
-                st, hp = self.state(), self.hp
-                with _GRAPH_LOCK:
-                    gc_on = _gc.isenabled()
-                    _gc.disable()                    # (a cycle collection inside the capture could destroy an old engine's graphs)
-                    try:
-                        g = torch.cuda.CUDAGraph()
-                        side.wait_stream(cur)
-                        with torch.cuda.stream(side):
-                            g.capture_begin(capture_error_mode="thread_local")
-                            try:
-                                if snapshot:
-                                    L.check(self.lib.gfl_fit_iteration_snapshot(ctypes.byref(st), ctypes.byref(hp), *snap_args,
-                                                                                L.stream()), "snapshot iteration (capture)")
-                                else:
-                                    L.check(self.lib.gfl_fit_iterations(ctypes.byref(st), ctypes.byref(hp), count, reserved,
-                                                                        L.stream()), "fit iterations (capture)")
-                            finally:
-                                g.capture_end()
-                        cur.wait_stream(side)
-                    finally:
-                        if gc_on:
-                            _gc.enable()
-                self._graphs[gkey] = g
+                g = self.graphs.capture(gkey, launch)
             g.replay()
-            self._reserved_N = self.N
-            return self._snap_out if snapshot else None
-        if snapshot:
-            L.check(self.lib.gfl_fit_iteration_snapshot(ctypes.byref(self.state()), ctypes.byref(self.hp), *snap_args, L.stream()),
-                    "snapshot iteration")
         else:
-            L.check(self.lib.gfl_fit_iterations(ctypes.byref(self.state()), ctypes.byref(self.hp), count, int(flags) | reserved,
-                                                L.stream()), "fit iterations")
+            launch()
+            self._launched = True      # every kernel is loaded now: capture is safe from here on
         self._reserved_N = self.N
-        self._launched = True          # every kernel is loaded now: capture is safe from here on
         return self._snap_out if snapshot else None
 
     def snapshot(self, out=None):
@@ -515,7 +530,7 @@ class FitEngine:
 
     def check_overflow(self):
         """Blocking read of the pair-list overflow flag (sticky on the device); raises if pairs were dropped."""
-        self._ovf_event = None
+        self._ovf.drop()
         code = int(self.overflow[0].item())
         self.reap_graphs()                           # (the device is idle here)
         if code:
@@ -529,8 +544,8 @@ class FitEngine:
         fit that never overflowed would be.  The same count, without anything to grow, for iterations that were void
         because a tile outgrew its reserved region.  0: nothing happened.  (K_cap is max(4 M, 8 x capacity), ~15 x what fits
         produce: this is the rare path, but a silent or fatal one it must not be.)"""
-        self._ovf_event = None
-        self._pend_event = None        # (a blocking look supersedes an outstanding watch: its words are read and cleared here)
+        self._ovf.drop()
+        self._pend.drop()              # (a blocking look supersedes an outstanding watch: its words are read and cleared here)
         code, skipped = (int(v) for v in self.overflow[:2].tolist())                   # the host read
         self.reap_graphs()                           # (the device is idle here)
         if code == 0:
@@ -554,14 +569,12 @@ class FitEngine:
     def _double_pairs(self):
         self._K_grown = True
         self._alloc_pairs(2 * self.K_cap)
-        with _GRAPH_LOCK:
-            self._graphs.clear()
-        self._graph_key = None
+        self.graphs.clear()
         self.pairs_grown += 1
 
     def grow_pairs(self):
         """Twice the room for (splat, tile) pairs, before they run out (the caller has drained the stream)."""
-        self._pend_event = None
+        self._pend.drop()
         self._double_pairs()
 
     def _overflow_message(self, code):
@@ -578,28 +591,20 @@ class FitEngine:
         does an iteration on reserved regions -- the region-reserving workgroup of its LAST launch stores the sum of the
         tile counts there (gfl_fit_order.hpp: ``*ro.total = pairs``, ``ro.total = tile_offsets + T`` in gfl_fit.hip) -- so the
         word is at most one iteration old, whichever path ran (ADVICE r05 asked whether the reserved path leaves it stale)."""
-        if self._pend_host is None:
-            self._pend_host = torch.zeros(8, dtype=torch.int32, pin_memory=True)
-        self._pend_host[0:5].copy_(self._offsets_and_flags[self.T:self.T + 5], non_blocking=True)      # K, then the four words
-        self._pend_event = torch.cuda.Event()
-        self._pend_event.record()
+        self._pend.watch(self._offsets_and_flags[self.T:self.T + 5])       # K, then the four words
 
     def pending_ready(self):
         """False while a ``watch_pending`` copy has not landed yet (``read_pending`` would wait)."""
-        return self._pend_event is None or self._pend_event.query()
+        return self._pend.ready()
 
     def read_pending(self):
         """(code, iterations that stepped nothing, pair count) of the last ``watch_pending``; None without one."""
-        if self._pend_event is None:
-            return None
-        self._pend_event.synchronize()
-        self._pend_event = None
-        v = self._pend_host.tolist()
-        return v[1], v[2], v[0]
+        v = self._pend.read()
+        return None if v is None else (v[1], v[2], v[0])
 
     def drop_pending(self):
         """forget a ``watch_pending`` nobody has read (a new stage: the watch was the last one's)"""
-        self._pend_event = None
+        self._pend.drop()
 
     def take_pending(self):
         """The last ``watch_pending``, read.  None: there was none.  k >= 0: k iterations stepped nothing (counted, the word
@@ -624,19 +629,14 @@ class FitEngine:
         dropped pairs.  train() calls this once per frame -- a blocking read there drained the queue between two
         stages -- and fit_clip ends with the blocking check."""
         self.poll_overflow()
-        if self._ovf_host is None:
-            self._ovf_host = torch.zeros(1, dtype=torch.int32, pin_memory=True)
-        self._ovf_host.copy_(self.overflow[0:1], non_blocking=True)
-        self._ovf_event = torch.cuda.Event()
-        self._ovf_event.record()
+        self._ovf.watch(self.overflow[0:1])
 
     def poll_overflow(self):
-        ev = self._ovf_event
-        if ev is not None and ev.query():
-            self._ovf_event = None
-            if int(self._ovf_host[0]):
-                self.overflow.zero_()
-                raise RuntimeError(self._overflow_message(int(self._ovf_host[0])))
+        """raises if the last ``watch_overflow``'s copy has landed and shows dropped pairs; never waits"""
+        got = self._ovf.poll()
+        if got and got[0]:
+            self.overflow.zero_()
+            raise RuntimeError(self._overflow_message(got[0]))
 
     def loss_terms(self):
         """(loss_rgb, loss_depth) of the last backward_step as device scalars (trainer.py:460-462,485)."""

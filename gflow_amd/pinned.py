@@ -81,6 +81,47 @@ class PinnedPool:
         return out
 
 
+class DeferredRead:
+    """A few device int32 words, looked at later without stopping the host: ``watch`` copies them to page-locked memory behind
+    the work queued so far and records an event behind the copy.  The one place where this idiom exists (the overflow words of
+    FitEngine and of the batched rasteriser)."""
+
+    def __init__(self, words):
+        self.words = int(words)
+        self._host = self._event = None     # the pinned buffer (allocated by the first watch); the event of an armed watch
+
+    def watch(self, src):
+        """``src``: a device view of at most ``words`` int32, copied on the current stream; supersedes a watch nobody has read"""
+        if self._host is None:
+            self._host = torch.zeros(self.words, dtype=torch.int32, pin_memory=True)
+        self._host[:src.numel()].copy_(src, non_blocking=True)
+        self._event = torch.cuda.Event()
+        self._event.record()
+
+    armed = property(lambda self: self._event is not None)
+
+    def ready(self):
+        """False while a watched copy has not landed yet (``read`` would wait)."""
+        return self._event is None or self._event.query()
+
+    def read(self):
+        """The watched words as a list of ints (None without a watch); waits for exactly that copy -- never for work queued
+        after it -- and disarms."""
+        if self._event is None:
+            return None
+        self._event.synchronize()
+        self._event = None
+        return self._host.tolist()
+
+    def poll(self):
+        """``read`` if that would not wait, else None."""
+        return self.read() if self.ready() else None
+
+    def drop(self):
+        """forget a watch nobody has read"""
+        self._event = None
+
+
 PINNED = PinnedPool()
 _COPY_STREAMS = {}
 

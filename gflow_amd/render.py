@@ -12,58 +12,54 @@ import torch
 from . import _lib as L
 from . import msplat
 from .color import apply_float_colormap
+from .pinned import DeferredRead
 
 FUSED_TYPES = frozenset(("rgb", "uv", "depth", "depth_map"))
 USE_FUSED = True        # render_multiple routes {"rgb","uv","depth","depth_map"} requests through the fused operator
 
 # ------------------------------------------------------------ fused differentiable operator
-_POOL = {}              # (W, H, device) -> [FitEngine]; an engine is checked out from forward until backward
+_POOL = {}              # (W, H, device) -> [_Slot]; a slot's engine is checked out from forward until backward
+
+
+class _Slot:
+    """A pooled engine and what the pool keeps about it: ``busy`` / ``owner`` (the reservation token, _checkout) and ``pad2``,
+    the two zero columns that complete a parameter row."""
+
+    def __init__(self, eng):
+        self.eng, self.busy, self.owner, self.pad2 = eng, False, None, None
 
 
 def _checkout(W, H, n, dev):
-    """An engine of the pool, reserved for the caller: returns (engine, token).  The token is the reservation --
-    ``_release`` frees the engine only for the token it was checked out with, so a stale finalizer of an earlier
+    """A slot of the pool, reserved for the caller: returns (slot, token).  The token is the reservation --
+    ``_release`` frees the slot only for the token it was checked out with, so a stale finalizer of an earlier
     forward (its graph node is collected AFTER the next forward took the same engine) cannot free it under the
     forward / backward pair that owns it now."""
     from .fused import FitEngine
     key = (int(W), int(H), str(dev))
-    for eng in _POOL.setdefault(key, []):
-        if not eng.busy:
+    for slot in _POOL.setdefault(key, []):
+        if not slot.busy:
             break
     else:
-        eng = FitEngine(W, H, max(2 * n, 65536), dev)
-        eng.busy = False
-        eng.owner = None
-        eng.ovf_host = torch.zeros(1, dtype=torch.int32, pin_memory=True)
-        eng.ovf_event = None
-        _POOL[key].append(eng)
+        slot = _Slot(FitEngine(W, H, max(2 * n, 65536), dev))
+        _POOL[key].append(slot)
+    eng = slot.eng
     # the pair-list overflow flag of this engine's PREVIOUS call, copied to pinned memory behind that call: read it
     # here without waiting for the device (an overflow drops splat-tile pairs silently otherwise)
-    _poll_overflow(eng)
+    eng.poll_overflow()
     eng.ensure_capacity(n)
-    if getattr(eng, "pad2", None) is None or eng.pad2.shape[0] < eng.cap:
-        eng.pad2 = torch.zeros(eng.cap, 2, dtype=torch.float32, device=eng.dev)
+    if slot.pad2 is None or slot.pad2.shape[0] < eng.cap:
+        slot.pad2 = torch.zeros(eng.cap, 2, dtype=torch.float32, device=eng.dev)
     # the deterministic mode follows torch's switch at the time of the forward (the backward reads the same state word)
     eng.deterministic = torch.are_deterministic_algorithms_enabled()
-    eng.busy = True
-    eng.owner = object()
-    return eng, eng.owner
+    slot.busy = True
+    slot.owner = object()
+    return slot, slot.owner
 
 
-def _release(eng, token):
-    if eng.owner is token:
-        eng.owner = None
-        eng.busy = False
-
-
-def _poll_overflow(eng):
-    """raises if the copy of the flag that followed the engine's last forward has landed and shows dropped pairs"""
-    if eng.ovf_event is not None and eng.ovf_event.query():
-        eng.ovf_event = None
-        if int(eng.ovf_host[0]):
-            eng.overflow.zero_()
-            raise RuntimeError(f"gflow_amd.render: a render produced more than K_cap={eng.K_cap} splat-tile "
-                               f"pairs and dropped some; raise K_cap (FitEngine(..., K_cap=...))")
+def _release(slot, token):
+    if slot.owner is token:
+        slot.owner = None
+        slot.busy = False
 
 
 def check_overflow():
@@ -71,18 +67,11 @@ def check_overflow():
     so far dropped splat-tile pairs (the operator itself looks at
     the flag without stopping the host: at the backward of the same render, and at the next render on the same engine).
     Call it after the last render of a program whose result matters."""
-    for engines in _POOL.values():
-        for eng in engines:
-            eng.ovf_event = None
-            eng.check_overflow()
+    for slots in _POOL.values():
+        for slot in slots:
+            slot.eng.check_overflow()
     for ws in _BATCH_WS.values():
         ws.check(blocking=True)
-
-
-def _watch_overflow(eng):
-    eng.ovf_host.copy_(eng.overflow[0:1], non_blocking=True)
-    eng.ovf_event = torch.cuda.Event()
-    eng.ovf_event.record()
 
 
 class _FusedRender(torch.autograd.Function):
@@ -96,11 +85,12 @@ class _FusedRender(torch.autograd.Function):
     def forward(ctx, xyz, scale, rotate, opacity, rgb, intr, extr, bg, W, H):
         dev = xyz.device
         n = xyz.shape[0]
-        eng, token = _checkout(W, H, n, dev)
+        slot, token = _checkout(W, H, n, dev)
+        eng = slot.eng
         try:
             if n:
                 f = lambda t, c: t.detach().float().reshape(n, c)
-                torch.cat([f(xyz, 3), f(scale, 3), f(rotate, 4), f(opacity, 1), f(rgb, 3), eng.pad2[:n]], dim=1,
+                torch.cat([f(xyz, 3), f(scale, 3), f(rotate, 4), f(opacity, 1), f(rgb, 3), slot.pad2[:n]], dim=1,
                           out=eng.params[:n])
             intr_c = intr.detach().float().contiguous().reshape(4)
             extr_c = extr.detach().float().contiguous().reshape(12)
@@ -110,29 +100,29 @@ class _FusedRender(torch.autograd.Function):
             st.N, st.intr, st.extr, st.render, st.rec = n, intr_c.data_ptr(), extr_c.data_ptr(), out.data_ptr(), rec.data_ptr()
             eng.hp.bg = float(bg)
             L.check(eng.lib.gfl_render_fwd(ctypes.byref(st), ctypes.byref(eng.hp), L.stream()), "render")
-            _watch_overflow(eng)
+            eng.watch_overflow()
         except Exception:
-            _release(eng, token)
+            _release(slot, token)
             raise
         if any(ctx.needs_input_grad):
-            ctx.eng, ctx.n, ctx.keep, ctx.token = eng, n, (intr_c, extr_c, out, rec), token
+            ctx.slot, ctx.n, ctx.keep, ctx.token = slot, n, (intr_c, extr_c, out, rec), token
             ctx.intr_shape = intr.shape
             # a graph that is dropped without backward frees the engine too; backward() calls this same finalizer,
             # which runs at most once
-            ctx.fin = weakref.finalize(ctx, _release, eng, token)
+            ctx.fin = weakref.finalize(ctx, _release, slot, token)
         else:
-            _release(eng, token)
+            _release(slot, token)
         return out[:3], out[3:4], rec[:n, 0:2], rec[:n, 9:10]
 
     @staticmethod
     def backward(ctx, d_rgb, d_depth_map, d_uv, d_depth):
-        eng, n = ctx.eng, ctx.n
-        if eng.owner is not ctx.token:
+        eng, n = ctx.slot.eng, ctx.n
+        if ctx.slot.owner is not ctx.token:
             # (the tile lists, records and checkpoints of the forward live in the pooled engine, which went back to the
             # pool with the first backward)
             raise RuntimeError("gflow_amd.render: backward through the fused render operator a second time "
                                "(retain_graph) is not supported; call render() again")
-        _poll_overflow(eng)          # (the forward of this very render: by now its flag has usually reached the host)
+        eng.poll_overflow()          # (the forward of this very render: by now its flag has usually reached the host)
         dev = eng.dev
         H, W = eng.H, eng.W
         z = lambda c: torch.zeros(c, H, W, dtype=torch.float32, device=dev)
@@ -255,8 +245,8 @@ def batch_k_cap(n):
 
 class _BatchWorkspace:
     """The library workspace of the batched calls on one (W, H, device): grows, never shrinks.  ``pending``: the overflow
-    flags of earlier calls, copied to pinned memory behind each call together with an event (what _watch_overflow /
-    _poll_overflow do per engine); ``captured``: the device flags of calls that were captured into a graph (nothing can be
+    flags of earlier calls, each a watched DeferredRead with the call's K_cap (what FitEngine.watch_overflow / poll_overflow
+    do per engine); ``captured``: the device flags of calls that were captured into a graph (nothing can be
     copied to the host behind a replay: check_overflow() reads them)."""
 
     def __init__(self, dev):
@@ -274,37 +264,33 @@ class _BatchWorkspace:
         if torch.cuda.is_current_stream_capturing():
             self.captured.append((ovf, k_cap))
             return
-        host = torch.empty(ovf.shape, dtype=torch.int32, pin_memory=True)
-        host.copy_(ovf, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self.pending.append((ev, host, k_cap))
+        read = DeferredRead(ovf.numel())
+        read.watch(ovf)
+        self.pending.append((read, k_cap))
 
     def check(self, blocking=False):
         """raises if a finished (blocking: any) earlier call dropped pairs or had a row range outside its block"""
         if torch.cuda.is_current_stream_capturing():
             return
         keep, bad = [], None
-        for ev, host, k_cap in self.pending:
-            if blocking:
-                ev.synchronize()
-            elif not ev.query():
-                keep.append((ev, host, k_cap))
-                continue
-            if bad is None and bool(host.any()):
-                bad = (host.clone(), k_cap)
+        for read, k_cap in self.pending:
+            flags = read.read() if blocking else read.poll()
+            if flags is None:
+                keep.append((read, k_cap))
+            elif bad is None and any(flags):
+                bad = (flags, k_cap)
         self.pending = keep
         if blocking and bad is None:
             for ovf, k_cap in self.captured:
-                flags = ovf.cpu()
-                if bool(flags.any()):
+                flags = ovf.tolist()
+                if any(flags):
                     ovf.zero_()
                     bad = (flags, k_cap)
                     break
         if bad is not None:
             flags, k_cap = bad
-            jobs = torch.nonzero(flags).reshape(-1).tolist()
-            if bool((flags == 2).any()):
+            jobs = [j for j, f in enumerate(flags) if f]
+            if 2 in flags:
                 raise RuntimeError(f"gflow_amd.render: jobs {jobs} of a batched call had a row range outside the row block")
             raise RuntimeError(f"gflow_amd.render: jobs {jobs} of a batched call lost splat-tile pairs (the call's pool of "
                                f"K_cap={k_cap} pairs was full); raise K_cap")

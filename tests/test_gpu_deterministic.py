@@ -83,7 +83,7 @@ def test_fullsize_engines_are_bit_identical_eager_and_replayed():
         assert a.overflow.tolist()[0] == 0
         _assert_same(a, b, f"{name}: eager engine against eager engine")
         _assert_same(a, g, f"{name}: eager engine against graph replay")
-    assert g._graphs, "no graph was replayed"
+    assert g.graphs.live, "no graph was replayed"
 
 
 def test_fullsize_deterministic_iteration_matches_oracle_and_default_mode():

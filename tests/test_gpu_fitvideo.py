@@ -437,7 +437,7 @@ def test_no_watch_of_one_stage_is_read_by_the_next():
               render_parts=False, densify_interval=0)
     tr.train(iterations=30, **kw)                     # 29 is plain, 30 would be looked at
     eng = tr.engine
-    assert getattr(eng, "_pend_event", None) is None and eng.read_pending() is None
+    assert not eng._pend.armed and eng.read_pending() is None
     steps = int(eng.step.item())
     assert steps == 30
     # a watch somebody left behind (the old behaviour) must not reach the next stage's accounting

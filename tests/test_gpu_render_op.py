@@ -185,6 +185,43 @@ def test_a_stale_finalizer_cannot_free_an_engine_that_is_reserved_again():
     assert n_busy() == 0
 
 
+def test_a_pooled_render_that_drops_pairs_is_reported():
+    """A pooled engine whose pair lists are too short for the scene: render() itself never stops the host, the blocking
+    ``check_overflow()`` raises once and is clean afterwards, and without it the next render() on the same engine raises as
+    soon as the flag of the last one has reached the host."""
+    import gflow_amd.render as R
+    from gflow_amd.fused import FitEngine
+    s = to_dev(random_scene(300, 96, 80, seed=7, sigma_px=2.0))
+    dev = s["xyz"].device
+    key = (96, 80, str(dev))
+    view = lambda: R.render({k: s[k] for k in NAMES}, dict(intr=s["intr"], extr=s["extr"], W=96, H=80), 0.0)
+    saved = R._POOL.get(key)
+    try:
+        roomy = FitEngine(96, 80, 65536, dev)
+        R._POOL[key] = [R._Slot(roomy)]
+        view()
+        R.check_overflow()
+        K = roomy.K
+        assert K > 64, K
+        small = FitEngine(96, 80, 65536, dev, K_cap=64)
+        R._POOL[key] = [R._Slot(small)]
+        out = view()
+        assert out["rgb"].shape == (3, 80, 96)
+        with pytest.raises(RuntimeError, match="K_cap"):
+            R.check_overflow()
+        R.check_overflow()                                          # (reported once: the flag was cleared)
+        view()
+        torch.cuda.synchronize()
+        with pytest.raises(RuntimeError, match="K_cap"):
+            view()
+        assert not any(slot.busy for slot in R._POOL[key])
+    finally:
+        torch.cuda.synchronize()
+        R._POOL[key] = []
+        if saved is not None:
+            R._POOL[key] = saved
+
+
 def test_operator_cost_is_reported_not_asserted():
     """what the three levels of the drop-in cost at 480p / 60k -- the five msplat operators one by one
     (the one-line ``import msplat`` swap), the fused ``render`` operator, the whole fused fit iteration.  REPORTED (bench.py

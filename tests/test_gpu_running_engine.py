@@ -198,7 +198,7 @@ def test_gradients_of_a_moving_fit_whose_rows_change_their_layout_every_step(pat
             assert eng._reserved_flag() == eng.GFL_ITER_RESERVED
         res = gradient_of_next_iteration(eng, sc, img, dep, **_how(path))
         if path == "graph":
-            assert (1, eng.GFL_ITER_RESERVED) in eng._graphs
+            assert (1, eng.GFL_ITER_RESERVED) in eng.graphs.live
         now = device_rects(eng)
         sets = transition_sets(prev, now, rows, n)
         tag = f"[moving fit, {path}{', deterministic' if deterministic else ''}, iteration {it}] "

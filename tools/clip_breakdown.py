@@ -50,7 +50,7 @@ def it(self, use_graph=False, count=1, snapshot=False, **kw):
     #  count that has a graph already is timed as an iteration here)
     gkey = ("snap", count) if snapshot else (count,)
     will_capture = use_graph and self._launched and not FU.PROFILE["mask"] and (
-        self._graph_key != bytes(self.state()) + bytes(self.hp) or not any(k[:-1] == gkey for k in self._graphs))
+        self.graphs.key != bytes(self.state()) + bytes(self.hp) or not any(k[:-1] == gkey for k in self.graphs.live))
     if will_capture:
         torch.cuda.synchronize()
         t0 = time.perf_counter()

@@ -55,7 +55,7 @@ def make(self, *a, **k):
 T.SimpleGaussian.make_stepper = make
 from gflow_amd import fused as FU
 orig_it = FU.FitEngine.iteration
-orig_retire = FU.FitEngine._retire_graphs
+orig_retire = FU.GraphCache.retire
 orig_cb = torch.cuda.CUDAGraph.capture_begin
 orig_ce = torch.cuda.CUDAGraph.capture_end
 orig_rp = torch.cuda.CUDAGraph.replay
@@ -74,7 +74,7 @@ def timed(name, fn):
 
 
 FU.FitEngine.iteration = timed("FitEngine.iteration", orig_it)
-FU.FitEngine._retire_graphs = timed("  _retire_graphs", orig_retire)
+FU.GraphCache.retire = timed("  GraphCache.retire", orig_retire)
 torch.cuda.CUDAGraph.capture_begin = timed("  capture_begin", orig_cb)
 torch.cuda.CUDAGraph.capture_end = timed("  capture_end", orig_ce)
 torch.cuda.CUDAGraph.replay = timed("  replay", orig_rp)
