@@ -312,7 +312,7 @@ def fit_clip(frames, device, cfg=None, fused=True, deterministic=None, **options
 
 def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, log=None, load_extr=True, chunk=None,
                    async_snapshots=True, keep=None, cu_count=0, deterministic=None, track_queries=None, segment=False,
-                   recon=False, camera=False, flow=False, track_backward=False):
+                   recon=False, camera=False, flow=False, track_backward=False, track_vis=False):
     """fit_clip as a generator: yields after every ``chunk`` iterations of a stage (None: never) and returns the metrics
     dict of the clip (PSNR summed over its frames; with ``cfg["traj_num"]`` > 0 also ``"traj"``: the per-frame trajectory
     images and seed projections, host arrays -- what the reference's frame loop collects in
@@ -354,9 +354,22 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
     ``"flow"`` = dict(sums (T-1, 3, 6), EPE, acc_1px, acc_3px, acc_5px, coverage (T-1, 3) float64 -- per pair and class (all,
     still, moving)); ``flow="maps"`` also keeps the maps: ``maps`` (T-1, H, W, 2) float32, frame i -> i + 1 on frame i's
     grid, and ``valid`` (T-1, H, W) bool.  A one-frame clip gives empty arrays.  ``keep["record_flow_inputs"] = True``: clones
-    of each pair's kernel inputs (dicts) in ``keep["flow_inputs"]``."""
+    of each pair's kernel inputs (dicts) in ``keep["flow_inputs"]``.
+    ``track_vis`` (needs ``track_queries`` or ``cfg["traj_num"]`` > 0, else ValueError): also the reference's track overlays
+    (gflow_amd.track_vis; INTEGRATION.md, "Track overlays"): every frame's final render is kept as uint8 on the device, taken
+    where the frame's PSNR is taken, and once the clip is fitted the tracks are painted over them on the device (one
+    gfl_track_vis call per overlay, no rasterisation) and copied to the host together; the dict then has ``"track_vis"``, a
+    dict of (T, H, W, 3) uint8 arrays: with ``track_queries`` ``pred`` (the tracker's tracks and occlusion flags;
+    benchmark.py:164), with ``traj_num`` ``seeds`` (every seed, still_length = the split; the flags are
+    track_vis.seed_occlusions of the frames' hull masks, which a MoveSegRecorder collects as for ``segment``),
+    ``seeds_still`` and, when there are moving seeds, ``seeds_move`` (fit_video.py:386-392).  ``keep`` then also receives
+    ``keep["track_vis_inputs"]`` = dict(video (T, H, W, 3) uint8, masks (T, H, W) uint8 with ``traj_num``), host arrays.
+    ``track_vis`` may also be a dict name -> (tracks (T, N, 2), occluded (T, N)) of further tracks to paint over the same
+    renders, one more array each (the command line's ``gt``: benchmark.py:165)."""
     if track_backward and track_queries is None:
         raise ValueError("fit_clip(track_backward=True) needs track_queries")
+    if track_vis and track_queries is None and not int((cfg or {}).get("traj_num", DEFAULTS["traj_num"])) > 0:
+        raise ValueError("fit_clip(track_vis=True) needs track_queries or cfg['traj_num'] > 0")
     from .trainer import SimpleGaussian
     c = dict(DEFAULTS)
     c.update(cfg or {})
@@ -378,8 +391,9 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
                         device=device, seed=seed, fused=fused, deterministic=deterministic)
     tr.async_snapshots = bool(async_snapshots)       # (trainer.py: snapshots composed beside the next iterations, or behind theirs)
     tr.cu_count = int(cu_count)                      # (the caller's stream is CU-masked: fit_clips_concurrent(partition=True))
-    if segment:
+    if segment or (track_vis and int(c["traj_num"]) > 0):
         tr.seg_recorder = SG.MoveSegRecorder(len(frames), tr.H, tr.W, tr.device)
+    vis_frames = []                                  # track_vis: every frame's final render, (H, W, 3) uint8 on the device
     recon_rec = None
     if recon:
         recon_rec = QL.ReconRecorder(len(frames), tr.H, tr.W, tr.device)
@@ -518,6 +532,9 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
         psnr_sum = p.double() if psnr_sum is None else psnr_sum + p.double()
         if recon_rec is not None or cam_rec is not None:
             record_scores(i)
+        if track_vis:
+            from .render import render2img_device
+            vis_frames.append(render2img_device(tr.last_render[:3]))
         if keep is not None:
             keep["psnr"].append(p)
         if log:
@@ -531,7 +548,7 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
     end_of_frame(0)
     for i in range(1, len(frames)):
         begin_frame(tr, frames, i, load_extr)
-        if segment:
+        if tr.seg_recorder is not None:
             tr.seg_recorder.frame = i
         if c["camera_first"]:                            # fit_video.py:256-278
             yield from tr.train_steps(**stage_kwargs(c, frames, i, "camera"), **common)
@@ -583,6 +600,21 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
         out["camera"] = dict(extr=extr, **CM.evaluate(extr, gt))
     if flow_rec is not None:
         out["flow"] = flow_rec.result()               # (one copy of the (T-1, 3, 6) sums; with "maps" the maps behind it)
+    if track_vis:
+        from . import track_vis as TV
+        video = torch.stack(vis_frames)
+        pred = seeds = masks = None
+        if tracker is not None:
+            pred = (out["tracks"]["tracks"], out["tracks"]["occluded"])
+        if traj:
+            # (the hull masks are host work on a few thousand points per frame, as for ``segment``; a frame before any mask
+            #  exists has an empty one: nothing is occluded there)
+            rec = tr.seg_recorder
+            masks = out["segmentation"]["masks"] if segment else rec.masks(rec.fetch())[0]
+            seeds = (traj_out["uv"], TV.seed_occlusions(masks, traj_out["uv"]), split_interval)
+        out["track_vis"] = TV.clip_overlays(video, pred, seeds, track_vis if isinstance(track_vis, dict) else None)
+        if keep is not None:
+            keep["track_vis_inputs"] = dict(video=video.cpu().numpy(), masks=masks)
     return out
 
 
@@ -593,7 +625,7 @@ NUMERIC_KEYS = ("psnr_sum", "frames", "iterations", "rasterisations", "clips", "
 
 
 def fit_clips_concurrent(clips, device, cfg=None, seeds=None, chunk=32, partition=False, deterministic=None,
-                         track_queries=None, track_backward=False, **options):
+                         track_queries=None, track_backward=False, track_vis=False, **options):
     """Fit several clips AT THE SAME TIME on ONE device, in one host thread: every clip has its own trainer, engine and
     STREAM, and the clips take turns enqueueing ``chunk`` iterations each (fit_clip_steps), so their graph launches
     interleave on the device.  One fit leaves the chip partly idle -- its kernels are a chain of dependent launches,
@@ -611,13 +643,16 @@ def fit_clips_concurrent(clips, device, cfg=None, seeds=None, chunk=32, partitio
     ``deterministic`` (None: torch's switch): every clip's result is bit for bit that of fit_clip(..., deterministic=True)
     with the same seed -- without ``partition``, which changes the number of tile queues (include/gflow_hip.h).
     ``track_queries``: None, or one entry (fit_clip_steps' ``track_queries``, or None) per clip; ``track_backward``:
-    fit_clip_steps' for every clip that has queries (ValueError without ``track_queries``).  ``options``: fit_clip_steps'
+    fit_clip_steps' for every clip that has queries (ValueError without ``track_queries``).  ``track_vis``: fit_clip_steps',
+    for all clips, or a list with one entry per clip.  ``options``: fit_clip_steps'
     other ones, for all clips (``async_snapshots`` and ``cu_count`` are set here)."""
     n = len(clips)
     if track_queries is not None and len(track_queries) != n:
         raise ValueError("fit_clips_concurrent: track_queries needs one entry per clip")
     if track_backward and track_queries is None:
         raise ValueError("fit_clips_concurrent(track_backward=True) needs track_queries")
+    if isinstance(track_vis, (list, tuple)) and len(track_vis) != n:
+        raise ValueError("fit_clips_concurrent: a list of track_vis needs one entry per clip")
     seeds = list(range(n)) if seeds is None else seeds
     dev = torch.device(device)
     if dev.index is None:
@@ -637,7 +672,8 @@ def fit_clips_concurrent(clips, device, cfg=None, seeds=None, chunk=32, partitio
     gens = [fit_clip_steps(clips[i], dev, cfg, seed=seeds[i], chunk=chunk, async_snapshots=n == 1,
                            cu_count=shares[i][1] if shares else 0, deterministic=deterministic,
                            track_queries=None if track_queries is None else track_queries[i],
-                           track_backward=bool(track_backward) and track_queries[i] is not None, **options)
+                           track_backward=bool(track_backward) and track_queries[i] is not None,
+                           track_vis=track_vis[i] if isinstance(track_vis, (list, tuple)) else track_vis, **options)
             for i in range(n)]
     results = [None] * n
     live = list(range(n))
@@ -685,6 +721,12 @@ def main(argv=None):
                     help="with --track: the query protocol -- each track's first visible frame, or TAP-Vid's strided one "
                          "(every fifth frame where the track is visible; wants --track-backward)")
     ap.add_argument("--track-out", default=None, help="with --track: write each clip's predicted tracks to DIR/clip_<i>.npz")
+    ap.add_argument("--track-vis", default=None,
+                    help="paint the tracks over every frame's render on the device (the reference's trajectory visualiser) and "
+                         "write DIR/clip_<i>/<name>/<frame>.png: with --track `pred` and `gt` (the ground-truth tracks and "
+                         "occlusion flags), with --traj-num `seeds`, `seeds_still`, `seeds_move`")
+    ap.add_argument("--traj-num", type=int, default=0,
+                    help="trajectory seeds per clip (cfg traj_num; the reference's scripts use 100)")
     ap.add_argument("--seg", action="store_true",
                     help="keep every frame's moving-region mask and score it against the frame's move_mask with DAVIS J, F "
                          "and J&F (a \"davis\" block in the line)")
@@ -718,6 +760,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.track_backward and not args.track:
         ap.error("--track-backward needs --track")
+    if args.track_vis and not (args.track or args.traj_num > 0):
+        ap.error("--track-vis needs --track or --traj-num")
     if args.track and args.track_queries == "strided" and not args.track_backward:
         print("warning: --track-queries strided without --track-backward: every frame before a query is a miss",
               file=sys.stderr)
@@ -743,6 +787,8 @@ def main(argv=None):
             dist.init_process_group(backend="nccl", device_id=dev)
     cfg = dict(num_points=args.num_points, iterations_first=args.iterations_first,
                iterations_after=args.iterations_after, iterations_camera=args.iterations_camera)
+    if args.traj_num > 0:
+        cfg["traj_num"] = args.traj_num
     local = {k: 0.0 for k in METRIC_NAMES}
     n_clips = len(args.sequence) if args.sequence else args.clips
     # how long is every clip?  (every rank must see the same numbers: they decide who fits what)
@@ -793,16 +839,30 @@ def main(argv=None):
     order = sorted(clips, key=lambda j: (-lengths[j], j))          # (clips of similar length share the GPU)
     options = dict(track_backward=args.track_backward, deterministic=det, segment=args.seg, recon=args.recon, camera=args.camera,
                    flow=("maps" if args.flow_out else True) if args.flow else False, load_extr=not args.no_load_extr)
+
+    def vis_option(ci):
+        # --track-vis: with --track the ground truth as one more overlay, scaled to pixels like benchmark.py:151-154
+        if not args.track_vis:
+            return False
+        if ci not in gts:
+            return True
+        import numpy as np
+        pts, occ, h, w = gts[ci][:4]
+        n = len(clips[ci])
+        xy = pts[:, :n].astype(np.float32) * np.array([w, h], dtype=np.float32)
+        return dict(gt=(np.ascontiguousarray(xy.transpose(1, 0, 2)), np.ascontiguousarray(occ[:, :n].T)))
+
     results = {}
     for g0 in range(0, len(order), c):
         group = order[g0:g0 + c]
         if len(group) == 1:
             ci = group[0]
-            res = [fit_clip(clips[ci], dev, cfg, seed=ci, track_queries=queries.get(ci), **options,
+            res = [fit_clip(clips[ci], dev, cfg, seed=ci, track_queries=queries.get(ci), track_vis=vis_option(ci), **options,
                             log=(lambda s, ci=ci: print(f"[rank {rank} clip {ci}] {s}")) if args.verbose else None)]
         else:
             res = fit_clips_concurrent([clips[ci] for ci in group], dev, cfg, seeds=group,
-                                       track_queries=[queries.get(ci) for ci in group] if args.track else None, **options)
+                                       track_queries=[queries.get(ci) for ci in group] if args.track else None,
+                                       track_vis=[vis_option(ci) for ci in group], **options)
         for ci, m in zip(group, res):
             for k in METRIC_NAMES:
                 local[k] += m[k]
@@ -822,6 +882,11 @@ def main(argv=None):
             os.makedirs(args.track_out, exist_ok=True)
             for ci, p in preds.items():
                 np.savez(os.path.join(args.track_out, f"clip_{ci}.npz"), queries=queries[ci], **p)
+    if args.track_vis:
+        from . import track_vis as TV
+        for ci, vis in of("track_vis").items():
+            for name, imgs in vis.items():
+                TV.write_frames(imgs, os.path.join(args.track_vis, f"clip_{ci}", name))
     if args.seg:
         out["davis"] = reduce_davis(of("segmentation"), *over_ranks)
         if args.seg_out:

@@ -737,6 +737,42 @@ int gfl_epi_mask(const float* flow, int W, int H, const double* F, double thresh
 int gfl_flow_occlusion(const float* fwd, const float* bwd, int n_pairs, int W, int H, float alpha, float beta,
                        float* diff_fwd, float* diff_bwd, uint8_t* occ_fwd, uint8_t* occ_bwd, gfl_stream_t stream);
 
+/* ---- track overlays (additive within 312; gflow_amd/track_vis.py, INTEGRATION.md "Track overlays") ----------------------
+ * The reference's trajectory visualiser (gflow/utils/traj_visualizer.py: TrajVisualizer.visualize with mode "rainbow",
+ * linewidth 2, tracks_leave_trace -1, pad_value 0, query_frame 0, no segm_mask, gt_tracks or visibility) for all T frames of
+ * a clip in one call: every track's polyline up to the frame, a disc where its point is visible, a cross where it is occluded.
+ *   video, out [T][H][W][3] uint8 (they may not overlap);  tracks [T][N][2] float32 (x, y);  occluded [T][N] uint8 (nonzero =
+ *   occluded);  lut [256][3] float32 = the gist_rainbow table;  overflow [1] int32 on the device, WRITTEN by every call with T > 0.
+ * Coordinates: c = (int)clamp(v, -2^20, 2^20), truncated toward zero (the reference's .long()); a NaN gives -2^20, so every
+ *   non-finite coordinate lies outside the image.  A point is USABLE when 0 <= x < W, 0 <= y < H, x != 0 and y != 0 (the
+ *   reference's coord[0] != 0 and coord[1] != 0: it hides the zero rows a track has before its query frame).
+ * Colours: byte c of track n = trunc(255 * lut[idx][c]) -- the float32 entry times 255 in float64, which is exact --,
+ *   idx = min(int(v * 256), 255), v = (y0[n] - ymin) / (ymax - ymin) over the integer y of frame 0 (every track, usable or not),
+ *   v = 0 when ymax == ymin.  With 0 < still_length < N the tracks still_length .. N-1 take ymin, ymax over themselves.  (The
+ *   reference compares still_length with T there, traj_visualizer.py:222, which makes the colours depend on the clip's length.)
+ * Frame t, in this order, later paint over earlier paint:
+ *   1. for s = 0 .. t-1 (outer), i = 0 .. N-1 (inner): the segment tracks[s][i] -> tracks[s+1][i], width 2, drawn only if both
+ *      ends are inside the image and its first end is usable;
+ *   2. for i = 0 .. N-1: the marker at tracks[t][i] if that point is usable -- occluded: a cross, the segments (x-4, y) ->
+ *      (x+4, y) and (x, y-4) -> (x, y+4), width 4; visible: the filled disc dx^2 + dy^2 <= 4^2 + 2.
+ * Coverage, exact in integers: pixel p is on the segment (a, b, w), with d = b - a, when 0 <= (p-a).d <= d.d and
+ *   4 cross(p-a, d)^2 <= w^2 (d.d), the squares in 64 bits; for a == b the segment is the single pixel a.  (Against PIL's
+ *   ImageDraw.line / ellipse: each pixel set lies within one pixel of the other; the disc is PIL's exactly.)
+ * Paint is opaque, so a pixel has the colour of the covering primitive with the highest paint index -- segment (s, i): s N + i,
+ * marker i: (T-1) N + i -- or the video's: that is what is computed, and the result does not depend on the order in which a
+ * list was filled: the same bits run after run, in every mode.
+ * The clip's segments are binned ONCE into the 16 x 16 tiles their bounding box, grown by the width, touches; frame t takes the
+ * entries with s < t of a tile's list.  The pool holds K_cap (segment, tile) pairs: a clip that needs more raises overflow[0] = 1
+ * and its `out` is the video with the markers only, no traces at all; otherwise overflow[0] = 0.  The markers are not binned.
+ * One memset and six launches whatever the data; nothing is read back or allocated: the call can be captured into a graph.
+ * T == 0 succeeds and writes nothing; N == 0 copies the video.  GFL_ERR_INVALID, before anything touches a device: T or N < 0,
+ * W, H or K_cap <= 0, W or H > 16384 (the products above then fit), T N >= 2^31, a NULL video, lut, out, overflow or workspace,
+ * NULL tracks or occluded with T N > 0, workspace_bytes < gfl_track_vis_workspace_bytes (0 for arguments it rejects). */
+size_t gfl_track_vis_workspace_bytes(int T, int N, int W, int H, int K_cap);
+int gfl_track_vis(const uint8_t* video, const float* tracks, const uint8_t* occluded, int T, int N, int W, int H,
+                  int still_length, const float* lut, int K_cap, uint8_t* out, int32_t* overflow, void* workspace,
+                  size_t workspace_bytes, gfl_stream_t stream);
+
 /* sizeof(gfl_fit_state), sizeof(gfl_fit_hyper): lets an FFI binding verify its struct mirrors */
 int gfl_abi_sizes(int* sizeof_fit_state, int* sizeof_fit_hyper);
 
