@@ -54,7 +54,8 @@ def test_scan_workspace_is_one_double_per_chunk():
     assert lib.gfl_scan_f64(None, 0, None, None, 0, None) == 0
 
 
-def test_entry_points_take_deterministic():
+def test_entry_points_take_deterministic(monkeypatch, capsys):
+    from gflow_amd import fit_video as FV
     from gflow_amd.fit_video import fit_clip, fit_clip_steps, fit_clips_concurrent, main
     from gflow_amd.fused import FitEngine
     from gflow_amd.trainer import SimpleGaussian
@@ -62,7 +63,16 @@ def test_entry_points_take_deterministic():
         p = inspect.signature(fn).parameters["deterministic"]
         assert p.default is None, fn
     assert inspect.signature(FitEngine.__init__).parameters["deterministic"].default is False
-    assert "--deterministic" in inspect.getsource(main)
+    # the command line: the parser has the switch (off by default), and main hands it to the fit as deterministic=True / None
+    assert FV._parser().parse_args([]).deterministic is False and FV._parser().parse_args(["--deterministic"]).deterministic is True
+    seen = []
+    monkeypatch.setattr(FV, "_ranks", lambda: (0, 1, torch.device("cpu"), None, (None, torch.device("cpu"))))
+    monkeypatch.setattr(FV, "_load_clips", lambda args, mine, lengths, dev: {ci: [{}] for ci in mine})
+    monkeypatch.setattr(FV, "fit_clip", lambda frames, dev, cfg, **kw: seen.append(kw["deterministic"]) or dict.fromkeys(FV.METRIC_NAMES, 0.0))
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a: None)
+    main(["--deterministic"])
+    main([])
+    assert seen == [True, None] and capsys.readouterr().out.count('"psnr_sum"') == 2
 
 
 def test_none_follows_torchs_switch():

@@ -50,6 +50,26 @@ def test_every_output_on_equals_each_output_alone():
         assert out["camera"][k] == alone["camera"][k] and out["camera"][k] is not None, k
 
 
+def test_overlays_and_backward_tracks_on_top_of_every_output():
+    """The overlays and backward tracking beside every other output: the fit does not notice them (the overlays rasterise
+    nothing, backward tracking reads the shared forward: ``rasterisations`` is equal), the tracks are those of the fit with
+    nothing else on, and the overlays have equal bytes whether the seeds' hull masks come from ``out["segmentation"]``
+    (``segment=True``) or from the recorder the overlays asked for themselves."""
+    all_on = _fit(traj=True, q=True, track_backward=True, track_vis=True, segment=True, recon=True, camera=True, flow=True)
+    base = _fit(traj=True, q=True, track_backward=True)
+    alone = _fit(traj=True, q=True, track_backward=True, track_vis=True)
+    SF.assert_same_fit(*all_on, *base)
+    tracks, tracks_alone = all_on[0]["tracks"], alone[0]["tracks"]
+    assert sorted(tracks) == sorted(tracks_alone) and "back_anchor" in tracks
+    for k in tracks:
+        np.testing.assert_array_equal(tracks[k], tracks_alone[k], err_msg=k)
+    vis, vis_alone = all_on[0]["track_vis"], alone[0]["track_vis"]
+    assert sorted(vis) == sorted(vis_alone) and {"pred", "seeds", "seeds_still"} <= set(vis)
+    for k in vis:
+        assert vis[k].dtype == np.uint8 and vis[k].shape == vis_alone[k].shape == (N_FRAMES, SF.H, SF.W, 3), k
+        assert vis[k].tobytes() == vis_alone[k].tobytes(), k
+
+
 # one forward per frame on the fused path, shared by the tracker and the flow recorder; on the operator path each of
 # them renders for itself
 @pytest.mark.parametrize("fused,outputs,forwards", [(True, dict(q=True, flow=True), N_FRAMES), (True, dict(q=True), N_FRAMES),

@@ -2,7 +2,7 @@
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from gflow_amd import synthetic as S, fit_video as FV
+from gflow_amd import synthetic as S, fit_video as FV, clip_fit as CF
 import gflow_amd.trainer as T
 
 n_frames = int(sys.argv[1]) if len(sys.argv) > 1 else 4
@@ -20,7 +20,7 @@ def timed(name, fn):
     return w
 
 
-FV.select_traj_seeds = timed("select_traj_seeds", FV.select_traj_seeds)
+CF.select_traj_seeds = timed("select_traj_seeds", CF.select_traj_seeds)      # (where ClipFit.steps looks it up)
 T.SimpleGaussian.eval_trajectories = timed("eval_trajectories", T.SimpleGaussian.eval_trajectories)
 T.SimpleGaussian._render_scene_fused = timed("_render_scene_fused", T.SimpleGaussian._render_scene_fused)
 import gflow_amd.hull as Hh
