@@ -105,7 +105,9 @@ __device__ __forceinline__ int xcd_logical_block(int b, int nb) {
     return x * q + min(x, r) + i;
 }
 
-// Reduce-scatter of ten per-lane values over the wave (blend backward: five conic/centre moments, do, df0..3).
+// Reduce-scatter of N per-lane values over the wave (blend backward): N = 10, the five conic/centre moments, do, df0..3 of the
+// first frame; N = 7, later frames, whose colours are frozen (trainer.py:537-540) -- the moments, the opacity's and the depth
+// feature's gradient; N = 6, the camera-only stage -- nobody reads the opacity / colour gradients of frozen splats.
 // gfx950's v_permlane32_swap / v_permlane16_swap exchange half-waves / rows between two
 // registers, so "swap + add" halves the number of live values while summing lane pairs:
 //   stage 1  10 -> 5 values (lanes i, i+32),  stage 2  5 -> 3 values (rows 2k, 2k+1),
@@ -114,7 +116,10 @@ __device__ __forceinline__ int xcd_logical_block(int b, int nb) {
 // Afterwards, in row r = (hi, odd) = (lane>>5, (lane>>4)&1) every lane holds
 //   x0 = sum of component 2*odd + hi,  x1 = sum of component 4 + 2*odd + hi,
 //   x2 = sum of component 8 + hi (even rows only).
-// Returns the value this lane ends up with; reduce_scatter10_component(lane) says which component it is.
+// Six and seven values take eight slots {c0 .. c6, 0}: 8 -> 4 -> 2 values (six: 6 -> 3 -> 2), then the two folded over the 16
+// lanes of a row: 16 / 18 VALU ops.  Afterwards lanes with bit 0 clear hold component 2 * odd + hi, lanes with bit 0 set
+// component 4 + hi in even rows and (seven) component 6 in row (hi = 0, odd = 1).
+// Returns the value this lane ends up with; reduce_scatter_component<N>(lane) says which component it is.
 // NOTE (ROCm 7.2 hipcc): __builtin_amdgcn_permlane{16,32}_swap returns the updated vdst in BOTH
 // elements of its result (verified on hardware), so the swaps are issued as inline asm; the
 // leading s_nop covers the VALU-write -> permlane-read hazard that hipcc does not pad inside asm.
@@ -125,140 +130,96 @@ __device__ __forceinline__ void permlane16_swap(float& a, float& b) {
     asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
 }
 
-// five (three) independent swaps behind ONE hazard nop: the operands of all of them are written
+// five (four, three, two) independent swaps behind ONE hazard nop: the operands of all of them are written
 // before the block, and no swap reads what another one wrote
-__device__ __forceinline__ void permlane32_swap_x5(float (&a)[5], float (&b)[5]) {
+__device__ __forceinline__ void permlane32_swap(float (&a)[5], float (&b)[5]) {
     asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %5\n\tv_permlane32_swap_b32 %1, %6\n\tv_permlane32_swap_b32 %2, %7\n\t"
         "v_permlane32_swap_b32 %3, %8\n\tv_permlane32_swap_b32 %4, %9"
         : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]), "+v"(b[4]));
 }
-__device__ __forceinline__ void permlane16_swap_x3(float (&a)[3], float (&b)[3]) {
-    asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %3\n\tv_permlane16_swap_b32 %1, %4\n\tv_permlane16_swap_b32 %2, %5"
-        : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]));
-}
-
-__device__ __forceinline__ float wave_reduce_scatter10(const float (&v)[10], int lane) {
-    float w[5];
-    {
-        float a[5] = {v[0], v[2], v[4], v[6], v[8]}, b[5] = {v[1], v[3], v[5], v[7], v[9]};
-        permlane32_swap_x5(a, b);     // a = {a_lo, b_lo}, b = {a_hi, b_hi}
-#pragma unroll
-        for (int m = 0; m < 5; ++m) w[m] = a[m] + b[m];   // lanes 0-31: component 2m, lanes 32-63: component 2m+1
-    }
-    float x[3];
-    {
-        float a[3] = {w[0], w[2], w[4]}, b[3] = {w[1], w[3], 0.f};
-        permlane16_swap_x3(a, b);     // a = {a_r0, b_r0, a_r2, b_r2}, b = {a_r1, b_r1, a_r3, b_r3}
-        x[0] = a[0] + b[0];
-        x[1] = a[1] + b[1];
-        x[2] = a[2] + b[2];
-    }
-    // stage 3: the three values of a 16-lane row.  Instead of three independent 4-step reductions
-    // (12 DPP adds) the values are folded onto lane classes on the way: after the xor-1 step the
-    // even lanes carry x0 and the odd lanes x1, after the xor-2 step lanes with bit 1 set carry x2;
-    // two rotations by 4 and 8 lanes (which keep the low two lane bits) finish the sums: 9 ops.
-#define GFL_DPP(val, ctrl) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, (val)), ctrl, 0xF, 0xF, true))
-    const bool b0 = lane & 1, b1 = lane & 2;
-    const float keep01 = b0 ? x[1] : x[0], send01 = b0 ? x[0] : x[1];
-    const float y = keep01 + GFL_DPP(send01, 0xB1);          // quad_perm [1,0,3,2]
-    const float z = x[2] + GFL_DPP(x[2], 0xB1);
-    const float keep = b1 ? z : y, send = b1 ? y : z;
-    float t = keep + GFL_DPP(send, 0x4E);                    // quad_perm [2,3,0,1]
-    t += GFL_DPP(t, 0x124);                                  // row_ror:4
-    t += GFL_DPP(t, 0x128);                                  // row_ror:8
-#undef GFL_DPP
-    // lane & 3 == 0: x0 total, == 1: x1 total, >= 2: x2 total
-    return t;
-}
-
-// which of the ten components the value returned to this lane belongs to (-1: a duplicate, not to
-// be used).  Depends on the lane only: callers evaluate it ONCE, outside their loops (inside, the
-// compiler turned the nested selects into a dozen exec-mask instructions per call).
-__device__ __forceinline__ int reduce_scatter10_component(int lane) {
-    const int hi = lane >> 5, odd = (lane >> 4) & 1, sel = lane & 15;
-    return sel == 0 ? 2 * odd + hi : (sel == 1 ? 4 + 2 * odd + hi : ((sel == 2 && odd == 0) ? 8 + hi : -1));
-}
-
-// The same for SIX values (camera-only stage of the backward blend: the five moments and the depth feature's gradient --
-// nobody reads the opacity / colour gradients of frozen splats): 6 -> 3 -> 2 values, then the two folded over the 16 lanes
-// of a row: 16 VALU ops instead of 27.  v = {c0, c1, c2, c3, c4, c5}; afterwards, in row (hi, odd), lanes with bit 0
-// clear hold the sum of component 2 * odd + hi, lanes with bit 0 set the sum of component 4 + hi (even rows only).
-__device__ __forceinline__ void permlane32_swap_x3(float (&a)[3], float (&b)[3]) {
-    asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %3\n\tv_permlane32_swap_b32 %1, %4\n\tv_permlane32_swap_b32 %2, %5"
-        : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]));
-}
-__device__ __forceinline__ void permlane16_swap_x2(float (&a)[2], float (&b)[2]) {
-    asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %2\n\tv_permlane16_swap_b32 %1, %3"
-        : "+v"(a[0]), "+v"(a[1]), "+v"(b[0]), "+v"(b[1]));
-}
-__device__ __forceinline__ float wave_reduce_scatter6(const float (&v)[6], int lane) {
-    float w[3];
-    {
-        float a[3] = {v[0], v[2], v[4]}, b[3] = {v[1], v[3], v[5]};
-        permlane32_swap_x3(a, b);
-#pragma unroll
-        for (int m = 0; m < 3; ++m) w[m] = a[m] + b[m];   // lanes 0-31: component 2m, lanes 32-63: component 2m+1
-    }
-    float x[2];
-    {
-        float a[2] = {w[0], w[2]}, b[2] = {w[1], 0.f};
-        permlane16_swap_x2(a, b);
-        x[0] = a[0] + b[0];                                // even rows: w0, odd rows: w1
-        x[1] = a[1] + b[1];                                // even rows: w2
-    }
-#define GFL_DPP(val, ctrl) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, (val)), ctrl, 0xF, 0xF, true))
-    const bool b0 = lane & 1;
-    const float keep = b0 ? x[1] : x[0], send = b0 ? x[0] : x[1];
-    float t = keep + GFL_DPP(send, 0xB1);                  // quad_perm [1,0,3,2]
-    t += GFL_DPP(t, 0x4E);                                 // quad_perm [2,3,0,1]
-    t += GFL_DPP(t, 0x124);                                // row_ror:4
-    t += GFL_DPP(t, 0x128);                                // row_ror:8
-#undef GFL_DPP
-    return t;
-}
-__device__ __forceinline__ int reduce_scatter6_component(int lane) {
-    const int hi = lane >> 5, odd = (lane >> 4) & 1, sel = lane & 15;
-    return sel == 0 ? 2 * odd + hi : ((sel == 1 && odd == 0) ? 4 + hi : -1);
-}
-
-// ... and for SEVEN (later frames: the colours are frozen, trainer.py:537-540 -- the moments, the opacity's and the depth
-// feature's gradient remain): eight slots {c0 .. c6, 0}, 8 -> 4 -> 2 values, then the two folded over a row: 18 VALU ops.
-// Afterwards lanes with bit 0 clear hold component 2 * odd + hi, lanes with bit 0 set component 4 + hi in even rows and
-// component 6 in row (hi = 0, odd = 1).
-__device__ __forceinline__ void permlane32_swap_x4(float (&a)[4], float (&b)[4]) {
+__device__ __forceinline__ void permlane32_swap(float (&a)[4], float (&b)[4]) {
     asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %4\n\tv_permlane32_swap_b32 %1, %5\n\tv_permlane32_swap_b32 %2, %6\n\t"
         "v_permlane32_swap_b32 %3, %7"
         : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]));
 }
-__device__ __forceinline__ float wave_reduce_scatter7(const float (&v)[7], int lane) {
-    float w[4];
-    {
-        float a[4] = {v[0], v[2], v[4], v[6]}, b[4] = {v[1], v[3], v[5], 0.f};
-        permlane32_swap_x4(a, b);
-#pragma unroll
-        for (int m = 0; m < 4; ++m) w[m] = a[m] + b[m];   // lanes 0-31: component 2m, lanes 32-63: component 2m+1
-    }
-    float x[2];
-    {
-        float a[2] = {w[0], w[2]}, b[2] = {w[1], w[3]};
-        permlane16_swap_x2(a, b);
-        x[0] = a[0] + b[0];                                // even rows: w0, odd rows: w1
-        x[1] = a[1] + b[1];                                // even rows: w2, odd rows: w3
-    }
+__device__ __forceinline__ void permlane32_swap(float (&a)[3], float (&b)[3]) {
+    asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %3\n\tv_permlane32_swap_b32 %1, %4\n\tv_permlane32_swap_b32 %2, %5"
+        : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]));
+}
+__device__ __forceinline__ void permlane16_swap(float (&a)[3], float (&b)[3]) {
+    asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %3\n\tv_permlane16_swap_b32 %1, %4\n\tv_permlane16_swap_b32 %2, %5"
+        : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]));
+}
+__device__ __forceinline__ void permlane16_swap(float (&a)[2], float (&b)[2]) {
+    asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %2\n\tv_permlane16_swap_b32 %1, %3"
+        : "+v"(a[0]), "+v"(a[1]), "+v"(b[0]), "+v"(b[1]));
+}
+
 #define GFL_DPP(val, ctrl) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, (val)), ctrl, 0xF, 0xF, true))
-    const bool b0 = lane & 1;
-    const float keep = b0 ? x[1] : x[0], send = b0 ? x[0] : x[1];
-    float t = keep + GFL_DPP(send, 0xB1);                  // quad_perm [1,0,3,2]
-    t += GFL_DPP(t, 0x4E);                                 // quad_perm [2,3,0,1]
-    t += GFL_DPP(t, 0x124);                                // row_ror:4
-    t += GFL_DPP(t, 0x128);                                // row_ror:8
-#undef GFL_DPP
+
+template <int N>
+__device__ __forceinline__ float wave_reduce_scatter(const float (&v)[N], int lane) {
+    static_assert(N == 10 || N == 7 || N == 6, "ten, seven or six sums per pair");
+    constexpr int H = (N + 1) / 2;
+    float w[H];
+    {
+        float a[H], b[H];
+#pragma unroll
+        for (int m = 0; m < H; ++m) { a[m] = v[2 * m]; b[m] = 2 * m + 1 < N ? v[2 * m + 1] : 0.f; }
+        permlane32_swap(a, b);        // a = {a_lo, b_lo}, b = {a_hi, b_hi}
+#pragma unroll
+        for (int m = 0; m < H; ++m) w[m] = a[m] + b[m];   // lanes 0-31: component 2m, lanes 32-63: component 2m+1
+    }
+    float t;
+    if constexpr (N == 10) {
+        float x[3];
+        {
+            float a[3] = {w[0], w[2], w[4]}, b[3] = {w[1], w[3], 0.f};
+            permlane16_swap(a, b);    // a = {a_r0, b_r0, a_r2, b_r2}, b = {a_r1, b_r1, a_r3, b_r3}
+            x[0] = a[0] + b[0];
+            x[1] = a[1] + b[1];
+            x[2] = a[2] + b[2];
+        }
+        // stage 3: the three values of a 16-lane row.  Instead of three independent 4-step reductions
+        // (12 DPP adds) the values are folded onto lane classes on the way: after the xor-1 step the
+        // even lanes carry x0 and the odd lanes x1, after the xor-2 step lanes with bit 1 set carry x2;
+        // two rotations by 4 and 8 lanes (which keep the low two lane bits) finish the sums: 9 ops.
+        const bool b0 = lane & 1, b1 = lane & 2;
+        const float keep01 = b0 ? x[1] : x[0], send01 = b0 ? x[0] : x[1];
+        const float y = keep01 + GFL_DPP(send01, 0xB1);          // quad_perm [1,0,3,2]
+        const float z = x[2] + GFL_DPP(x[2], 0xB1);
+        const float keep = b1 ? z : y, send = b1 ? y : z;
+        t = keep + GFL_DPP(send, 0x4E);                          // quad_perm [2,3,0,1]
+        // lane & 3 == 0: x0 total, == 1: x1 total, >= 2: x2 total
+    } else {
+        float x[2];
+        {
+            float a[2] = {w[0], w[2]}, b[2] = {w[1], H > 3 ? w[H - 1] : 0.f};
+            permlane16_swap(a, b);
+            x[0] = a[0] + b[0];                                // even rows: w0, odd rows: w1
+            x[1] = a[1] + b[1];                                // even rows: w2, odd rows: w3 (seven)
+        }
+        const bool b0 = lane & 1;
+        const float keep = b0 ? x[1] : x[0], send = b0 ? x[0] : x[1];
+        t = keep + GFL_DPP(send, 0xB1);                        // quad_perm [1,0,3,2]
+        t += GFL_DPP(t, 0x4E);                                 // quad_perm [2,3,0,1]
+    }
+    t += GFL_DPP(t, 0x124);                                    // row_ror:4
+    t += GFL_DPP(t, 0x128);                                    // row_ror:8
     return t;
 }
-__device__ __forceinline__ int reduce_scatter7_component(int lane) {
+
+// which of the N components the value returned to this lane belongs to (-1: a duplicate, not to
+// be used).  Depends on the lane only: callers evaluate it ONCE, outside their loops (inside, the
+// compiler turned the nested selects into a dozen exec-mask instructions per call).
+template <int N>
+__device__ __forceinline__ int reduce_scatter_component(int lane) {
     const int hi = lane >> 5, odd = (lane >> 4) & 1, sel = lane & 15;
-    return sel == 0 ? 2 * odd + hi : (sel == 1 ? (odd == 0 ? 4 + hi : (hi == 0 ? 6 : -1)) : -1);
+    if constexpr (N == 10) return sel == 0 ? 2 * odd + hi : (sel == 1 ? 4 + 2 * odd + hi : ((sel == 2 && odd == 0) ? 8 + hi : -1));
+    if constexpr (N == 7) return sel == 0 ? 2 * odd + hi : (sel == 1 ? (odd == 0 ? 4 + hi : (hi == 0 ? 6 : -1)) : -1);
+    return sel == 0 ? 2 * odd + hi : ((sel == 1 && odd == 0) ? 4 + hi : -1);
 }
+
 
 // Deterministic block-level reduction of NV values -> one partial row per block.
 // partial[blockIdx.x * NV + k]; a second tiny kernel folds the rows in order.

@@ -5,7 +5,7 @@
 // the launchers declared in gfl_fit.hpp; tile sort and loss kernels through their own C entry points (gfl_bin.hip,
 // gfl_ssim.hip).  Environment switches read here, once per process -- ALL the library has: GFL_EWA_MFMA, GFL_RESERVED,
 // GFL_FWD_SPLIT_MIN (include/gflow_hip.h).
-#include "gfl_fit.hpp"
+#include "gfl_fit_blend.hpp"
 
 using namespace gfl;
 
@@ -106,7 +106,7 @@ static size_t fit_regions(Arena& a, int cap_arg, int K_cap, int W, int H, FitWs&
     w.sched.list = a.take<int32_t>("sched_list", queue_items);                               // queue items
     w.sched.count = a.take<int32_t>("sched_count", 2 * SCHED_MAX_QUEUES);                    // queue lengths
     w.sched.counters = a.take<int32_t>("sched_counters", 2 * SCHED_MAX_QUEUES);              // pull counters, forward then backward
-    w.ckpt = a.take<float>("ckpt", (size_t)SCHED_MAX_QUEUES * (HEAVY_PARTS - 1) * 5 * 256);  // heavy-tile checkpoints
+    w.ckpt = a.take<float>("ckpt", CKPT_REGION_FLOATS);  // heavy-tile checkpoints
     w.sched_fwd.work = a.take<int32_t>("sched_fwd_work", 4 * T);                             // forward schedule: work feedback,
     w.sched_fwd.list = a.take<int32_t>("sched_fwd_list", queue_items);                       //   queue items,
     w.sched_fwd.count = a.take<int32_t>("sched_fwd_count", 2 * SCHED_MAX_QUEUES);            //   queue lengths

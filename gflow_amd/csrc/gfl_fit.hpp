@@ -1,6 +1,6 @@
 // Fused fit iteration -- what the stage files (gfl_fit_bin / _fwd / _bwd / _splat .hip) and the host file (gfl_fit.hip)
 // share: the data layout's constants, the device functions more than one stage inlines (camera from pose, activations, the
-// culling disc, a splat's walk over its tiles, the alpha test, the plain tile composite), the argument structs of the kernels, the carved workspace, and the launchers through which
+// culling disc, a splat's walk over its tiles, the alpha test, the plain tile composite, the end of an iteration), the argument structs of the kernels, the carved workspace, and the launchers through which
 // the host file reaches a stage's kernels (a kernel is launched from the translation unit that defines it).
 //
 // The whole of gflow/trainer.py:387-558 (activations, render, losses, backward, gradient masking, Adam) is ~6-9 kernel
@@ -428,6 +428,65 @@ struct LossTail {
     float* d_extr_out;                      // [12]: zeros (not computed in such an iteration)
     int32_t* overflow;                      // [4]: the forward dropped pairs ([0] | [2]) -> nothing is stepped, [1] counts the iteration
 };
+
+// The end of an iteration, once for its two holders: loss_tail (gfl_fit_bwd.hip, 256 threads of a backward-blend workgroup) and
+// fused_camera_adam_kernel (gfl_fit_splat.hip, one block of 1024).
+// What thread 0 needs after the reduction, requested before it.
+struct AffineRegs { float ab[2], m[2], v[2]; int step; };      // (thread 0's: request_affine leaves the other threads' alone)
+__device__ __forceinline__ void request_affine(const LossTail& t, AffineRegs& r) {
+    if (threadIdx.x == 0) {
+        r.step = *t.d_step;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) { r.ab[k] = t.depth_ab[k]; r.m[k] = t.ab_m[k]; r.v[k] = t.ab_v[k]; }
+    }
+}
+// A thread's share of the loss partials of a block of B threads, added into acc = {mse, ssim, depth, d/da, d/db}.  One
+// workgroup, nothing to overlap a load with but other loads: they are issued in batches of eight and four (one load per trip
+// made the camera kernel a chain of ~8 dependent L2 round trips).  The strides and the order of a thread's adds are part of
+// the result's bits: 256 and 1024 threads each keep their tree.
+template <int B>
+__device__ __forceinline__ void fold_loss_partials(const float* __restrict__ p_ssim, int n_ssim, const float* __restrict__ p_grad,
+                                                   int n_grad, float* acc) {
+    for (int r0 = threadIdx.x; r0 < n_ssim; r0 += 8 * B) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = (r0 + u * B < n_ssim) ? p_ssim[r0 + u * B] : 0.f;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc[1] += v[u];
+    }
+    for (int r0 = threadIdx.x; r0 < n_grad; r0 += 4 * B) {
+        float4 q[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            q[u] = (r0 + u * B < n_grad) ? reinterpret_cast<const float4*>(p_grad)[r0 + u * B]
+                                           : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { acc[0] += q[u].x; acc[2] += q[u].y; acc[3] += q[u].z; acc[4] += q[u].w; }
+    }
+}
+// Thread 0, behind the reduction; g_ab: the folded d/da, d/db.  camera(): what the holder steps besides the depth affine
+// (the camera kernel's pose), under the same two conditions.
+template <typename Camera>
+__device__ __forceinline__ void finish_iteration(const LossTail& t, AffineRegs& r, const float* g_ab, Camera&& camera) {
+    if (t.overflow && (t.overflow[0] | t.overflow[2]) != 0) {
+        // The forward of this iteration dropped (splat, tile) pairs: its gradients are not the scene's.  Nothing is
+        // stepped -- the per-splat launch skips its rows the same way --, the step counter stays, and the iteration is
+        // counted so that the host can run it again once it has grown the lists (FitEngine.settle_overflow).
+        t.overflow[1] += 1;
+        return;
+    }
+    if (t.step_affine) {
+        camera();
+        float ss, isb;
+        adam_scalars(t.ac_ab, r.step, t.ac_ab.lr, ss, isb);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            t.depth_ab[k] = adam_update(r.ab[k], g_ab[k], r.m[k], r.v[k], t.ac_ab, ss, isb);
+            t.ab_m[k] = r.m[k]; t.ab_v[k] = r.v[k];
+        }
+    }
+    *t.d_step = r.step + 1;
+}
 
 // ------------------------------------------------- preprocess backward + Adam (A13)
 struct RegCfg {                 // per-splat regularisers (trainer.py:490-530)

@@ -1,7 +1,8 @@
 // Fused fit iteration, stage 4: the backward of the compositing -- back to front over the sorted per-tile lists, one
 // 48-byte row of raw moments per (splat, tile) pair, no global atomics -- and, in iterations that cannot move the camera,
-// the fold of the loss partials + the depth-affine step in one of its workgroups (LossTail, gfl_fit.hpp).
-#include "gfl_fit.hpp"
+// the fold of the loss partials + the depth-affine step in one of its workgroups (loss_tail over LossTail, fold_loss_partials
+// and finish_iteration, gfl_fit.hpp).  Block plan, alive box and the checkpoints' layout: gfl_fit_blend.hpp.
+#include "gfl_fit_blend.hpp"
 
 namespace gfl {
 
@@ -41,30 +42,10 @@ __device__ void loss_tail(const LossTail& t) {
     constexpr int NV = 5;                   // mse, ssim, depth, d/da, d/db
     __shared__ float red[B / 64][NV];
     __shared__ float ge[NV];
-    float ab[2] = {0.f, 0.f}, abm[2] = {0.f, 0.f}, abv[2] = {0.f, 0.f};
-    int e_step = 0;
-    if (threadIdx.x == 0) {                 // thread 0 needs these after the reduction: request them now
-        e_step = *t.d_step;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) { ab[k] = t.depth_ab[k]; abm[k] = t.ab_m[k]; abv[k] = t.ab_v[k]; }
-    }
+    AffineRegs regs = {};
+    request_affine(t, regs);
     float acc[NV] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int r0 = threadIdx.x; r0 < t.n_ssim; r0 += 8 * B) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = (r0 + u * B < t.n_ssim) ? t.p_ssim[r0 + u * B] : 0.f;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc[1] += v[u];
-    }
-    for (int r0 = threadIdx.x; r0 < t.n_grad; r0 += 4 * B) {
-        float4 q[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            q[u] = (r0 + u * B < t.n_grad) ? reinterpret_cast<const float4*>(t.p_grad)[r0 + u * B]
-                                           : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { acc[0] += q[u].x; acc[2] += q[u].y; acc[3] += q[u].z; acc[4] += q[u].w; }
-    }
+    fold_loss_partials<B>(t.p_ssim, t.n_ssim, t.p_grad, t.n_grad, acc);
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
@@ -82,25 +63,7 @@ __device__ void loss_tail(const LossTail& t) {
     if (threadIdx.x >= NV && threadIdx.x < NV + 3) t.sums[threadIdx.x] = 0.f;
     if (threadIdx.x >= 16 && threadIdx.x < 28) t.d_extr_out[threadIdx.x - 16] = 0.f;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        if (t.overflow && (t.overflow[0] | t.overflow[2]) != 0) {
-            // The forward of this iteration dropped (splat, tile) pairs: its gradients are not the scene's.  Nothing is
-            // stepped -- the per-splat launch skips its rows the same way --, the step counter stays, and the iteration is
-            // counted so that the host can run it again once it has grown the lists (FitEngine.settle_overflow).
-            t.overflow[1] += 1;
-            return;
-        }
-        if (t.step_affine) {
-            float ss, isb;
-            adam_scalars(t.ac_ab, e_step, t.ac_ab.lr, ss, isb);
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                t.depth_ab[k] = adam_update(ab[k], ge[3 + k], abm[k], abv[k], t.ac_ab, ss, isb);
-                t.ab_m[k] = abm[k]; t.ab_v[k] = abv[k];
-            }
-        }
-        *t.d_step = e_step + 1;
-    }
+    if (threadIdx.x == 0) finish_iteration(t, regs, ge + 3, [] {});
 }
 
 // DET (GFL_FIT_DETERMINISTIC): the four waves do not add their sums into one row with LDS float atomics, in whatever order they
@@ -150,25 +113,17 @@ __global__ void __launch_bounds__(256, 8) fused_blend_bwd_kernel(const float* __
     __shared__ int32_t s_simd[4];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     // the component this lane adds into acc[][] (SUMS 6 / 7: the last value is the depth feature's gradient, column 9)
-    const int comp_few = SUMS == 6 ? reduce_scatter6_component(lane) : reduce_scatter7_component(lane);
-    const int comp = SUMS == 10 ? reduce_scatter10_component(lane) : (comp_few == SUMS - 1 ? 9 : comp_few);
-    // Which SIMD is this wave on?  The scheduler plans which SIMD walks which 8x8 block of every item (gfl_sched.hpp,
-    // "block plan"); the plan is followed only if the workgroup's four waves sit on four different SIMDs (they do: the
-    // dispatcher deals a workgroup's waves round the SIMDs), otherwise wave k walks block k.
-    unsigned hw_id;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_id));
-    const int simd = (hw_id >> 4) & 3;
-    if (lane == 0) s_simd[wave] = simd;
-    __syncthreads();
-    const bool simd_ok = ((1 << s_simd[0]) | (1 << s_simd[1]) | (1 << s_simd[2]) | (1 << s_simd[3])) == 15;
+    const int comp_own = reduce_scatter_component<SUMS>(lane);
+    const int comp = (SUMS != 10 && comp_own == SUMS - 1) ? 9 : comp_own;
+    // block plan (gfl_fit_blend.hpp): which 8x8 block of a tile this wave walks follows from the SIMD it sits on
+    const int simd = wave_simd();
+    const bool simd_ok = simds_distinct(s_simd, simd);
   for (bool first = true;; first = false) {
     const TileItem item = next_item(queue, &s_ticket, first, HEAVY_PARTS, gridDim.x);
     const int tile = item.tile;
     if (tile < 0) break;
-    const unsigned plan = item.plan;
-    const bool plan_ok = simd_ok && ((1 << (plan & 3)) | (1 << ((plan >> 2) & 3)) | (1 << ((plan >> 4) & 3)) | (1 << ((plan >> 6) & 3))) == 15;
     // (the segments of a heavy first tile turning the plan by one SIMD each was measured slower: tools/experiments/README.md)
-    const int blk = plan_ok ? (int)((plan >> (2 * simd)) & 3u) : wave;          // the 8x8 block of the tile this wave walks
+    const int blk = plan_block(item.plan, simd, simd_ok, wave);          // the 8x8 block of the tile this wave walks
     const int tx = tile % gx, ty = tile / gx;
     const int px = tx * GFL_TILE + (blk & 1) * 8 + (lane & 7);
     const int py = ty * GFL_TILE + (blk >> 1) * 8 + (lane >> 3);
@@ -198,10 +153,10 @@ __global__ void __launch_bounds__(256, 8) fused_blend_bwd_kernel(const float* __
         } else {
             // state in front of this segment's far boundary, from the forward checkpoint: T as it
             // was there and S = sum_c g_c * (everything blended behind it) = sum_c g_c * (out_c - C_c)
-            const float* ck = ckpt + ((size_t)item.queue * (HEAVY_PARTS - 1) + item.part) * 5 * 256 + blk * 64 + lane;
-            T = ck[0];
-            S = g0 * (render[pix] - ck[256]) + g1 * (render[plane + pix] - ck[512]) +
-                g2 * (render[2 * plane + pix] - ck[768]) + g3 * (render[3 * plane + pix] - ck[1024]);
+            float C[4];
+            ckpt_load(ckpt_at(ckpt, item.queue, item.part) + tile_place(blk, lane), T, C);
+            S = g0 * (render[pix] - C[0]) + g1 * (render[plane + pix] - C[1]) +
+                g2 * (render[2 * plane + pix] - C[2]) + g3 * (render[3 * plane + pix] - C[3]);
         }
     }
     if (tid == 0) s_max_last = 0;
@@ -250,18 +205,7 @@ __global__ void __launch_bounds__(256, 8) fused_blend_bwd_kernel(const float* __
                 // positions can receive anything from it; splats that do not reach their bounding box are skipped
                 // before their alpha is evaluated (the test of block_mask on a smaller box)
                 const unsigned long long alive = __ballot(last > hi - 1 - r0 - c0 - 63);
-                if (alive != alive0 && alive != 0ull) {
-                    unsigned long long a = alive | (alive >> 32);
-                    a |= a >> 16;
-                    a |= a >> 8;
-                    const unsigned cols = (unsigned)a & 0xffu;
-                    const int xl = __builtin_ctz(cols), xh = 31 - __builtin_clz(cols);
-                    const int yl = (int)__builtin_ctzll(alive) >> 3, yh = (63 - (int)__builtin_clzll(alive)) >> 3;
-                    if (hit) {
-                        const BlockTest t = block_test(recs[slot].p0, recs[slot].p1, recs[slot].p2.z);
-                        hit = box_hit(t, (float)(px0w + xl), (float)(px0w + xh), (float)(py0w + yl), (float)(py0w + yh));
-                    }
-                }
+                if (alive != alive0 && alive != 0ull) cull_to_alive_box(hit, alive, recs[slot], px0w, py0w);
             }
             unsigned long long bits = __ballot(hit);
             while (bits) {
@@ -279,16 +223,10 @@ __global__ void __launch_bounds__(256, 8) fused_blend_bwd_kernel(const float* __
                 // (an interleaved two-splat version of this body was measured slower, twice)
                 float v[10];
                 blend_bwd_terms(p0, p1, p2, fx, fy, valid, alpha, G, g0, g1, g2, g3, T, S, v);
-                float mine;
-                if (SUMS == 6) {
-                    const float v6[6] = {v[0], v[1], v[2], v[3], v[4], v[9]};
-                    mine = wave_reduce_scatter6(v6, lane);
-                } else if (SUMS == 7) {
-                    const float v7[7] = {v[0], v[1], v[2], v[3], v[4], v[5], v[9]};
-                    mine = wave_reduce_scatter7(v7, lane);
-                } else {
-                    mine = wave_reduce_scatter10(v, lane);
-                }
+                float s[SUMS];               // the sums somebody reads: v[0 .. SUMS - 2] and, last, v[9] (SUMS)
+#pragma unroll
+                for (int k = 0; k < SUMS; ++k) s[k] = v[k < SUMS - 1 ? k : 9];
+                const float mine = wave_reduce_scatter<SUMS>(s, lane);
                 if constexpr (DET) {
                     if (comp >= 0) acc[blk][j][comp] = mine;
                 } else {
@@ -337,16 +275,14 @@ __global__ void __launch_bounds__(256, 8) fused_blend_bwd_kernel(const float* __
     if (lane == 0) atomicAdd(&tile_work[4 * tile + blk], units + 1);
 #ifdef GFL_TRACE
     if (lane == 0 && tile < 2048) {
-        unsigned hw, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        const unsigned hw = wave_hw_id(), xcc = wave_xcc_id();
         long long* tr = g_bwd_trace + (size_t)(tile + (last_part ? 0 : 2048 * (1 + item.part))) * 8;
         if (wave == 0) {
             tr[0] = trace_t0; tr[1] = wall_clock64();
             tr[2] = ((long long)total << 32) | (unsigned)depth_n;
             tr[3] = ((long long)(xcc & 15) << 32) | hw;
         }
-        tr[4 + wave] = ((long long)(trace_lanes | ((hw >> 4) & 3) << 28) << 32) | (unsigned)units;   // bits 60-61: this wave's SIMD
+        tr[4 + wave] = ((long long)(trace_lanes | simd << 28) << 32) | (unsigned)units;   // bits 60-61: this wave's SIMD
     }
 #endif
   }

@@ -387,7 +387,8 @@ __global__ void __launch_bounds__(REDUCE_BLOCK) splat_intr_bwd_kernel(
 
 // camera + depth affine: fold the extr partials, chain to the pose, Adam, step += 1
 // One block of 1024 lanes also folds the loss partial rows (no separate fold launch): every lane
-// is at most a couple of loads deep, the tree has a fixed shape (reproducible).
+// is at most a couple of loads deep, the tree has a fixed shape (reproducible).  The fold and thread 0's tail (void rule,
+// depth-affine step, step counter) are loss_tail's too: fold_loss_partials, finish_iteration (gfl_fit.hpp).
 __global__ void __launch_bounds__(1024) fused_camera_adam_kernel(
     const float* __restrict__ partial, int rows, const float* __restrict__ p_ssim, int n_ssim,
     const float* __restrict__ p_grad, int n_grad, float* __restrict__ pose, float* __restrict__ pose_m,
@@ -404,32 +405,16 @@ __global__ void __launch_bounds__(1024) fused_camera_adam_kernel(
         acc[0] += a.x; acc[1] += a.y; acc[2] += a.z; acc[3] += a.w; acc[4] += b.x; acc[5] += b.y; acc[6] += b.z;
         acc[7] += b.w; acc[8] += c.x; acc[9] += c.y; acc[10] += c.z; acc[11] += c.w;
     }
-    // one workgroup, nothing to overlap a load with but other loads: issue them in batches
-    // (one load per trip made this kernel a chain of ~8 dependent L2 round trips)
-    for (int r0 = threadIdx.x; r0 < n_ssim; r0 += 8 * 1024) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = (r0 + u * 1024 < n_ssim) ? p_ssim[r0 + u * 1024] : 0.f;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc[13] += v[u];
-    }
-    for (int r0 = threadIdx.x; r0 < n_grad; r0 += 4 * 1024) {
-        float4 q[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            q[u] = (r0 + u * 1024 < n_grad) ? reinterpret_cast<const float4*>(p_grad)[r0 + u * 1024] : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { acc[12] += q[u].x; acc[14] += q[u].y; acc[15] += q[u].z; acc[16] += q[u].w; }
-    }
+    const LossTail t = {1, p_ssim, n_ssim, p_grad, n_grad, depth_ab, ab_m, ab_v, sums, ac_ab, step_camera, d_step, d_extr_out, overflow};
+    fold_loss_partials<1024>(p_ssim, n_ssim, p_grad, n_grad, acc + 12);
     // thread 0 needs these after the reduction: request them now
-    float pz[7], pm[7], pv[7], ab[2], abm[2], abv[2];
-    int e_step = 0;
+    float pz[7], pm[7], pv[7];
+    AffineRegs regs;
+    regs.step = 0;
+    request_affine(t, regs);
     if (threadIdx.x == 0) {
-        e_step = *d_step;
 #pragma unroll
         for (int k = 0; k < 7; ++k) { pz[k] = pose[k]; pm[k] = pose_m[k]; pv[k] = pose_v[k]; }
-#pragma unroll
-        for (int k = 0; k < 2; ++k) { ab[k] = depth_ab[k]; abm[k] = ab_m[k]; abv[k] = ab_v[k]; }
     }
     __shared__ float red[16][NV];
     __shared__ float ge[NV];
@@ -449,47 +434,33 @@ __global__ void __launch_bounds__(1024) fused_camera_adam_kernel(
     }
     if (threadIdx.x >= NV && threadIdx.x < NV + 3) sums[threadIdx.x - NV + 5] = 0.f;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        const int e = e_step;
-        if (overflow && (overflow[0] | overflow[2]) != 0) {      // the forward dropped pairs: nothing is stepped, the iteration is counted (LossTail)
-            overflow[1] += 1;
-            return;
+    if (threadIdx.x == 0) finish_iteration(t, regs, ge + 15, [&] {
+        // d_extr (rows R|t) -> d_pose; q = raw/|raw| in XYZW order
+        const float rx = pz[0], ry = pz[1], rz = pz[2], rw = pz[3];
+        const float n = sqrtf(rx * rx + ry * ry + rz * rz + rw * rw);
+        const float x = rx / n, y = ry / n, z = rz / n, w = rw / n;
+        const float* dR = ge;   // dR[i][j] = ge[4 i + j]
+        const float d00 = dR[0], d01 = dR[1], d02 = dR[2], d10 = dR[4], d11 = dR[5], d12 = dR[6], d20 = dR[8],
+                    d21 = dR[9], d22 = dR[10];
+        float dq[4];   // x y z w
+        dq[3] = 2.f * (-z * d01 + y * d02 + z * d10 - x * d12 - y * d20 + x * d21);
+        dq[0] = 2.f * (y * d01 + z * d02 + y * d10 - 2.f * x * d11 - w * d12 + z * d20 + w * d21 - 2.f * x * d22);
+        dq[1] = 2.f * (-2.f * y * d00 + x * d01 + w * d02 + x * d10 + z * d12 - w * d20 + z * d21 - 2.f * y * d22);
+        dq[2] = 2.f * (-2.f * z * d00 - w * d01 + x * d02 + w * d10 - 2.f * z * d11 + y * d12 + x * d20 + y * d21);
+        const float qh[4] = {x, y, z, w};
+        const float dot = qh[0] * dq[0] + qh[1] * dq[1] + qh[2] * dq[2] + qh[3] * dq[3];
+        float gp[7];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) gp[k] = (dq[k] - qh[k] * dot) / n;
+        gp[4] = ge[3]; gp[5] = ge[7]; gp[6] = ge[11];
+        float ss, isb;
+        adam_scalars(ac_cam, regs.step, ac_cam.lr, ss, isb);
+#pragma unroll
+        for (int k = 0; k < 7; ++k) {
+            pose[k] = adam_update(pz[k], gp[k], pm[k], pv[k], ac_cam, ss, isb);
+            pose_m[k] = pm[k]; pose_v[k] = pv[k];
         }
-        if (step_camera) {
-            // d_extr (rows R|t) -> d_pose; q = raw/|raw| in XYZW order
-            const float rx = pz[0], ry = pz[1], rz = pz[2], rw = pz[3];
-            const float n = sqrtf(rx * rx + ry * ry + rz * rz + rw * rw);
-            const float x = rx / n, y = ry / n, z = rz / n, w = rw / n;
-            const float* dR = ge;   // dR[i][j] = ge[4 i + j]
-            const float d00 = dR[0], d01 = dR[1], d02 = dR[2], d10 = dR[4], d11 = dR[5], d12 = dR[6], d20 = dR[8],
-                        d21 = dR[9], d22 = dR[10];
-            float dq[4];   // x y z w
-            dq[3] = 2.f * (-z * d01 + y * d02 + z * d10 - x * d12 - y * d20 + x * d21);
-            dq[0] = 2.f * (y * d01 + z * d02 + y * d10 - 2.f * x * d11 - w * d12 + z * d20 + w * d21 - 2.f * x * d22);
-            dq[1] = 2.f * (-2.f * y * d00 + x * d01 + w * d02 + x * d10 + z * d12 - w * d20 + z * d21 - 2.f * y * d22);
-            dq[2] = 2.f * (-2.f * z * d00 - w * d01 + x * d02 + w * d10 - 2.f * z * d11 + y * d12 + x * d20 + y * d21);
-            const float qh[4] = {x, y, z, w};
-            const float dot = qh[0] * dq[0] + qh[1] * dq[1] + qh[2] * dq[2] + qh[3] * dq[3];
-            float gp[7];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) gp[k] = (dq[k] - qh[k] * dot) / n;
-            gp[4] = ge[3]; gp[5] = ge[7]; gp[6] = ge[11];
-            float ss, isb;
-            adam_scalars(ac_cam, e, ac_cam.lr, ss, isb);
-#pragma unroll
-            for (int k = 0; k < 7; ++k) {
-                pose[k] = adam_update(pz[k], gp[k], pm[k], pv[k], ac_cam, ss, isb);
-                pose_m[k] = pm[k]; pose_v[k] = pv[k];
-            }
-            adam_scalars(ac_ab, e, ac_ab.lr, ss, isb);
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                depth_ab[k] = adam_update(ab[k], ge[15 + k], abm[k], abv[k], ac_ab, ss, isb);
-                ab_m[k] = abm[k]; ab_v[k] = abv[k];
-            }
-        }
-        *d_step = e + 1;
-    }
+    });
 }
 
 // ---- launchers (gfl_fit.hpp)

@@ -4,15 +4,15 @@
 
 namespace gfl {
 
-// one wave: in[64][10] -> out[10] via wave_reduce_scatter10; out2[10] via ten wave_sum calls
+// one wave: in[64][10] -> out[10] via wave_reduce_scatter<10>; out2[10] via ten wave_sum calls
 __global__ void __launch_bounds__(64) selftest_reduce10_kernel(const float* __restrict__ in, float* __restrict__ out,
                                                                float* __restrict__ out2) {
     const int lane = threadIdx.x;
     float v[10];
 #pragma unroll
     for (int k = 0; k < 10; ++k) v[k] = in[lane * 10 + k];
-    const int comp = reduce_scatter10_component(lane);
-    const float mine = wave_reduce_scatter10(v, lane);
+    const int comp = reduce_scatter_component<10>(lane);
+    const float mine = wave_reduce_scatter<10>(v, lane);
     if (comp >= 0) out[comp] = mine;
 #pragma unroll
     for (int k = 0; k < 10; ++k) {

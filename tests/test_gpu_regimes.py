@@ -168,6 +168,47 @@ def test_reserved_tile_regions_on_the_regime_scene():
     assert int((live & (cutoff > 1e38)).sum()) >= 100 and int((live & (cutoff < 0)).sum()) >= 100
 
 
+# ------------------------------------------------------------------------------------------------ the blend's modes, long tile
+def test_forward_modes_agree_on_the_long_tile_walk():
+    """The pile's tile is long enough for the forward's quarter walk (four 8x8 blocks on four CUs, three staged batches,
+    checkpoints at 192, 384 and 576), which the sparse scenes of tests/test_gpu_fused.py never reach in modes 1, 2 and 3.
+    The equalities those tests assert, on this scene: a snapshot iteration (mode 2) against a plain one (mode 0) followed by
+    gfl_fit_snapshot (mode 1) -- render, final_T, n_contrib bit for bit, the three uint8 images byte for byte --, and with a
+    footprint mask the plain iteration (mode 3: footprint workgroups behind the blend's) against the snapshot iteration
+    (a footprint launch of its own): the same keep, the same render."""
+    sc, img, dep, sets, _ = _case("pile")
+    hyper = dict(lr=2e-4, lr_camera=0.0, total_iters=100, **REGIME_LAMBDAS)
+    a = _engine(sc["raw"], sc, img, dep, pose=POSE, **hyper)
+    b = _engine(sc["raw"], sc, img, dep, pose=POSE, **hyper)
+    got = a.iteration(snapshot=True).clone()
+    b.iteration(reserved=False)
+    want = b.snapshot()
+    a.check_overflow(); b.check_overflow()
+    for e in (a, b):
+        tr = e.tile_range[sc["pile_tile"]].cpu()
+        assert int(tr[1] - tr[0]) > max(448, 3 * 192), f"the pile's list has {int(tr[1] - tr[0])} entries"
+    assert torch.equal(a.render, b.render) and torch.equal(a.final_T, b.final_T) and torch.equal(a.n_contrib, b.n_contrib)
+    for k, name in enumerate(("rgb", "depth_map_color", "center")):
+        assert torch.equal(got[k], want[k]), f"{name}: {(got[k] != want[k]).float().mean().item():.2e} of the bytes differ"
+    # mode 3 against mode 2 + footprint_kernel: every sixteenth row behind the pile is flagged as moving (the pile's own splats
+    # are 20-60 pixels wide: any eleven of them cover the image); the footprint's workgroup still walks the pile tile's list
+    n = sc["raw"]["xyz"].shape[0]
+    moving = (torch.arange(n) >= sc["n_pile"]) & ((torch.arange(n) % 16) == 0)
+    move_mask = torch.zeros(sc["H"], sc["W"], dtype=torch.bool)
+    move_mask[2:6, 30:40] = True
+    c = _engine(sc["raw"], sc, img, dep, pose=POSE, **hyper)
+    d = _engine(sc["raw"], sc, img, dep, pose=POSE, **hyper)
+    for e in (c, d):
+        e.set_footprint_mask(move_mask, moving)
+    c.iteration()
+    d.iteration(snapshot=True)
+    c.check_overflow(); d.check_overflow()
+    masked = 1.0 - c.keep.float().mean().item()
+    assert float(move_mask.float().mean()) < masked < 1.0, f"{masked:.3f} of the pixels masked: the footprint case is degenerate"
+    assert torch.equal(c.keep, d.keep) and torch.equal(c.render, d.render)
+    assert torch.equal(c.final_T, d.final_T) and torch.equal(c.n_contrib, d.n_contrib)
+
+
 # ------------------------------------------------------------------------------------------------ fused render operator
 def test_render_operator_per_regime():
     """gfl_render_fwd / _bwd on ACTIVATED rows (splat_from_row's other branch): values, and the gradients with respect to the
