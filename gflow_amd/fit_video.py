@@ -56,6 +56,12 @@ def _parser():
                     help="path of a prepared sequence folder (images + the reference's sibling folders, "
                          "gflow_amd/io.py); may be given several times, one clip each; default: synthetic clips")
     ap.add_argument("--resize", type=int, default=None, help="shorter image side after loading a --sequence")
+    ap.add_argument("--blur", action="store_true",
+                    help="with --sequence: GaussianBlur(7, 5.0) on the image, the occlusion mask and the flow after the resize "
+                         "(the reference's blur option)")
+    ap.add_argument("--prep", choices=("host", "device"), default="host",
+                    help="with --sequence: where the decoded files are converted, resized and blurred -- on the host with "
+                         "torch, one file at a time, or as whole stacks on this rank's device (gflow_amd.prep)")
     ap.add_argument("--deterministic", action="store_true",
                     help="bit-identical results for identical inputs (the library's deterministic mode, INTEGRATION.md)")
     ap.add_argument("--track", action="store_true",
@@ -159,7 +165,8 @@ def _load_clips(args, mine, lengths, dev):
         if args.sequence:
             clips[ci] = gio.load_sequence(args.sequence[ci], resize=args.resize,
                                           move_masks="epipolar" if args.make_move_masks else "files",
-                                          occ_masks="flow" if args.make_occ_masks else "files")
+                                          occ_masks="flow" if args.make_occ_masks else "files", blur=args.blur,
+                                          device=dev if args.prep == "device" else None)
         else:
             clips[ci] = upload_clip(S.make_clip(lengths[ci], args.height, args.width, seed=ci, device=dev), dev)
     return clips

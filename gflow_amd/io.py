@@ -39,19 +39,37 @@ def _resize_chw(t, resize):
     return F.interpolate(t.unsqueeze(0), size=(nh, nw), mode="bilinear", antialias=True, align_corners=False).squeeze(0)
 
 
-def image_path_to_tensor(image_path, resize=None):
+def _blur_chw(t, blur, kernel_size=7, sigma=5.0):
+    """torchvision.transforms.GaussianBlur(kernel_size, sigma) on a (C,H,W) float tensor: reflect padding, then the
+    outer-product kernel as a grouped conv2d (the reference's ``blur`` option: conversion.py:13-14, read.py:32-33)."""
+    if not blur:
+        return t
+    half = (kernel_size - 1) * 0.5
+    x = torch.linspace(-half, half, steps=kernel_size)
+    pdf = torch.exp(-0.5 * (x / sigma).pow(2))
+    k1 = (pdf / pdf.sum()).to(t.dtype)
+    k2 = torch.mm(k1[:, None], k1[None, :]).expand(t.shape[0], 1, kernel_size, kernel_size)
+    r = kernel_size // 2
+    return F.conv2d(F.pad(t.unsqueeze(0), [r, r, r, r], mode="reflect"), k2, groups=t.shape[0]).squeeze(0)
+
+
+def _image_div(dtype):
+    return 255.0 if dtype == np.uint8 else 65535.0 if dtype == np.uint16 else 1.0
+
+
+def image_path_to_tensor(image_path, resize=None, blur=False):
     """conversion.py:6-19 -> (H,W,3) float in [0,1]."""
     from PIL import Image
     img = np.asarray(Image.open(image_path))
     t = torch.from_numpy(img.copy())
     if t.dim() == 2:
         t = t.unsqueeze(-1)
-    t = t.permute(2, 0, 1).float() / (255.0 if img.dtype == np.uint8 else 65535.0 if img.dtype == np.uint16 else 1.0)
-    return _resize_chw(t, resize).permute(1, 2, 0)[..., :3]
+    t = t.permute(2, 0, 1).float() / _image_div(img.dtype)
+    return _blur_chw(_resize_chw(t, resize), blur).permute(1, 2, 0)[..., :3]
 
 
-def read_flow(fn, resize=None):
-    """read.py:7-38: Middlebury .flo (little endian) -> (H,W,2); None on a bad magic number."""
+def _read_flo(fn):
+    """The (h, w, 2) float32 array of a Middlebury .flo file (little endian); None on a bad magic number."""
     with open(fn, "rb") as f:
         magic = np.fromfile(f, np.float32, count=1)
         if magic.size != 1 or magic[0] != np.float32(FLO_MAGIC):
@@ -60,8 +78,15 @@ def read_flow(fn, resize=None):
         w = int(np.fromfile(f, np.int32, count=1)[0])
         h = int(np.fromfile(f, np.int32, count=1)[0])
         data = np.fromfile(f, np.float32, count=2 * w * h)
-    flow = torch.from_numpy(np.resize(data, (h, w, 2)).copy()).permute(2, 0, 1)
-    return _resize_chw(flow, resize).permute(1, 2, 0)
+    return np.resize(data, (h, w, 2)).copy()
+
+
+def read_flow(fn, resize=None, blur=False):
+    """read.py:7-38: Middlebury .flo (little endian) -> (H,W,2); None on a bad magic number."""
+    flow = _read_flo(fn)
+    if flow is None:
+        return None
+    return _blur_chw(_resize_chw(torch.from_numpy(flow).permute(2, 0, 1), resize), blur).permute(1, 2, 0)
 
 
 def write_flow(fn, flow):
@@ -128,7 +153,7 @@ def sequence_paths(sequence_path, frame_start=0, frame_range=-1, skip_interval=1
 
 
 def load_sequence(sequence_path, resize=None, frame_start=0, frame_range=-1, skip_interval=1, depth_offset=0.0,
-                  move_masks="files", occ_masks="files"):
+                  move_masks="files", occ_masks="files", blur=False, device=None):
     """Frames in the dict form ``gflow_amd.fit_video.fit_clip`` takes.  Frame i carries the flow
     i -> i+1 (fit_video.py:249: frame i+1 is fitted with flow_paths[i]) and the occlusion mask that
     fit_video.py:248 reads for it (img_occ_paths[i-1]).
@@ -138,36 +163,150 @@ def load_sequence(sequence_path, resize=None, frame_start=0, frame_range=-1, ski
     ``occ_masks``: "files" reads ``*occ_bwd.*``; "flow" ignores those files and computes the mask of frame i + 1 from the
     flows i -> i + 1 and i + 1 -> i (``*pred_bwd.flo``) at the flows' NATIVE resolution, on the device
     (gflow_amd.occlusion.clip_occ_masks), then resizes the mask as a mask file would be.  Either way a frame without its
-    file(s) gets no ``occ_mask``."""
+    file(s) gets no ``occ_mask``.
+    ``blur``: the reference's option -- GaussianBlur(7, 5.0) after the resize on the image, the occlusion mask and the flow
+    (fit_video.py:245-248), not on the depth or the move mask.
+    ``device``: None prepares every file on the host with torch, one file at a time, and returns host tensors.  With a
+    device the files are only decoded on the host: the raw arrays of one kind are stacked, uploaded once and prepared there
+    (gflow_amd.prep.prep_frames), and the frames hold device tensors of the same shapes and dtypes (``extr`` stays on the
+    host, ``occ_count`` is set from one read-back for the whole clip).  The device's resize is the same filter with exact
+    weights ("Frame preparation"): without ``resize`` and ``blur`` both paths give the same bits."""
     if occ_masks not in ("files", "flow"):
         raise ValueError(f"load_sequence: occ_masks must be \"files\" or \"flow\", got {occ_masks!r}")
     if move_masks not in ("files", "epipolar"):
         raise ValueError(f"load_sequence: move_masks must be \"files\" or \"epipolar\", got {move_masks!r}")
     p = sequence_paths(sequence_path, frame_start, frame_range, skip_interval)
     focal, pp, poses = read_camera(p["camera"])
+    if device is not None:
+        frames = _load_frames_device(p, focal, pp, poses, resize, depth_offset, move_masks, occ_masks, blur,
+                                     torch.device(device))
+    else:
+        frames = _load_frames_host(p, focal, pp, poses, resize, depth_offset, move_masks, occ_masks, blur)
+    if move_masks == "epipolar":
+        from .move_seg import clip_move_masks
+        clip_move_masks(frames, n_flows=len(p["flow"]))
+    return frames
+
+
+def _load_frames_host(p, focal, pp, poses, resize, depth_offset, move_masks, occ_masks, blur):
     frames = []
     for i, ip in enumerate(p["img"]):
-        fr = dict(image=image_path_to_tensor(ip, resize), focal=focal, pp=pp, name=os.path.basename(ip).split(".")[0])
+        fr = dict(image=image_path_to_tensor(ip, resize, blur), focal=focal, pp=pp, name=os.path.basename(ip).split(".")[0])
         fr["depth"] = read_depth(p["depth"][i], resize, depth_offset=depth_offset).unsqueeze(-1)
         H, W = fr["image"].shape[:2]
         from_file = move_masks == "files" and i < len(p["move"])
         fr["move_mask"] = read_mask(p["move"][i], resize) if from_file else torch.zeros(H, W, dtype=torch.bool)
-        fr["flow"] = read_flow(p["flow"][i], resize) if i < len(p["flow"]) else torch.zeros(H, W, 2)
+        fr["flow"] = read_flow(p["flow"][i], resize, blur) if i < len(p["flow"]) else torch.zeros(H, W, 2)
         if occ_masks == "files" and i >= 1 and i - 1 < len(p["occ"]):
-            fr["occ_mask"] = image_path_to_tensor(p["occ"][i - 1], resize)
+            fr["occ_mask"] = image_path_to_tensor(p["occ"][i - 1], resize, blur)
         if i < len(poses):
             fr["extr"] = torch.tensor(poses[i], dtype=torch.float32)
         frames.append(fr)
-    if move_masks == "epipolar":
-        from .move_seg import clip_move_masks
-        clip_move_masks(frames, n_flows=len(p["flow"]))
     if occ_masks == "flow":
         from .occlusion import clip_occ_masks
         n_pairs = min(len(frames) - 1, len(p["flow"]), len(p["flow_bwd"]))
         # (the reference resizes a flow without rescaling its values: the check must not see fr["flow"] of a resized clip)
-        fwd = [frames[i]["flow"] if resize is None else read_flow(p["flow"][i]) for i in range(n_pairs)]
+        native = resize is None and not blur
+        fwd = [frames[i]["flow"] if native else read_flow(p["flow"][i]) for i in range(n_pairs)]
         bwd = [read_flow(p["flow_bwd"][i]) for i in range(n_pairs)]
         clip_occ_masks(frames, bwd, fwd_flows=fwd, resize=resize)
+        if blur:                                   # (no frame had a mask before: the files are ignored)
+            for fr in frames:
+                if "occ_mask" in fr:
+                    fr["occ_mask"] = _blur_chw(fr["occ_mask"].permute(2, 0, 1), True).permute(1, 2, 0)
+    return frames
+
+
+# ---- the device path: decode on the host, prepare whole stacks on the device
+def _decode_image(path):
+    """(array (H, W, C <= 3) uint8 or float32, the divisor that makes it [0, 1]) as image_path_to_tensor reads the file"""
+    from PIL import Image
+    img = np.asarray(Image.open(path))
+    div = _image_div(img.dtype)
+    if img.ndim == 2:
+        img = img[..., None]
+    img = img[..., :3]
+    return np.ascontiguousarray(img if img.dtype == np.uint8 else img.astype(np.float32)), div
+
+
+def _decode_mask(path):
+    """(H, W, C) uint8 or float32 as read_mask reads the file"""
+    from PIL import Image
+    mask = np.asarray(Image.open(path))
+    if mask.ndim == 2:
+        mask = mask[..., None]
+    elif mask.ndim != 3:
+        raise ValueError("The mask should be 2D or 3D")
+    return np.ascontiguousarray(mask if mask.dtype == np.uint8 else mask.astype(np.float32))
+
+
+def _prep_stacks(arrays, device, resize, keys=None, **kw):
+    """prep_frames over a list of (H, W, C) arrays (None: no file): the arrays of one shape and dtype (and ``keys`` entry,
+    the divisor) go up as ONE stack and come back as views of one result.  Returns the list of device tensors."""
+    from .prep import prep_frames
+    out = [None] * len(arrays)
+    groups = {}
+    for i, a in enumerate(arrays):
+        if a is not None:
+            groups.setdefault((a.shape, a.dtype.str, None if keys is None else keys[i]), []).append(i)
+    for (_, _, key), idx in groups.items():
+        stack = torch.from_numpy(np.stack([arrays[i] for i in idx])).to(device)
+        res = prep_frames(stack, resize, **(kw if key is None else dict(kw, div=key)))
+        for j, i in enumerate(idx):
+            out[i] = res[j]
+    return out
+
+
+def _load_frames_device(p, focal, pp, poses, resize, depth_offset, move_masks, occ_masks, blur, device):
+    if device.type != "cuda":
+        raise RuntimeError("gflow_amd.io: load_sequence(device=...) needs a HIP (cuda) device; there is no CPU fallback")
+    n = len(p["img"])
+    images = [_decode_image(ip) for ip in p["img"]]
+    image = _prep_stacks([a for a, _ in images], device, resize, keys=[d for _, d in images], blur=blur)
+    depth = _prep_stacks([np.asarray(np.load(p["depth"][i]), dtype=np.float32)[..., None] for i in range(n)], device, resize,
+                         mul=1.0, add=depth_offset)
+    flows = [_read_flo(p["flow"][i]) if i < len(p["flow"]) else None for i in range(n)]
+    flow = _prep_stacks(flows, device, resize, blur=blur)
+    move = [None] * n
+    if move_masks == "files":
+        move = _prep_stacks([_decode_mask(p["move"][i]) if i < len(p["move"]) else None for i in range(n)], device, resize,
+                            as_mask=True)
+    occ = [None] * n
+    if occ_masks == "files":
+        files = [_decode_image(p["occ"][i - 1]) if 1 <= i <= len(p["occ"]) else (None, None) for i in range(n)]
+        occ = _prep_stacks([a for a, _ in files], device, resize, keys=[d for _, d in files], blur=blur)
+    else:
+        from .occlusion import flow_occlusion
+        from .prep import prep_frames
+        # the check sees the flows at their native resolution (resizing a flow does not rescale its values)
+        bwd = [_read_flo(p["flow_bwd"][i]) for i in range(min(n - 1, len(p["flow"]), len(p["flow_bwd"])))]
+        pairs = [i for i, b in enumerate(bwd) if b is not None and flows[i] is not None]
+        if pairs:
+            res = flow_occlusion(torch.from_numpy(np.stack([flows[i] for i in pairs])).to(device),
+                                 torch.from_numpy(np.stack([bwd[i] for i in pairs])).to(device))["occ_bwd"]
+            masks = prep_frames((res != 0).to(torch.uint8).unsqueeze(-1).contiguous(), resize, blur=blur)
+            for j, i in enumerate(pairs):
+                occ[i + 1] = masks[j]
+    frames = []
+    for i, ip in enumerate(p["img"]):
+        fr = dict(image=image[i], focal=focal, pp=pp, name=os.path.basename(ip).split(".")[0], depth=depth[i])
+        H, W = fr["image"].shape[:2]
+        fr["move_mask"] = move[i] if move[i] is not None else torch.zeros(H, W, dtype=torch.bool, device=device)
+        if i < len(p["flow"]):
+            fr["flow"] = flow[i]                   # (None for a file with a bad magic number, as read_flow gives)
+        else:
+            fr["flow"] = torch.zeros(H, W, 2, device=device)
+        if occ[i] is not None:
+            fr["occ_mask"] = occ[i]
+        if i < len(poses):
+            fr["extr"] = torch.tensor(poses[i], dtype=torch.float32)
+        frames.append(fr)
+    # what upload_clip counts on the host, one frame at a time: here one read-back for the clip
+    with_occ = [fr for fr in frames if "occ_mask" in fr]
+    if with_occ:
+        counts = torch.stack([(fr["occ_mask"][..., 0] > 0).sum() for fr in with_occ]).cpu()
+        for fr, c in zip(with_occ, counts.tolist()):
+            fr["occ_count"] = int(c)
     return frames
 
 

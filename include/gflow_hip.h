@@ -107,7 +107,8 @@ typedef enum gfl_status {
  * 310: gfl_flow_pair, gfl_flow_workspace_bytes.  311: gfl_fit_workspace_layout.  312: gfl_epi_fundamental, gfl_epi_mask,
  * gfl_epi_workspace_bytes; gfl_flow_occlusion was added WITHIN 312 (an additive entry: nothing that existed changed, so the
  * number stays; a binding that needs it looks the symbol up).  gfl_track_history, gfl_track_backward and
- * gfl_track_backward_workspace_bytes were added WITHIN 312 in the same way.
+ * gfl_track_backward_workspace_bytes were added WITHIN 312 in the same way, and so were gfl_track_vis and gfl_prep_frames with
+ * their workspace queries.
  * A binding checks gfl_version() >= GFL_VERSION of the header it was written for. */
 #define GFL_VERSION 312
 int gfl_version(void);
@@ -772,6 +773,44 @@ size_t gfl_track_vis_workspace_bytes(int T, int N, int W, int H, int K_cap);
 int gfl_track_vis(const uint8_t* video, const float* tracks, const uint8_t* occluded, int T, int N, int W, int H,
                   int still_length, const float* lut, int K_cap, uint8_t* out, int32_t* overflow, void* workspace,
                   size_t workspace_bytes, gfl_stream_t stream);
+
+/* ---- frame preparation (additive within 312; gflow_amd/prep.py, INTEGRATION.md "Frame preparation") ----------------------
+ * What the reference does to every file of a sequence after decoding it (gflow/utils/conversion.py:6-19, read.py:7-70,
+ * fit_video.py:245-248): to float, torchvision's Resize(n, antialias=True), optionally GaussianBlur(7, 5.0), then depth's
+ * scale and offset or the mask test -- for T frames of one shape in one call.
+ *   src [T][Hs][Ws][C] uint8 (src_is_u8 = 1) or float32 (0; 4-byte aligned), interleaved as PIL, .flo and .npy give it;
+ *   dst [T][Hd][Wd][C] float32, or with as_mask [T][Hd][Wd] uint8 holding 0 or 1.  Per frame and channel, in this order:
+ * (a) convert: v = (float)src / div, correctly rounded (div = 255 for 8-bit images, 1 otherwise).
+ * (b) resize, unless (Hd, Wd) == (Hs, Ws): bilinear with antialiasing, align_corners = False, the horizontal pass, then the
+ *   vertical one.  Per axis, with s = n_in / n_out, support = max(s, 1), inv = 1 / support, output i has the centre
+ *   c = s (i + 0.5), reads the taps j in [lo, hi), lo = max(0, (int)(c - support + 0.5)), hi = min((int)(c + support + 0.5),
+ *   n_in), with the weights w_j = max(0, 1 - |(j - c + 0.5) inv|) divided by their sum over the taps: all of it in float64,
+ *   every operation rounded on its own (nothing fused), the normalised weight then rounded to float32.  A pass is the
+ *   float32 sum of w_j v_j in ascending j, product and sum rounded separately.
+ *   torch's CPU kernel (F.interpolate(mode="bilinear", antialias=True)) is the SAME filter with float32 weights formed from
+ *   float32 coordinates.  Measured against it: values differ by up to 2.8e-6 at 240 columns, growing with the coordinate; a
+ *   mask (> 0 after the resize) differs in 1-3 % of its pixels at non-dyadic scales (31x47 -> 7x10, 13x29 -> 5x11, 33x59 ->
+ *   13x23; random masks, 3 % set) -- the pixels where a source pixel sits exactly on the edge of the support -- and in none
+ *   at the scales 2.0, 2.5, 2.25 or at an upscale of 1.5.  What torch computes there is not reproducible bit for bit; this is.
+ * (c) blur, when blur_k > 0 (odd, 3 .. 31, blur_k / 2 < min(Hd, Wd); blur_sigma finite and > 0): the taps
+ *   exp(-0.5 (x / sigma)^2) at x = -(k - 1) / 2 .. (k - 1) / 2, normalised in float64 and rounded to float32; reflect padding
+ *   (index -i reads i, the edge is not repeated); the horizontal pass, then the vertical one, float32 sums in ascending tap
+ *   order.
+ * (d) output: r mul + add, a multiply and an add rounded separately (read_depth's * depth_scale + depth_offset; skipped for
+ *   mul = 1, add = 0).  With as_mask: 1 where the channels' sum in ascending c is > 0, else 0 (a NaN gives 0); blur_k, mul and
+ *   add must then be 0, 1 and 0.
+ * GFL_ERR_INVALID, before anything is launched: T < 1, C outside 1 .. 4, an extent < 1 or > 16384, n_in > 64 n_out on an
+ * axis, more than 2^31 - 1 elements in src, in the horizontal intermediate [T][Hs][Wd][C] or in dst, a div that is not
+ * finite and > 0, a mul or add that is not finite, a bad blur_k or blur_sigma, src_is_u8 or as_mask that is not 0 or 1, a NULL
+ * src, dst or workspace, a float32 src or dst that is not 4-byte aligned, a workspace that is not 16-byte aligned or is
+ * smaller than gfl_prep_workspace_bytes (0 for arguments it rejects).
+ * The launches are fixed by the arguments alone: the tables (one launch: the 256 conversions of a uint8 source and the two
+ * axes' taps), the two resize passes -- or one conversion launch where the resize is skipped --, and the two blur passes
+ * when on.  No atomics, no allocation, no host synchronisation, everything on `stream`; the same inputs give the same bits. */
+size_t gfl_prep_workspace_bytes(int T, int C, int Hs, int Ws, int Hd, int Wd, int blur_k);
+int gfl_prep_frames(const void* src, int src_is_u8, int T, int C, int Hs, int Ws, int Hd, int Wd, float div, float mul,
+                    float add, int blur_k, float blur_sigma, int as_mask, void* dst, void* workspace, size_t workspace_bytes,
+                    gfl_stream_t stream);
 
 /* sizeof(gfl_fit_state), sizeof(gfl_fit_hyper): lets an FFI binding verify its struct mirrors */
 int gfl_abi_sizes(int* sizeof_fit_state, int* sizeof_fit_hyper);
