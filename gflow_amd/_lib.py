@@ -79,6 +79,8 @@ SIGNATURES = {
     "gfl_render_bwd_cam": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gfl_render_batch_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "gfl_render_batch": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "gfl_compose_rows_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "gfl_compose_rows": (c_int, [_P, _P, c_int, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "gfl_fit_prepare_targets": (c_int, [_P, _P]),
     "gfl_fit_schedule_info": (c_int, [_P, _P, _P, _P, _P]),
     "gfl_fit_schedule_info_fwd": (c_int, [_P, _P, _P, _P, _P]),

@@ -63,7 +63,7 @@ def _release(slot, token):
 
 
 def check_overflow():
-    """Blocking: raises if ANY render of the fused operator -- or any batched call (render_views / render_jobs / render_block) --
+    """Blocking: raises if ANY render of the fused operator -- or any batched call (render_views / render_jobs / render_block / render_composed) --
     so far dropped splat-tile pairs (the operator itself looks at
     the flag without stopping the host: at the backward of the same render, and at the next render on the same engine).
     Call it after the last render of a program whose result matters."""
@@ -401,6 +401,92 @@ def render_block(block, ranges, intr, extr, bg, W, H, uint8=False, records=False
     res = {"img": img} if uint8 else {"rgb": out[:, :3], "depth_map": out[:, 3:4]}
     if records:
         res["rec"] = rec[:sum(per_job)]
+    return res
+
+
+def _job_table(values, dtype, width, dev):
+    """A small per-job table on the device: a device tensor is taken as it is; host values whose rows are all alike are made
+    with fills (nothing is copied from the host: such a call can be captured), others go through page-locked memory."""
+    if torch.is_tensor(values):
+        return values.detach().to(dev).to(dtype).reshape(-1, width).contiguous()
+    rows = [tuple(r) if width > 1 else (r,) for r in values]
+    if len(set(rows)) <= 1:
+        out = torch.zeros(len(rows), width, dtype=dtype, device=dev)
+        for k, x in enumerate(rows[0] if rows else ()):
+            if x:
+                out[:, k].fill_(x)
+        return out
+    return torch.tensor(rows, dtype=dtype).pin_memory().to(dev, non_blocking=True)
+
+
+def render_composed(block, labels, job_src, job_s, job_edit, intr, extr, bg, W, H, rows_max, uint8=False, rows=False):
+    """In-between frames, layers and group edits of a clip's row block, rendered: gfl_compose_rows (include/gflow_hip.h) makes
+    every job's rows on the device -- frame a blended with frame b at s, the group edits applied, invisible rows dropped --
+    and gfl_render_batch renders them where the composer left them.  block: [R][16] float32 ACTIVATED rows (rows_block);
+    labels: (R,) uint8 on the device, a group per row (0 still, 1 moving), or None; job_src: J rows (first_a, count_a, first_b,
+    count_b) or (J, 4) int32 on the device; job_s: J floats in [0, 1] or a tensor; job_edit: (J, G, 16) float32 on the device
+    (viewer.Edit.table) or None; intr, extr, bg as render_block takes them; rows_max: room per job, at least the longest
+    range.  Returns what render_block returns, and with ``rows`` also out_rows (J * rows_max, 16) and out_job_rows (J, 2) =
+    (j * rows_max, rows kept).  NOT differentiable.  Nothing here waits for the device; a source range outside the block, or
+    longer than rows_max, and dropped pairs raise at the next batched call or in check_overflow()."""
+    L.need_device(block)
+    lib = L.load()
+    dev = block.device
+    W, H, rows_max = int(W), int(H), int(rows_max)
+    block = block.detach()
+    if block.dtype != torch.float32 or not block.is_contiguous() or block.dim() != 2 or block.shape[1] != 16:
+        raise ValueError("gflow_amd.render: the row block is [R][16] float32, contiguous")
+    R = block.shape[0]
+    if labels is not None:
+        L.need_device(labels)
+        if labels.dtype != torch.uint8 or labels.numel() != R or not labels.is_contiguous():
+            raise ValueError("gflow_amd.render: labels are (R,) uint8, contiguous")
+    src = _job_table(job_src, torch.int32, 4, dev)
+    J = src.shape[0]
+    s = _job_table(job_s, torch.float32, 1, dev)
+    G = 1
+    if job_edit is not None:
+        L.need_device(job_edit)
+        if job_edit.dtype != torch.float32 or not job_edit.is_contiguous() or job_edit.dim() != 3 or job_edit.shape[0] != J \
+                or job_edit.shape[2] != 16:
+            raise ValueError("gflow_amd.render: the edit table is [J][G][16] float32, contiguous")
+        G = job_edit.shape[1]
+    if s.shape[0] != J:
+        raise ValueError(f"gflow_amd.render: {J} jobs, but {s.shape[0]} blend weights")
+    ws = _batch_ws(W, H, dev)
+    ws.check()
+    img = torch.empty(J, H, W, 3, dtype=torch.uint8, device=dev) if uint8 else None
+    out = None if uint8 else torch.empty(J, 4, H, W, dtype=torch.float32, device=dev)
+    out_rows = torch.empty(max(J * rows_max, 1), 16, dtype=torch.float32, device=dev)
+    job_rows = torch.empty(J, 2, dtype=torch.int32, device=dev)
+    if J:
+        cams = _job_cams(J, intr, extr, bg, dev)
+        flags = torch.empty(J, dtype=torch.int32, device=dev)
+        ovf = torch.empty(J, dtype=torch.int32, device=dev)
+        buf = ws.room(lib.gfl_compose_rows_workspace_bytes(J, rows_max))
+        L.check(lib.gfl_compose_rows(L.ptr(block), L.ptr(labels), R, L.ptr(src), L.ptr(s), L.ptr(job_edit), G, J, rows_max,
+                                     L.ptr(out_rows), L.ptr(job_rows), L.ptr(flags), L.ptr(buf), buf.numel(), L.stream()),
+                "compose_rows")
+        # the composer's rows are the rasteriser's block: R = J * rows_max, job j's range is out_job_rows[j]
+        T = ((W + 15) // 16) * ((H + 15) // 16)
+        k_job = batch_k_cap(rows_max)
+        step = max(1, min(int(BATCH_MAX_JOBS), int(BATCH_MAX_TILES) // T, int(BATCH_MAX_PAIRS) // k_job))
+        k_used = 0
+        for a in range(0, J, step):
+            b = min(J, a + step)
+            rows_total = (b - a) * rows_max
+            k_cap = k_job * (b - a)
+            k_used = max(k_used, k_cap)
+            buf = ws.room(lib.gfl_render_batch_workspace_bytes(b - a, rows_total, k_cap, W, H))
+            L.check(lib.gfl_render_batch(L.ptr(out_rows), J * rows_max, L.ptr(job_rows[a:b]), L.ptr(cams[a:b]), b - a, rows_total,
+                                         W, H, k_cap, L.ptr(out[a:b]) if out is not None else None,
+                                         L.ptr(img[a:b]) if img is not None else None, None, L.ptr(ovf[a:b]), L.ptr(buf),
+                                         buf.numel(), L.stream()), "render_batch")
+        torch.maximum(ovf, flags, out=ovf)           # (one watched word per job: 2 from either side is a refused range)
+        ws.watch(ovf, k_used)
+    res = {"img": img} if uint8 else {"rgb": out[:, :3], "depth_map": out[:, 3:4]}
+    if rows:
+        res["out_rows"], res["out_job_rows"] = out_rows[:J * rows_max], job_rows
     return res
 
 

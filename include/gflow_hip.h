@@ -457,6 +457,37 @@ size_t gfl_render_batch_workspace_bytes(int J, int rows_total, int K_cap, int W,
 int gfl_render_batch(const float* params, int R, const int32_t* job_rows, const float* job_cam, int J, int rows_total, int W,
                      int H, int K_cap, float* out_f32, uint8_t* out_u8, float* out_rec, int32_t* overflow, void* workspace,
                      size_t workspace_bytes, gfl_stream_t stream);
+/* ---- row composer (additive within 312): in-between frames, still / moving layers and group edits ---------------
+ * The rows of a clip fit keep their index from frame to frame (densification only appends), so two frames of a clip blend row
+ * by row.  A job makes the rows of time a + s from the rows of frames a and b, applies an edit per group, and leaves them where
+ * gfl_render_batch reads them: params = out_rows, R = rows_total = J rows_max, job_rows = out_job_rows.
+ *   params   [R][16]     ACTIVATED rows, gfl_render_fwd's column layout
+ *   labels   [R]         a group per row, 0 = still, 1 = moving; NULL = every row in group 0
+ *   job_src  [J][4]      device: first_a, count_a, first_b, count_b (ranges may overlap or repeat)
+ *   job_s    [J]         device: s in [0, 1]
+ *   job_edit [J][G][16]  device, 16-byte aligned, or NULL for no edits; 1 <= G <= 8; an entry is
+ *                        gain | size | q wxyz (unit) | pivot xyz | shift xyz | tint rgb | mix
+ *   out_rows [J rows_max][16];  out_job_rows [J][2] = (j rows_max, rows kept)
+ *   flags    [J]         device: 2 = a source range leaves [0, R) or max(count_a, count_b) > rows_max (the job keeps 0 rows), else 0
+ * Source index i in [0, max(count_a, count_b)):  in both ranges, xyz, scale, opacity and rgb are fmaf(s, b - a, a), and the
+ * quaternion is the same lerp of a's and b's -- b's negated when its dot with a's is negative --, normalised; s == 0 gives a's
+ * row and s == 1 b's, bit for bit.  Only in b (a row appended at frame b): b's row with opacity x s.  Only in a: a's row with
+ * opacity x (1 - s).  The row's group is the label of its a row when it has one, else of its b row, and its edit is
+ * job_edit[j][group]; a group >= G, or no table, is the identity (nothing is touched).  opacity' = min(opacity gain, 1);
+ * rgb' = fmaf(mix, tint - rgb, rgb); and unless size == 1, q == (+-1, 0, 0, 0) and shift == 0 exactly (xyz, scale and rotate
+ * then keep their bits): xyz' = fmaf(size, R(q)(xyz - pivot), pivot) + shift, scale' = size scale, rotate' = normalise(q (x) rotate).
+ * A row with opacity' <= 0 is dropped; the others are written compacted in ascending i.  A row's place is a function of the
+ * keep decisions before it alone (wave ballots, popcounts and a prefix over the chunks of 256 rows; no atomic decides a place):
+ * the same bytes alone, first, last or between other jobs, run after run, and nothing is written outside
+ * [j rows_max, j rows_max + kept) of out_rows.  The tables are read on the device, nothing is read back or allocated, and the
+ * call is three launches whatever J, the counts or the data are: it can be captured into a graph on one stream in front of the
+ * gfl_render_batch it feeds.  J == 0 succeeds and writes nothing.  GFL_ERR_INVALID, before anything touches a device: J, R or
+ * rows_max < 0, G outside 1 .. 8 with a table, a required pointer NULL, J rows_max beyond 2^31 - 1 or more than 2^30 (job, chunk) pairs, a workspace smaller than
+ * gfl_compose_rows_workspace_bytes (0 for arguments it rejects). */
+size_t gfl_compose_rows_workspace_bytes(int J, int rows_max);
+int gfl_compose_rows(const float* params, const uint8_t* labels, int R, const int32_t* job_src, const float* job_s,
+                     const float* job_edit, int G, int J, int rows_max, float* out_rows, int32_t* out_job_rows, int32_t* flags,
+                     void* workspace, size_t workspace_bytes, gfl_stream_t stream);
 /* The three snapshot images GFlow keeps every 10th iteration (trainer.py:573-582) in one call, entirely on the
  * device: rgb of the last forward, the turbo-coloured depth map and the centre blobs (render.py:76-106; both composites
  * of the same lists, the per-splat values are derived while the records are staged), each clamped, scaled by 255 and
