@@ -78,6 +78,9 @@ def _parser():
                     help="paint the tracks over every frame's render on the device (the reference's trajectory visualiser) and "
                          "write DIR/clip_<i>/<name>/<frame>.png: with --track `pred` and `gt` (the ground-truth tracks and "
                          "occlusion flags), with --traj-num `seeds`, `seeds_still`, `seeds_move`")
+    ap.add_argument("--video", action="store_true",
+                    help="with --track-vis: also write every overlay as DIR/clip_<i>/<name>.avi beside its folder of PNGs, a "
+                         "Motion-JPEG AVI at 5 fps coded on the device (gflow_amd.video)")
     ap.add_argument("--traj-num", type=int, default=0,
                     help="trajectory seeds per clip (cfg traj_num; the reference's scripts use 100)")
     ap.add_argument("--seg", action="store_true",
@@ -118,6 +121,8 @@ def _check_args(ap, args):
         ap.error("--track-backward needs --track")
     if args.track_vis and not (args.track or args.traj_num > 0):
         ap.error("--track-vis needs --track or --traj-num")
+    if args.video and not args.track_vis:
+        ap.error("--video needs --track-vis")
     if args.track and args.track_queries == "strided" and not args.track_backward:
         print("warning: --track-queries strided without --track-backward: every frame before a query is a miss",
               file=sys.stderr)
@@ -251,6 +256,8 @@ def _report(args, results, wall, clips, gts, queries, dropped, rank, world, over
         for ci, vis in of("track_vis").items():
             for name, imgs in vis.items():
                 TV.write_frames(imgs, os.path.join(args.track_vis, f"clip_{ci}", name))
+                if args.video:
+                    TV.write_video(imgs, os.path.join(args.track_vis, f"clip_{ci}", name + ".avi"))
     if args.seg:
         out["davis"] = reduce_davis(of("segmentation"), *over_ranks)
         if args.seg_out:

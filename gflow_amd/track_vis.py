@@ -133,6 +133,17 @@ def write_frames(images, dir):
     return paths
 
 
+def write_video(images, path, fps=5):
+    """``images`` (T, H, W, 3) uint8 (device tensor or array) as ONE file: a Motion-JPEG AVI at ``fps`` (5: the reference's
+    save_video, traj_visualizer.py:171), the frames coded on the device (gflow_amd.video.write_avi; INTEGRATION.md, "Video
+    files").  Returns dict(frames, bytes)."""
+    from . import video
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    return video.write_avi(path, images, fps=fps)
+
+
 def clip_overlays(video, pred=None, seeds=None, extra=None):
     """What ``fit_clip(track_vis=...)`` adds: a dict of (T, H, W, 3) uint8 host arrays, drawn on the device over ``video``
     ((T, H, W, 3) uint8 on the device) and copied to the host together.

@@ -10,6 +10,7 @@ command line that writes a path's images with PIL:
 
     python -m gflow_amd.viewer --folder LOG --path follow|fixed:T|offset:dx,dy,dz|orbit:T,N,R|lerp:A,B,N --out DIR
                                [--format png|jpeg] [--gpu 0] [--slowmo K] [--layer all|still|moving] [--edit TEXT ...]
+                               [--video FILE.avi [--fps 5] [--quality 90]]      (one Motion-JPEG AVI; --out is then optional)
 
 The rows of a clip fit keep their index from frame to frame and carry a still / moving label, so the session also shows the
 clip BETWEEN its frames, one layer of it, or a group of it moved, turned, resized, tinted or hidden (``frame_at`` / ``play_at``,
@@ -533,8 +534,12 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description="render a camera path through a saved fit to image files")
     ap.add_argument("--folder", required=True, help="log folder (holds ckpt/*.tar)")
     ap.add_argument("--path", default="follow", help="follow | fixed:T | offset:dx,dy,dz | orbit:T,N,R | lerp:A,B,N")
-    ap.add_argument("--out", required=True, help="directory the images are written to")
+    ap.add_argument("--out", default=None, help="directory the images are written to (needed unless --video is given)")
     ap.add_argument("--format", default="png", choices=("png", "jpeg"))
+    ap.add_argument("--video", default=None, metavar="FILE.avi",
+                    help="write the path as ONE Motion-JPEG AVI, coded on the device (gflow_amd.video), instead of images")
+    ap.add_argument("--fps", type=float, default=5, help="with --video: frames per second of the file")
+    ap.add_argument("--quality", type=int, default=90, help="with --video: JPEG quality, 1 .. 100")
     ap.add_argument("--gpu", type=int, default=0)
     ap.add_argument("--slowmo", type=int, default=0, metavar="K",
                     help="K images per frame step: the times 0, 1/K, ... of the clip, rows and cameras blended in between "
@@ -544,6 +549,8 @@ def main(argv=None):
                     help="GROUP:key=value;... with GROUP still | moving | 0..7 and the keys gain, size, turn=AXIS,DEGREES, "
                          "pivot=x,y,z, shift=x,y,z, tint=r,g,b,MIX; may be given several times")
     args = ap.parse_args(argv)
+    if not args.out and not args.video:
+        ap.error("one of --out and --video is needed")
     kind, pargs = parse_path(args.path)
     edits = [parse_edit(t) for t in args.edit]
     if args.slowmo < 0 or (args.slowmo and kind not in ("follow", "fixed", "offset")):
@@ -559,6 +566,17 @@ def main(argv=None):
         imgs = session.play_at(frames, extrs, args.layer, edits)
     else:
         imgs = session._render(frames, extrs)
+    if args.video:
+        # the images stay on the device until they are the file's bytes
+        from . import video
+        session._R.check_overflow()
+        d = os.path.dirname(args.video)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        info = video.write_avi(args.video, imgs, fps=args.fps, quality=args.quality)
+        print(f"{info['frames']} frames of {session.W}x{session.H} at {args.fps:g} fps -> {args.video}  ({info['bytes']} bytes)")
+        if not args.out:
+            return 0
     imgs = imgs.cpu().numpy()
     session._R.check_overflow()
     os.makedirs(args.out, exist_ok=True)

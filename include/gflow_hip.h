@@ -108,7 +108,7 @@ typedef enum gfl_status {
  * gfl_epi_workspace_bytes; gfl_flow_occlusion was added WITHIN 312 (an additive entry: nothing that existed changed, so the
  * number stays; a binding that needs it looks the symbol up).  gfl_track_history, gfl_track_backward and
  * gfl_track_backward_workspace_bytes were added WITHIN 312 in the same way, and so were gfl_track_vis and gfl_prep_frames with
- * their workspace queries.
+ * their workspace queries, and the four gfl_jpeg_* entries.
  * A binding checks gfl_version() >= GFL_VERSION of the header it was written for. */
 #define GFL_VERSION 312
 int gfl_version(void);
@@ -842,6 +842,38 @@ size_t gfl_prep_workspace_bytes(int T, int C, int Hs, int Ws, int Hd, int Wd, in
 int gfl_prep_frames(const void* src, int src_is_u8, int T, int C, int Hs, int Ws, int Hd, int Wd, float div, float mul,
                     float add, int blur_k, float blur_sigma, int as_mask, void* dst, void* workspace, size_t workspace_bytes,
                     gfl_stream_t stream);
+
+/* ---- video files (additive within 312; gflow_amd/video.py, INTEGRATION.md "Video files") ---------------------------------
+ * Baseline sequential JPEG (ITU-T T.81, 8 bits per sample) of T images of one shape in two calls: the entropy-coded SCAN of
+ * every image.  The host puts the header in front (gflow_amd.video.jpeg_header) and EOI behind.
+ *   images [T][H][W][C] uint8, C = 3 (R, G, B -> YCbCr 4:4:4, an MCU is the blocks Y, Cb, Cr) or C = 1 (one grey component);
+ *   qtables [2][64] uint16 on the device, natural (row-major) order: [0] luminance / grey, [1] chrominance; 0 counts as 1.
+ * Arithmetic, float32, nothing rounded to integers on the way: Y = 0.299 R + 0.587 G + 0.114 B - 128,
+ *   Cb = -0.168736 R - 0.331264 G + 0.5 B, Cr = 0.5 R - 0.418688 G - 0.081312 B (JFIF, level shift included; grey: v - 128);
+ *   the separable 8x8 DCT-II of A.3.3, rows then columns; coefficient = F / q rounded half away from zero; zigzag.  A block
+ *   that hangs over the right or bottom edge repeats the last column / row.
+ * Entropy coding: Annex K's four Huffman tables (K.3 - K.6), fixed.  The scan is cut into restart intervals of
+ *   GFL_JPEG_RI MCUs in scan order (not per MCU row; a frame's last interval is shorter): each is a byte-aligned bit stream,
+ *   padded with 1-bits, whose DC prediction starts from 0, FF stuffed as FF 00, followed -- except the frame's last -- by
+ *   RSTm, m = (interval index) mod 8.  One workgroup codes one (frame, interval); the bytes depend on the inputs alone.
+ * gfl_jpeg_sizes codes every interval, keeps its length, and scans the lengths: the interval offsets stay in the workspace,
+ *   frame_offsets [T + 1] int64 on the device = where frame t's scan starts in `out`, [T] = the total.  gfl_jpeg_emit (same
+ *   images, shape, qtables and workspace, after gfl_jpeg_sizes on the same stream) codes again through the same routine and
+ *   writes every interval at its offset: exactly frame_offsets[T] bytes.  An interval that would end behind out_bytes is not
+ *   written at all -- nothing is ever stored outside [out, out + out_bytes).
+ * GFL_ERR_INVALID, before any launch: a NULL pointer, C not 1 or 3, T, W or H < 1, W or H > 65535, more than 2^30
+ *   (frame, interval) pairs, out_bytes < 1, a workspace or frame_offsets that is not 8-byte aligned.  GFL_ERR_WORKSPACE:
+ *   workspace_bytes < gfl_jpeg_workspace_bytes (0 for arguments it rejects).  No allocation, no host synchronisation;
+ *   gfl_jpeg_restart_interval and gfl_jpeg_workspace_bytes need no device. */
+#ifndef GFL_JPEG_RI
+#define GFL_JPEG_RI 32
+#endif
+int gfl_jpeg_restart_interval(void);
+size_t gfl_jpeg_workspace_bytes(int T, int C, int W, int H);
+int gfl_jpeg_sizes(const uint8_t* images, int T, int C, int W, int H, const uint16_t* qtables, int64_t* frame_offsets,
+                   void* workspace, size_t workspace_bytes, gfl_stream_t stream);
+int gfl_jpeg_emit(const uint8_t* images, int T, int C, int W, int H, const uint16_t* qtables, uint8_t* out, int64_t out_bytes,
+                  void* workspace, size_t workspace_bytes, gfl_stream_t stream);
 
 /* sizeof(gfl_fit_state), sizeof(gfl_fit_hyper): lets an FFI binding verify its struct mirrors */
 int gfl_abi_sizes(int* sizeof_fit_state, int* sizeof_fit_hyper);
