@@ -217,18 +217,24 @@ class ClipFit:
         self.traj_rec = [] if self.traj else None        # per frame: where the seeds are, the camera, the scene's rgb image
         # the trajectory seeds (select_traj_seeds, after the first frame's fit): their rows, those on the device, the split
         self.traj_index = self.traj_index_t = self.split_interval = None
-        self.final = None                                # this frame's final_forward, once it has run (end_of_frame forgets it)
+        self.final = None                                # the engine of this frame's final_forward, once it has run (end_of_frame forgets it)
         self.psnr_sum = None
 
-    def final_forward(self):
+    def final_forward(self, scene=False):
         # The forward of THIS frame's final state on the second engine (fused path): run when the first of the frame's
-        # recorders asks for it, shared by those after it -- the frame is rasterised once more, not once per recorder.  (The
-        # trajectory recorder asks first and has the scene's images taken from it: see there.)
+        # recorders asks for it, shared by those after it -- the frame is rasterised once more, not once per recorder.
+        # Returns (that engine, None); the reader that runs it may ask for the scene's images too (``scene=True``, the
+        # trajectory recorder, which asks first): (the engine, (3, H, W, 3) uint8) -- the forward, the snapshot of its images,
+        # then the overflow watch.
+        tr, images = self.tr, None
         if self.final is None:
-            self.final = self.tr._aux_forward()
-            self.final.watch_overflow()
-            self.tr.rasterisations_done += 1
-        return self.final
+            if scene:
+                images = tr.second.scene_u8(tr.engine, tr.bg)
+            else:
+                tr.second.forward(tr.engine, tr.bg).watch_overflow()
+            self.final = tr.second.engine
+            tr.rasterisations_done += 1
+        return self.final, images
 
     def record_trajectories(self):
         # fit_video.py:226-238 / 335-349 call trainer.eval + project_points here, after every frame.  What they need of THIS
@@ -241,13 +247,11 @@ class ClipFit:
             xyz_now = tr.get_attribute("xyz")[self.traj_index_t].detach().float().clone()
             extr_now = tr.get_extr().detach().clone()
             if tr.engine_current:
-                # (the frame's forward, the snapshot of its images, then the overflow watch: final_forward's forward with
-                #  the snapshot in between, so it is handed to final_forward's readers)
-                rgb_u8 = tr._render_scene_fused()[0].clone()
-                self.final = tr._aux
+                _, scene = self.final_forward(scene=True)            # (its readers behind this one share the forward)
+                rgb_u8 = scene[0].clone()
             else:
                 rgb_u8 = render_mod.render2img_device(render_mod.render_multiple(tr._input_group(detach=True), ["rgb"])["rgb"])
-            tr.rasterisations_done += 1
+                tr.rasterisations_done += 1
         self.traj_rec.append((xyz_now, extr_now, rgb_u8))
 
     def record_tracks(self, i):
@@ -256,7 +260,7 @@ class ClipFit:
         tr, keep = self.tr, self.keep
         with torch.no_grad():
             if tr.engine_current:
-                aux = self.final_forward()
+                aux, _ = self.final_forward()
                 n = aux.N
                 uv, uv_stride, depth, depth_stride, dm = aux.rec[:n, 0:2], REC, aux.rec[:n, 9], REC, aux.render[3]
             else:
@@ -275,7 +279,7 @@ class ClipFit:
         tr = self.tr
         with torch.no_grad():
             if tr.engine_current:
-                aux = self.final_forward()
+                aux, _ = self.final_forward()
                 rec, n, ids, tile_range = aux.rec, aux.N, aux.ids, aux.tile_range
             else:
                 rec, n, ids, tile_range = FL.operator_state(tr._input_group(detach=True))

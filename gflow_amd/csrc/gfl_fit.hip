@@ -361,7 +361,7 @@ int gfl_fit_snapshot(const gfl_fit_state* st, const gfl_fit_hyper* hp, const flo
     rc = check(hipMemsetAsync(workspace, 0, sw.head_bytes, s));
     if (rc) return rc;
     if (st->N > 0) launch_rec_depth_range(st->rec, st->N, sw.mm, s);
-    // center first: a kernel of its own (gfl_fit_fwd.hip), short-lived workgroups.  On a side stream (trainer.py: _snapshot_async)
+    // center first: a kernel of its own (gfl_fit_fwd.hip), short-lived workgroups.  On a side stream (companion.py: SnapshotShadow)
     // these launches run beside the NEXT iteration's binning and tile sort, and the persistent workgroups of the blend kernel
     // below hold every CU's registers for their ~50 us: the tile sort beside them took 44 us instead of 14
     // (tools/snapshot_gaps.py); behind this kernel they start when that iteration is past its sort.

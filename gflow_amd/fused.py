@@ -227,7 +227,6 @@ class FitEngine:
         self._reserved_sup = (None, 0)                   # (W, H, K_cap) the library was asked about, its answer (_reserved_flag)
         self.regions_outgrown = self.pairs_grown = 0     # void iterations made up for; times the pair lists were doubled
         self._pend, self._ovf = DeferredRead(5), DeferredRead(1)     # watch_pending, watch_overflow
-        self._snap_ring = self._snap_ring_done = None    # snapshot_ring / snapshot_ring_copied
         self._snap_out = self._snap_ws = None            # the image buffer of iteration(snapshot=True), snapshot()'s workspace
         self._launched = False
         self._reserved_N = -1          # N of the last full iteration whose last launch reserved the next one's tile regions
@@ -387,23 +386,6 @@ class FitEngine:
             self._state.flags = GFL_FIT_DETERMINISTIC if self._deterministic else 0
 
     # -------------------------------------------------------------------- calls
-    def snapshot_ring(self, rows):
-        """(rows, 3, H, W, 3) uint8 on the device: where a train() call keeps its snapshots until its end
-        (stage.RingSink).  One ring per engine, grown on demand; the current stream waits for the copy that emptied
-        it last (``snapshot_ring_copied``)."""
-        ring = self._snap_ring
-        if ring is None or ring.shape[0] < rows:
-            ring = torch.empty(int(rows), 3, self.H, self.W, 3, dtype=torch.uint8, device=self.dev)
-            self._snap_ring = ring
-        if self._snap_ring_done is not None:
-            torch.cuda.current_stream().wait_event(self._snap_ring_done)
-        return ring[:rows]
-
-    def snapshot_ring_copied(self):
-        """call on the stream that has just been given the ring's device-to-host copy"""
-        self._snap_ring_done = torch.cuda.Event()
-        self._snap_ring_done.record()
-
     def forward(self):
         L.check(self.lib.gfl_fit_forward(ctypes.byref(self.state()), ctypes.byref(self.hp), L.stream()), "fit forward")
 
@@ -473,6 +455,13 @@ class FitEngine:
         L.check(self.lib.gfl_fit_snapshot(ctypes.byref(self.state()), ctypes.byref(self.hp), L.ptr(lut("turbo", self.dev)),
                                           L.ptr(out), L.ptr(self._snap_ws), self._snap_ws.numel(), L.stream()), "snapshot")
         return out
+
+    def stage_forward_to(self, dst):
+        """What the last forward left behind (records, sorted ids, tile ranges, the render, the forward's tile queues, the
+        camera) copied into the engine ``dst`` in one launch on the current stream (gfl_fit_snapshot_stage): ``dst.snapshot()``
+        then composes this engine's images (companion.SnapshotShadow)."""
+        L.check(self.lib.gfl_fit_snapshot_stage(ctypes.byref(self.state()), ctypes.byref(dst.state()), L.stream()),
+                "snapshot stage")
 
     # ------------------------------------------------------------- saved states
     _STATE_TENSORS = ("step", "pose", "pose_m", "pose_v", "depth_ab", "ab_m", "ab_v")

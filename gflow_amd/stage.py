@@ -1,5 +1,5 @@
 """One ``train`` call of the per-frame optimiser (SimpleGaussian.make_stepper): what happens at which iteration (StagePlan),
-where the snapshots go (RingSink / ListSink), the iteration loop on the fused and on the operator path."""
+where the snapshots go (RingSink on a SnapshotRing / ListSink), the iteration loop on the fused and on the operator path."""
 from types import SimpleNamespace
 
 import torch
@@ -37,7 +37,7 @@ class StagePlan(SimpleNamespace):
 
 class ListSink:
     """The operator path's snapshots: lists (rgb, depth colour, centre) of uint8 device images, copied at the end."""
-    copy_stream = snap_stream = None
+    copy_stream = None
 
     def __init__(self):
         self.lists = ([], [], [])
@@ -54,6 +54,28 @@ class ListSink:
         return [[f for f in torch.stack(lst).cpu().numpy()] if lst else [] for lst in self.lists]
 
 
+class SnapshotRing:
+    """(rows, 3, H, W, 3) uint8 on the device: where a train() call keeps its snapshots until its end (RingSink).  One ring per
+    trainer, reused by its train() calls and grown on demand; ``done``: the event of the copy that emptied it last."""
+
+    def __init__(self, H, W, dev):
+        self.H, self.W, self.dev = H, W, dev
+        self.buf = self.done = None
+
+    def rows(self, n):
+        """the first ``n`` rows; the current stream waits for the copy that emptied the ring last (``copied``)"""
+        if self.buf is None or self.buf.shape[0] < n:
+            self.buf = torch.empty(int(n), 3, self.H, self.W, 3, dtype=torch.uint8, device=self.dev)
+        if self.done is not None:
+            torch.cuda.current_stream().wait_event(self.done)
+        return self.buf[:n]
+
+    def copied(self):
+        """call on the stream that has just been given the ring's device-to-host copy"""
+        self.done = torch.cuda.Event()
+        self.done.record()
+
+
 class RingSink(ListSink):
     """The fused path's snapshots: the lists hold views of a page-locked block, one per snapshot taken."""
     # They stay on the DEVICE until the end of this train() call (a ring of uint8 images in HBM: 3.7 MB each at
@@ -63,12 +85,14 @@ class RingSink(ListSink):
     # per 74 us copy); at the end of the call it runs beside the host's set-up of the next stage, when the
     # device has little else to do.  (The reference blocks on three device-to-host copies right here.)
 
-    def __init__(self, eng, plan, H, W, dev):
+    def __init__(self, store, shadow, plan, H, W, dev):
+        """``store``: the trainer's SnapshotRing; ``shadow``: its companion.SnapshotShadow, or None where the snapshots are
+        taken inside the iteration's own launch"""
         super().__init__()
-        self.eng, self.plan, self.H, self.W, self.dev = eng, plan, H, W, dev
+        self.store, self.shadow, self.plan, self.H, self.W, self.dev = store, shadow, plan, H, W, dev
         self.pin = self.pin_block = self.pin_hold = self.ring = None
         self.copy_stream = None          # the stream of the copies to the host, once there is one to wait for
-        self.snap_stream = None          # the side stream of the shadow engine, once it has written into the ring
+        self.composed = False            # the shadow engine has written into the ring, on its side stream, in this call
 
     def slot(self, k):
         """(3, H, W, 3) uint8 on the device: where the three images of snapshot ``k`` (the next one) are to be written"""
@@ -76,6 +100,17 @@ class RingSink(ListSink):
             self._grow(k)
         self.put(*self.pin[k])
         return self.ring[k]
+
+    def compose(self, main, dst, n):
+        """the images of the forward ``main`` has just run (``n`` rows) into ``dst`` (this snapshot's ``slot``), beside what
+        the current stream does next (companion.SnapshotShadow.compose)"""
+        self.shadow.compose(main, dst, n)
+        self.composed = True
+
+    def watch_overflow(self):
+        """the end of the call: the shadow engine's overflow watch behind its snapshots, if it took any in this call"""
+        if self.composed:
+            self.shadow.watch_overflow()
 
     def _grow(self, k):
         H, W, p = self.H, self.W, self.plan
@@ -85,10 +120,10 @@ class RingSink(ListSink):
         pin = block[0][:n_snaps * 3 * H * W * 3].view(n_snaps, 3, H, W, 3)
         hold = PINNED.hold(block, self)                      # ... while this sink (its stepper) lives
         PINNED.release(block)
-        ring = self.eng.snapshot_ring(n_snaps)               # (waits, on the stream, for the last call's copy)
+        ring = self.store.rows(n_snaps)                      # (waits, on the stream, for the last call's copy)
         if self.pin is not None:
-            if self.snap_stream is not None:
-                torch.cuda.current_stream().wait_stream(self.snap_stream)   # (the shadow engine writes the old ring)
+            if self.composed:
+                torch.cuda.current_stream().wait_stream(self.shadow.stream)     # (the shadow engine writes the old ring)
             ring[:k].copy_(self.ring[:k])
             self.lists = tuple([pin[j, c] for j in range(k)] for c in range(3))
             self.pin_hold()
@@ -115,13 +150,13 @@ class RingSink(ListSink):
         k = len(self.lists[0])
         if self.pin is not None and k:
             self.copy_stream.wait_stream(torch.cuda.current_stream())
-            if self.snap_stream is not None:
-                self.copy_stream.wait_stream(self.snap_stream)       # (the shadow engine's last images)
+            if self.composed:
+                self.copy_stream.wait_stream(self.shadow.stream)     # (the shadow engine's last images)
             with torch.cuda.stream(self.copy_stream):
                 self.pin[:k].copy_(self.ring[:k], non_blocking=True)
-                self.eng.snapshot_ring_copied()                      # (an event: the ring is free again after it)
+                self.store.copied()                                  # (an event: the ring is free again after it)
             PINNED.copied(self.pin_block, self.copy_stream)
-            self.ring.record_stream(self.copy_stream)                # (should the engine replace it by a larger one)
+            self.ring.record_stream(self.copy_stream)                # (should the store replace it by a larger one)
         if self.copy_stream is not None and not lazy:
             self.copy_stream.synchronize()           # fused path: the images are already in pinned host memory
 
@@ -256,7 +291,8 @@ class FusedStage(_Stage):
     def __init__(self, tr, p):
         tr.lr, tr.lr_camera = p.lr, p.lr_camera
         eng = self.eng = tr._pack_to_engine()
-        super().__init__(tr, p, RingSink(eng, p, tr.H, tr.W, tr.device))
+        # (a lone fit composes its snapshots on the shadow engine's side stream; with ``async_snapshots`` off: _launch)
+        super().__init__(tr, p, RingSink(tr.ring, tr.shadow if tr.async_snapshots else None, p, tr.H, tr.W, tr.device))
         eng.drop_pending()                         # (a watch the last stage queued and never read is not this stage's)
         eng.pose.copy_(tr.pose.detach())
         eng.invalidate_regions()                   # (new pose, new frame's warp of the moving splats: the first iteration bins exactly)
@@ -352,7 +388,7 @@ class FusedStage(_Stage):
     def _launch(self, dst, n_rendered, looked_at):
         """the library's iteration; ``dst``: the sink's slot for its snapshot (None: no snapshot)"""
         tr, eng = self.tr, self.eng
-        if dst is not None and not tr.async_snapshots:
+        if dst is not None and self.sink.shadow is None:
             # (several fits sharing the device -- fit_clips_concurrent -- already fill each other's gaps, and a side
             #  stream and a shadow engine per clip cost them more than they give: 12.7 -> 10.9 frames/s with two clips.
             #  There the snapshot stays behind the iteration, in the same graph launch; an elementwise kernel moves it
@@ -363,8 +399,7 @@ class FusedStage(_Stage):
             # one call (or one hipGraph replay)
             eng.iteration(use_graph=tr.use_graph, reserved=None if not looked_at else False)
             if dst is not None:
-                tr._snapshot_async(dst, n_rendered)
-                self.sink.snap_stream = tr._snap_stream
+                self.sink.compose(eng, dst, n_rendered)
 
     def one_iteration(self):
         tr, eng, p, iteration = self.tr, self.eng, self.plan, self.iteration

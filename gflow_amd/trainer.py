@@ -22,6 +22,7 @@ scope.
 """
 import math
 import os
+import weakref
 
 import numpy as np
 import torch
@@ -34,8 +35,9 @@ from . import render as render_mod
 from .geometry import device_constant, pose_to_extr, rotmat_to_unitquat_xyzw      # (importable from here, as they were)
 from .optim import Adam
 from .pinned import PINNED
+from .companion import SecondEngine, SnapshotShadow
 from .sampling import complex_texture_sampling
-from .stage import FusedStage, OperatorStage, StagePlan
+from .stage import FusedStage, OperatorStage, SnapshotRing, StagePlan
 
 
 def run_to_end(g):
@@ -121,8 +123,15 @@ class SimpleGaussian:
         # trajectory state, None until the first frame's overlay (eval_trajectories)
         self.traj_xyz = self.traj_scale = self.traj_rotate = self.traj_opacity = self.traj_rgb = self.last_traj_group = None
         self._engine_live = False                        # ``_attributes`` were last set to views of the engine's rows
-        # the second engine (_aux_engine); the shadow engine, its stream, its last snapshot's event (_snapshot_async)
-        self._aux = self._snap_aux = self._snap_stream = self._snap_done = None
+        # beside ``engine``, for this trainer's lifetime (companion.py, stage.py): the second engine, which renders the current
+        # splats; the shadow engine of the asynchronous snapshots; the ring the snapshots of a train() call wait in
+        # (the factory reaches this trainer weakly: in a reference cycle a dropped trainer's engines -- their HBM, their graphs --
+        #  would wait for the cycle collector, which may run in the middle of the next fit)
+        factory = weakref.WeakMethod(self._new_engine)
+        new_engine = lambda capacity, K_cap=None: factory()(capacity, K_cap)
+        self.second = SecondEngine(new_engine)
+        self.shadow = SnapshotShadow(new_engine, self.device)
+        self.ring = SnapshotRing(H, W, self.device)
 
     # ------------------------------------------------------------- predicates
     @property
@@ -417,9 +426,7 @@ class SimpleGaussian:
             #  boundary's ~70 small torch kernels are a chain of launch latencies on the device whoever waits for whom; the tail's
             #  exact binning cost the 0.25 ms back.  tools/stage_times.py, tools/experiments/README.md.)
             st.settle()
-            if st.sink.snap_stream is not None:
-                with torch.cuda.stream(st.sink.snap_stream):
-                    self._snap_aux.watch_overflow()
+            st.sink.watch_overflow()
         move_mask = kw.get("move_mask")
         if move_mask is not None:
             move_mask = move_mask.to(self.device).bool()
@@ -504,13 +511,13 @@ class SimpleGaussian:
     def _render_parts(self, sink):
         """trainer.py:632-677: ((still_rgb, still_center, move_rgb, move_center), None), or -- through the fused kernels --
         (the (2, 3, H, W, 3) page-locked array the device is filling, its block: handed out once the sink is flushed)"""
-        # (``engine.N == still_mask.shape[0]``, not ``engine_current``: _render_parts_fused hides a row by its label, so every
+        # (``engine.N == still_mask.shape[0]``, not ``engine_current``: SecondEngine.parts_u8 hides a row by its label, so every
         #  row of the engine needs one -- after a camera-only stage on a checkpoint's labels, say, they may be fewer)
         if self.fused and self.engine is not None and self.engine.N == self.still_mask.shape[0]:
             # both renders through the fused kernels on a second engine, the images converted on the device and on
             # their way to page-locked memory without stopping the host (four operator-path renders and four
             # blocking copies took ~3 ms per train() call: 4 % of a clip fit)
-            block, pin = sink.copy_out(self._render_parts_fused())
+            block, pin = sink.copy_out(self.second.parts_u8(self.engine, self.bg, self.still_mask))
             return pin, block
         with torch.no_grad():
             o = render_mod.render_multiple(self._input_group(sel=self.still_mask, detach=True), ["rgb", "center"])
@@ -518,91 +525,6 @@ class SimpleGaussian:
             o = render_mod.render_multiple(self._input_group(sel=~self.still_mask, detach=True), ["rgb", "center"])
             move_rgb, move_center = render_mod.render2img(o["rgb"]), render_mod.render2img(o["center"])
         return (still_rgb, still_center, move_rgb, move_center), None
-
-    def _snapshot_async(self, out, n):
-        """The snapshot images of the forward the engine has just run (``n`` rows) into ``out`` ((3, H, W, 3) uint8 on the
-        device), composed by a shadow engine on a side stream from a copy of that forward's state; returns at once.
-        ``self._snap_stream`` is that stream."""
-        import ctypes
-        eng = self.engine
-        cur = torch.cuda.current_stream()
-        if not self._fits(self._snap_aux, n, eng.K_cap):
-            if self._snap_aux is not None:
-                # the engine grew.  The side stream may still be composing the previous snapshot from the old shadow's
-                # buffers (allocated on the fit stream, used over there): let it finish before they are freed -- a rare
-                # event, a wait of one snapshot -- and keep the SAME stream, so that everything that waits on
-                # the sink's ``snap_stream`` (the ring's growth, the final copy to the host) still sees its last write
-                self._snap_stream.synchronize()
-            else:
-                self._snap_stream = torch.cuda.Stream(device=self.device)
-            self._snap_aux = self._new_engine(max(eng.cap, n), eng.K_cap)
-            self._snap_done = None
-        aux, side = self._snap_aux, self._snap_stream
-        if self._snap_done is not None:
-            cur.wait_event(self._snap_done)          # the previous snapshot has read the shadow's buffers (ten iterations ago)
-        # (count and compositing constants only: gfl_fit_snapshot_stage copies the camera with the rest of the forward's state)
-        aux.set_count(n)
-        aux.hp.bg, aux.hp.nearest, aux.hp.extent = eng.hp.bg, eng.hp.nearest, eng.hp.extent
-        L.check(eng.lib.gfl_fit_snapshot_stage(ctypes.byref(eng.state()), ctypes.byref(aux.state()), L.stream()),
-                "snapshot stage")
-        ready = torch.cuda.Event()
-        ready.record(cur)
-        with torch.cuda.stream(side):
-            side.wait_event(ready)
-            aux.snapshot(out=out)
-            self._snap_done = torch.cuda.Event()
-            self._snap_done.record(side)
-
-    @staticmethod
-    def _fits(aux, n, K_cap=None):
-        """``aux`` (a second engine, or None) has room for ``n`` rows and ``K_cap`` pairs"""
-        return aux is not None and aux.cap >= n and (K_cap is None or aux.K_cap >= K_cap)
-
-    def _aux_engine(self):
-        """The second engine, with room for the first one's rows and primed with its count, camera and background."""
-        eng = self.engine
-        if not self._fits(self._aux, eng.N):
-            self._aux = self._new_engine(max(eng.cap, eng.N))
-        aux = self._aux
-        aux.set_count(eng.N)
-        aux.pose.copy_(eng.pose)
-        aux.intr.copy_(eng.intr)
-        aux.hp.bg = self.bg
-        return aux
-
-    def _render_scene_fused(self):
-        """(3, H, W, 3) uint8 on the device: rgb, depth colour, centre blobs of the CURRENT splats and camera (what
-        render_multiple(["rgb", "center", "depth_map_color"]) + render2img give, trainer.py:765-777) through the fused
-        kernels on the second engine: one forward, one gfl_fit_snapshot; nothing is read back."""
-        aux = self._aux_forward()
-        out = aux.snapshot()
-        aux.watch_overflow()
-        return out
-
-    def _aux_forward(self):
-        """One forward of the CURRENT splats and camera on the second engine; returns it, its records (``rec``: uv in
-        columns 0:2, depth in column 9) and ``render`` (rgb, depth_map) holding the result.  The caller watches its
-        overflow flag."""
-        aux, n = self._aux_engine(), self.engine.N
-        aux.params[:n].copy_(self.engine.params[:n])
-        aux.forward()
-        return aux
-
-    def _render_parts_fused(self):
-        """(2, 3, H, W, 3) uint8 on the device: [still splats, moving splats] x [rgb, depth colour, centre blobs] of the
-        current state (trainer.py:632-677 renders rgb and centre of both sets).  A splat that is not in the set gets a raw
-        opacity of -1000 -- sigmoid(-10^4) = 0 < 1/255, so the preprocess kernel never bins it -- instead of being
-        gathered out: no boolean gather (that is a host read of the count), the depth order of the others is unchanged."""
-        eng, aux, n = self.engine, self._aux_engine(), self.engine.N
-        out = []
-        hidden = torch.full((), -1000.0, device=self.device)
-        for sel in (self.still_mask, ~self.still_mask):
-            aux.params[:n].copy_(eng.params[:n])
-            aux.params[:n, 10] = torch.where(sel, eng.params[:n, 10], hidden)
-            aux.forward()
-            out.append(aux.snapshot())
-        aux.watch_overflow()
-        return torch.stack(out)
 
     # ------------------------------------------------------------ densification
     def densify_weights(self, error_map, error_threshold=1e-3, mask=None):

@@ -507,7 +507,7 @@ int gfl_fit_iteration_snapshot(const gfl_fit_state* st, const gfl_fit_hyper* hp,
 /* Copies from one engine to another (same image size, same row count N, capacities at least as large) everything
  * gfl_fit_snapshot reads of a forward: records, sorted ids, tile ranges, the rgb planes of the render and the forward's
  * tile queues -- one launch, ~9 MB at 480p / 60 000 splats.  The snapshot of iteration i can then be taken from the copy,
- * on another stream, BESIDE iteration i + 1 (gflow_amd/trainer.py: _snapshot_async) instead of between the two. */
+ * on another stream, BESIDE iteration i + 1 (gflow_amd/companion.py: SnapshotShadow.compose) instead of between the two. */
 int gfl_fit_snapshot_stage(const gfl_fit_state* src, const gfl_fit_state* dst, gfl_stream_t stream);
 /* once per ground-truth image / keep mask: SSIM statistics of the target into the workspace; set
  * st->gt_cached = 1 afterwards (0 is always valid: everything is then recomputed per iteration) */

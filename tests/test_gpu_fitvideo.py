@@ -395,6 +395,86 @@ def test_still_and_moving_part_images_equal_the_operator_path():
     assert np.abs(np.asarray(still_rgb).astype(int) - np.asarray(move_rgb).astype(int)).mean() > 1.0
 
 
+_GROW_KW = dict(lr=4e-3, lambda_rgb=1.0, lambda_depth=1e-2, lambda_var=1.0, densify_interval=6, densify_times=1,
+                densify_err_thre=0.0, densify_err_percent=0.5)
+
+
+def _trainer_on_2048_rows(f, deterministic):
+    """a 1 500-splat trainer on a planted engine of 2 048 rows: 750 rows more (_GROW_KW: every pixel is above a threshold
+    of 0, int(1500 * 1 * 0.5) rows behind iteration 5) make 2 250, the engine grows to 4 096 and every companion engine that
+    was made for 2 048 has to be replaced"""
+    from gflow_amd.fused import FitEngine
+    from gflow_amd.trainer import SimpleGaussian
+    tr = SimpleGaussian(f["image"], f["depth"], num_points=1500, device=DEV, seed=0, deterministic=deterministic)
+    tr.load_camera(focal=f["focal"], pp=f["pp"])
+    tr.init_gaussians_from_image(f["image"], f["depth"], num_points=1500)
+    tr.engine = FitEngine(128, 96, 2048, DEV, deterministic=deterministic)
+    return tr
+
+
+@pytest.fixture(scope="module")
+def renders_across_the_growth():
+    """[(rgb, depth colour, centre)] (H, W, 3) uint8 of iterations 0, 4, 8, 12, 16 of the deterministic fit below, each from a
+    fit of its own without snapshots, stopped there and rendered: the forward's rgb, the other two from ``snapshot()``"""
+    import gflow_amd.render as R
+    f = _clip(1)[0]
+    out = []
+    for k in (0, 4, 8, 12, 16):
+        tr = _trainer_on_2048_rows(f, True)
+        st = tr.make_stepper(iterations=17, snapshot_interval=0, move_mask=f["move_mask"], **_GROW_KW)
+        st.run(k)
+        st.settle()
+        assert int(tr.engine.step.item()) == (k if k < 6 else k - 6)       # (the densification restarts the count)
+        tr.engine.forward()
+        snap = tr.engine.snapshot()
+        torch.cuda.synchronize()
+        out.append((R.render2img(tr.engine.render[:3]), snap[1].cpu().numpy(), snap[2].cpu().numpy()))
+    return out
+
+
+@pytest.mark.parametrize("async_snapshots", [True, False])
+def test_snapshots_across_a_replaced_shadow_engine_are_the_renders_of_their_iterations(async_snapshots, renders_across_the_growth):
+    """A densification in the middle of ``train()`` outgrows the engine (2 048 -> 4 096 rows) and with it the shadow engine
+    the asynchronous snapshots are composed on: slots 0, 1 (iterations 0, 4) come from the first shadow, slots 2, 3, 4
+    (iterations 8, 12, 16) from its replacement, all through one ring.  Deterministic mode: every image must equal, byte for
+    byte, the render of an identically built fit stopped at that iteration."""
+    f = _clip(1)[0]
+    tr = _trainer_on_2048_rows(f, True)
+    tr.async_snapshots = async_snapshots
+    frames, centers, depths = tr.train(iterations=17, snapshot_interval=4, move_mask=f["move_mask"], **_GROW_KW)[:3]
+    assert tr.current_pts_num() == 2250 and tr.engine.cap == 4096        # (the scenario still covers the replacement)
+    assert len(frames) == len(centers) == len(depths) == 5
+    for k, (rgb, depth, centre) in enumerate(renders_across_the_growth):
+        for name, got, want in (("rgb", frames[k], rgb), ("depth", depths[k], depth), ("centre", centers[k], centre)):
+            d = np.abs(np.asarray(got).astype(int) - want.astype(int))
+            print(f"slot {k} {name}: {int((d > 0).sum())} bytes differ, max {int(d.max())}")
+            assert not d.any(), (k, name, int((d > 0).sum()), int(d.max()))
+
+
+def test_part_images_after_the_second_engine_regrew():
+    """The second engine that renders the still / moving part images is made for the rows of the first ``train()`` (2 048);
+    the densification of a second call on the same frame makes 2 250 and it is regrown: the four images of that call against
+    renders of the gathered subsets through the operator path (the bound of the test above)."""
+    import gflow_amd.render as R
+    f = _clip(1)[0]
+    tr = _trainer_on_2048_rows(f, False)
+    kw = dict(_GROW_KW, move_mask=f["move_mask"], snapshot_interval=4)
+    tr.train(iterations=12, **dict(kw, densify_interval=0))
+    assert tr.current_pts_num() == 1500 and tr.engine.cap == 2048
+    tr.set_gt_flow(torch.zeros_like(f["flow"]))        # (a second fit of the same frame: nothing moves)
+    out = tr.train(iterations=12, **kw)
+    assert tr.current_pts_num() == 2250 and tr.engine.cap == 4096 and tr.still_mask.shape[0] == 2250
+    still_rgb, still_center, move_rgb, move_center = out[3:7]
+    assert 0 < int(tr.still_mask.sum()) < 2250
+    with torch.no_grad():
+        for sel, rgb_img, centre_img in ((tr.still_mask, still_rgb, still_center), (~tr.still_mask, move_rgb, move_center)):
+            o = R.render_multiple(tr._input_group(sel=sel, detach=True), ["rgb", "center"])
+            for got, want in ((rgb_img, R.render2img(o["rgb"])), (centre_img, R.render2img(o["center"]))):
+                assert got.shape == (96, 128, 3) and got.dtype == np.uint8
+                d = np.abs(np.asarray(got).astype(int) - want.astype(int))
+                assert (d > 1).mean() < 4e-3, (d > 1).mean()
+
+
 def test_a_fit_whose_pair_lists_overflow_ends_where_one_with_room_ends():
     """train() on an engine whose pair lists are far too short: the lists are grown where the host stops anyway (before
     a densification, at the end of the call) and the iterations that stepped nothing are run again -- same splat count,

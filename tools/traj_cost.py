@@ -2,7 +2,7 @@
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from gflow_amd import synthetic as S, fit_video as FV, clip_fit as CF
+from gflow_amd import synthetic as S, fit_video as FV, clip_fit as CF, companion as CO
 import gflow_amd.trainer as T
 
 n_frames = int(sys.argv[1]) if len(sys.argv) > 1 else 4
@@ -22,7 +22,7 @@ def timed(name, fn):
 
 CF.select_traj_seeds = timed("select_traj_seeds", CF.select_traj_seeds)      # (where ClipFit.steps looks it up)
 T.SimpleGaussian.eval_trajectories = timed("eval_trajectories", T.SimpleGaussian.eval_trajectories)
-T.SimpleGaussian._render_scene_fused = timed("_render_scene_fused", T.SimpleGaussian._render_scene_fused)
+CO.SecondEngine.scene_u8 = timed("SecondEngine.scene_u8", CO.SecondEngine.scene_u8)
 import gflow_amd.hull as Hh
 Hh.FastConcaveHull2D.__init__ = timed("hull_init", Hh.FastConcaveHull2D.__init__)
 Hh.FastConcaveHull2D.mask = timed("hull_mask", Hh.FastConcaveHull2D.mask)
