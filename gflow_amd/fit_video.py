@@ -110,6 +110,11 @@ def _parser():
                     help="with --sequence: compute every frame's occ_mask from its forward and backward flows "
                          "(<seq>_flow_unimatch/*pred.flo, *pred_bwd.flo) on the device (gflow_amd.occlusion, before the clock "
                          "starts) instead of reading *occ_bwd.png")
+    ap.add_argument("--make-flows", action="store_true",
+                    help="with --sequence: estimate every pair's forward and backward flow from the images on the device "
+                         "(gflow_amd.optflow, a classical variational estimate, before the clock starts) instead of reading "
+                         "<seq>_flow_unimatch/*pred.flo, *pred_bwd.flo; --make-move-masks and --make-occ-masks then run on "
+                         "the estimated flows")
     ap.add_argument("--metrics-csv", default=None,
                     help="rank 0 writes the blocks that were asked for as key,value lines under the reference's "
                          "metrics.csv keys")
@@ -117,6 +122,8 @@ def _parser():
 
 
 def _check_args(ap, args):
+    if args.make_flows and not args.sequence:
+        ap.error("--make-flows needs --sequence")
     if args.track_backward and not args.track:
         ap.error("--track-backward needs --track")
     if args.track_vis and not (args.track or args.traj_num > 0):
@@ -171,7 +178,8 @@ def _load_clips(args, mine, lengths, dev):
             clips[ci] = gio.load_sequence(args.sequence[ci], resize=args.resize,
                                           move_masks="epipolar" if args.make_move_masks else "files",
                                           occ_masks="flow" if args.make_occ_masks else "files", blur=args.blur,
-                                          device=dev if args.prep == "device" else None)
+                                          device=dev if args.prep == "device" else None,
+                                          flows="estimate" if args.make_flows else "files")
         else:
             clips[ci] = upload_clip(S.make_clip(lengths[ci], args.height, args.width, seed=ci, device=dev), dev)
     return clips

@@ -7,6 +7,7 @@ Mirrors ``gflow/utils/read.py`` and ``gflow/utils/conversion.py`` and the direct
     <seq>_flow_unimatch/*pred.flo    forward flow i -> i+1, Middlebury    (read.py:7-38)
     <seq>_flow_unimatch/*occ_bwd.png occlusion mask of frame i+1          (fit_video.py:88-89,248)
     <seq>_flow_unimatch/*pred_bwd.flo backward flow i+1 -> i (optional; UniMatch's name as recalled: gflow_amd.occlusion)
+                                     (both kinds of .flo can be made from the images: gflow_amd.optflow)
     <seq>_epipolar/*_open.png        move mask                           (fit_video.py:96-97)
     <seq>_camera_mast3r_s2/*.json    {"focal", "pp", "pose"}              (read.py:72-89)
 
@@ -81,12 +82,16 @@ def _read_flo(fn):
     return np.resize(data, (h, w, 2)).copy()
 
 
-def read_flow(fn, resize=None, blur=False):
-    """read.py:7-38: Middlebury .flo (little endian) -> (H,W,2); None on a bad magic number."""
-    flow = _read_flo(fn)
+def _flow_to_tensor(flow, resize=None, blur=False):
+    """what read_flow makes of a file's (h, w, 2) array (None stays None): the resize does not rescale the values"""
     if flow is None:
         return None
     return _blur_chw(_resize_chw(torch.from_numpy(flow).permute(2, 0, 1), resize), blur).permute(1, 2, 0)
+
+
+def read_flow(fn, resize=None, blur=False):
+    """read.py:7-38: Middlebury .flo (little endian) -> (H,W,2); None on a bad magic number."""
+    return _flow_to_tensor(_read_flo(fn), resize, blur)
 
 
 def write_flow(fn, flow):
@@ -153,7 +158,7 @@ def sequence_paths(sequence_path, frame_start=0, frame_range=-1, skip_interval=1
 
 
 def load_sequence(sequence_path, resize=None, frame_start=0, frame_range=-1, skip_interval=1, depth_offset=0.0,
-                  move_masks="files", occ_masks="files", blur=False, device=None):
+                  move_masks="files", occ_masks="files", blur=False, device=None, flows="files"):
     """Frames in the dict form ``gflow_amd.fit_video.fit_clip`` takes.  Frame i carries the flow
     i -> i+1 (fit_video.py:249: frame i+1 is fitted with flow_paths[i]) and the occlusion mask that
     fit_video.py:248 reads for it (img_occ_paths[i-1]).
@@ -164,6 +169,11 @@ def load_sequence(sequence_path, resize=None, frame_start=0, frame_range=-1, ski
     flows i -> i + 1 and i + 1 -> i (``*pred_bwd.flo``) at the flows' NATIVE resolution, on the device
     (gflow_amd.occlusion.clip_occ_masks), then resizes the mask as a mask file would be.  Either way a frame without its
     file(s) gets no ``occ_mask``.
+    ``flows``: "files" reads ``*pred.flo`` (and for occ_masks="flow" ``*pred_bwd.flo``); "estimate" ignores both and estimates
+    the forward and the backward flow of every pair the files would cover from the decoded images at their NATIVE
+    resolution, on the device (gflow_amd.optflow.pair_flows: ONE batched call).  An estimated flow then goes exactly the way
+    a file's array goes (the resize that does not rescale the values, the blur), and move_masks="epipolar" and
+    occ_masks="flow" run on the estimated flows.  A frame without a following image gets zeros, as a frame without a file.
     ``blur``: the reference's option -- GaussianBlur(7, 5.0) after the resize on the image, the occlusion mask and the flow
     (fit_video.py:245-248), not on the depth or the move mask.
     ``device``: None prepares every file on the host with torch, one file at a time, and returns host tensors.  With a
@@ -175,20 +185,55 @@ def load_sequence(sequence_path, resize=None, frame_start=0, frame_range=-1, ski
         raise ValueError(f"load_sequence: occ_masks must be \"files\" or \"flow\", got {occ_masks!r}")
     if move_masks not in ("files", "epipolar"):
         raise ValueError(f"load_sequence: move_masks must be \"files\" or \"epipolar\", got {move_masks!r}")
+    if flows not in ("files", "estimate"):
+        raise ValueError(f"load_sequence: flows must be \"files\" or \"estimate\", got {flows!r}")
     p = sequence_paths(sequence_path, frame_start, frame_range, skip_interval)
     focal, pp, poses = read_camera(p["camera"])
+    n = len(p["img"])
+    if flows == "estimate":
+        fwd, bwd = _estimated_flows(sequence_path, frame_start, frame_range, skip_interval, device)
+    else:
+        fwd, bwd = [_FloFile(f) for f in p["flow"]], [_FloFile(f) for f in p["flow_bwd"]]
+    fwd, bwd = fwd[:n], bwd[:n]
     if device is not None:
-        frames = _load_frames_device(p, focal, pp, poses, resize, depth_offset, move_masks, occ_masks, blur,
+        frames = _load_frames_device(p, fwd, bwd, focal, pp, poses, resize, depth_offset, move_masks, occ_masks, blur,
                                      torch.device(device))
     else:
-        frames = _load_frames_host(p, focal, pp, poses, resize, depth_offset, move_masks, occ_masks, blur)
+        frames = _load_frames_host(p, fwd, bwd, focal, pp, poses, resize, depth_offset, move_masks, occ_masks, blur)
     if move_masks == "epipolar":
         from .move_seg import clip_move_masks
-        clip_move_masks(frames, n_flows=len(p["flow"]))
+        clip_move_masks(frames, n_flows=len(fwd))
     return frames
 
 
-def _load_frames_host(p, focal, pp, poses, resize, depth_offset, move_masks, occ_masks, blur):
+class _FloFile:
+    """a frame's flow at its native resolution, wherever it comes from: read() is the (h, w, 2) float32 array of a .flo
+    file (None on a bad magic number) or of an estimate"""
+
+    def __init__(self, path=None, array=None):
+        self.path, self.array = path, array
+
+    def read(self):
+        return _read_flo(self.path) if self.array is None else self.array
+
+
+def _estimated_flows(sequence_path, frame_start, frame_range, skip_interval, device):
+    """(forward, backward) _FloFile lists as sequence_paths would list the files of a folder that holds the flows of EVERY
+    pair of consecutive images (the one ``python -m gflow_amd.optflow`` writes): file k is the pair (image k, image k + 1)."""
+    from .optflow import pair_flows
+    sp = str(sequence_path).rstrip("/")
+    img = sequence_paths(sp, frame_range=1 << 30)["img"]
+    if frame_range == -1:
+        frame_range = len(img) - 1
+    pairs = list(range(max(len(img) - 1, 0)))[frame_start:frame_start + frame_range][::skip_interval]
+    if not pairs:
+        return [], []
+    fwd, bwd = pair_flows(img, pairs, device=device)
+    fwd, bwd = fwd.cpu().numpy(), bwd.cpu().numpy()
+    return ([_FloFile(array=np.ascontiguousarray(f)) for f in fwd], [_FloFile(array=np.ascontiguousarray(f)) for f in bwd])
+
+
+def _load_frames_host(p, flow_src, bwd_src, focal, pp, poses, resize, depth_offset, move_masks, occ_masks, blur):
     frames = []
     for i, ip in enumerate(p["img"]):
         fr = dict(image=image_path_to_tensor(ip, resize, blur), focal=focal, pp=pp, name=os.path.basename(ip).split(".")[0])
@@ -196,7 +241,7 @@ def _load_frames_host(p, focal, pp, poses, resize, depth_offset, move_masks, occ
         H, W = fr["image"].shape[:2]
         from_file = move_masks == "files" and i < len(p["move"])
         fr["move_mask"] = read_mask(p["move"][i], resize) if from_file else torch.zeros(H, W, dtype=torch.bool)
-        fr["flow"] = read_flow(p["flow"][i], resize, blur) if i < len(p["flow"]) else torch.zeros(H, W, 2)
+        fr["flow"] = _flow_to_tensor(flow_src[i].read(), resize, blur) if i < len(flow_src) else torch.zeros(H, W, 2)
         if occ_masks == "files" and i >= 1 and i - 1 < len(p["occ"]):
             fr["occ_mask"] = image_path_to_tensor(p["occ"][i - 1], resize, blur)
         if i < len(poses):
@@ -204,11 +249,11 @@ def _load_frames_host(p, focal, pp, poses, resize, depth_offset, move_masks, occ
         frames.append(fr)
     if occ_masks == "flow":
         from .occlusion import clip_occ_masks
-        n_pairs = min(len(frames) - 1, len(p["flow"]), len(p["flow_bwd"]))
+        n_pairs = min(len(frames) - 1, len(flow_src), len(bwd_src))
         # (the reference resizes a flow without rescaling its values: the check must not see fr["flow"] of a resized clip)
         native = resize is None and not blur
-        fwd = [frames[i]["flow"] if native else read_flow(p["flow"][i]) for i in range(n_pairs)]
-        bwd = [read_flow(p["flow_bwd"][i]) for i in range(n_pairs)]
+        fwd = [frames[i]["flow"] if native else _flow_to_tensor(flow_src[i].read()) for i in range(n_pairs)]
+        bwd = [_flow_to_tensor(bwd_src[i].read()) for i in range(n_pairs)]
         clip_occ_masks(frames, bwd, fwd_flows=fwd, resize=resize)
         if blur:                                   # (no frame had a mask before: the files are ignored)
             for fr in frames:
@@ -257,7 +302,7 @@ def _prep_stacks(arrays, device, resize, keys=None, **kw):
     return out
 
 
-def _load_frames_device(p, focal, pp, poses, resize, depth_offset, move_masks, occ_masks, blur, device):
+def _load_frames_device(p, flow_src, bwd_src, focal, pp, poses, resize, depth_offset, move_masks, occ_masks, blur, device):
     if device.type != "cuda":
         raise RuntimeError("gflow_amd.io: load_sequence(device=...) needs a HIP (cuda) device; there is no CPU fallback")
     n = len(p["img"])
@@ -265,7 +310,7 @@ def _load_frames_device(p, focal, pp, poses, resize, depth_offset, move_masks, o
     image = _prep_stacks([a for a, _ in images], device, resize, keys=[d for _, d in images], blur=blur)
     depth = _prep_stacks([np.asarray(np.load(p["depth"][i]), dtype=np.float32)[..., None] for i in range(n)], device, resize,
                          mul=1.0, add=depth_offset)
-    flows = [_read_flo(p["flow"][i]) if i < len(p["flow"]) else None for i in range(n)]
+    flows = [flow_src[i].read() if i < len(flow_src) else None for i in range(n)]
     flow = _prep_stacks(flows, device, resize, blur=blur)
     move = [None] * n
     if move_masks == "files":
@@ -279,7 +324,7 @@ def _load_frames_device(p, focal, pp, poses, resize, depth_offset, move_masks, o
         from .occlusion import flow_occlusion
         from .prep import prep_frames
         # the check sees the flows at their native resolution (resizing a flow does not rescale its values)
-        bwd = [_read_flo(p["flow_bwd"][i]) for i in range(min(n - 1, len(p["flow"]), len(p["flow_bwd"])))]
+        bwd = [bwd_src[i].read() for i in range(min(n - 1, len(flow_src), len(bwd_src)))]
         pairs = [i for i, b in enumerate(bwd) if b is not None and flows[i] is not None]
         if pairs:
             res = flow_occlusion(torch.from_numpy(np.stack([flows[i] for i in pairs])).to(device),
@@ -292,7 +337,7 @@ def _load_frames_device(p, focal, pp, poses, resize, depth_offset, move_masks, o
         fr = dict(image=image[i], focal=focal, pp=pp, name=os.path.basename(ip).split(".")[0], depth=depth[i])
         H, W = fr["image"].shape[:2]
         fr["move_mask"] = move[i] if move[i] is not None else torch.zeros(H, W, dtype=torch.bool, device=device)
-        if i < len(p["flow"]):
+        if i < len(flow_src):
             fr["flow"] = flow[i]                   # (None for a file with a bad magic number, as read_flow gives)
         else:
             fr["flow"] = torch.zeros(H, W, 2, device=device)

@@ -24,6 +24,10 @@
  *                             the render differ in the last bits on the tiles that take it (which tiles do depends on the
  *                             schedule as well), lists and contributor counts not at all;
  *     tests/test_gpu_switches.py flips each one in a process of its own and holds the results against the defaults.
+ *     A fourth switch belongs to the optical-flow entries alone and is read at every call of theirs:
+ *       GFL_OPTFLOW_FUSED=0   every Jacobi sweep of gfl_optflow / gfl_optflow_level is a launch of its own (the comparison
+ *                             path of DESIGN.md, "Optical flow"); the flows are bit-identical either way
+ *                             (tests/test_gpu_optflow.py flips it in-process).
  *     (Rounds 3-4 had fourteen; the measured-and-rejected variants behind the others now live in tools/experiments/.)
  *   - return value: GFL_OK or a negative gfl_status; HIP launch errors are
  *     returned as GFL_ERR_HIP and the hipError_t is kept in gfl_last_hip_error();
@@ -108,7 +112,7 @@ typedef enum gfl_status {
  * gfl_epi_workspace_bytes; gfl_flow_occlusion was added WITHIN 312 (an additive entry: nothing that existed changed, so the
  * number stays; a binding that needs it looks the symbol up).  gfl_track_history, gfl_track_backward and
  * gfl_track_backward_workspace_bytes were added WITHIN 312 in the same way, and so were gfl_track_vis and gfl_prep_frames with
- * their workspace queries, and the four gfl_jpeg_* entries.
+ * their workspace queries, the four gfl_jpeg_* entries, and gfl_optflow, gfl_optflow_level, gfl_optflow_workspace_bytes.
  * A binding checks gfl_version() >= GFL_VERSION of the header it was written for. */
 #define GFL_VERSION 312
 int gfl_version(void);
@@ -874,6 +878,47 @@ int gfl_jpeg_sizes(const uint8_t* images, int T, int C, int W, int H, const uint
                    void* workspace, size_t workspace_bytes, gfl_stream_t stream);
 int gfl_jpeg_emit(const uint8_t* images, int T, int C, int W, int H, const uint16_t* qtables, uint8_t* out, int64_t out_bytes,
                   void* workspace, size_t workspace_bytes, gfl_stream_t stream);
+
+/* ---- optical flow (additive within 312; gflow_amd/optflow.py, INTEGRATION.md "Flows from the images") --------------------
+ * The flow a -> b on a's grid, in pixels, of P pairs of images: a classical coarse-to-fine variational estimate (robust data
+ * term on the grey value, robust isotropic smoothness), NOT a learned one.  All arithmetic is float32 in the order written,
+ * products and sums rounded separately (nothing fused); tests/optflow_ref.py restates it in float64.
+ *   a, b [P][H][W][3] uint8 (src_is_u8 = 1: v / 255) or float32 in [0, 1];  flow_out [P][H][W][2] float32 (8-byte aligned).
+ * (1) grey: I = 255 ((0.299 R + 0.587 G) + 0.114 B).
+ * (2) pyramid: level 0 is the image; level l + 1 is (ceil(H_l / 2), ceil(W_l / 2)), pixel (x, y) = level l filtered by
+ *   ((((f(-2) + 4 f(-1)) + 6 f(0)) + 4 f(1)) + f(2)) / 16 along the rows, then along the columns, border replicated, sampled
+ *   at (2x, 2y).  Levels are added while min(H_l, W_l) / 2 (integer) >= min_side.
+ * (3) the flow is zero at the coarsest level; flow_l(x, y) = 2 B(flow_{l+1}, x / 2, y / 2), coordinates clamped to the coarse
+ *   grid.  B(f, x, y), bilinear: x0 = floor(x), x1 = min(x0 + 1, W - 1), t = x - x0 (y likewise),
+ *   (1 - ty) ((1 - tx) f00 + tx f01) + ty ((1 - tx) f10 + tx f11).
+ * (4) per level, `warps` times with the current (u, v): Iw(x, y) = B(Ib, x + u, y + v) with the coordinates clamped to the
+ *   image, inside = 1 where the unclamped ones lie in [0, W - 1] x [0, H - 1], else 0; D = the central difference
+ *   1/2 (f(+1) - f(-1)), border replicated; Ix = 1/2 (Dx Iw + Dx Ia), Iy likewise, It = Iw - Ia; du = dv = 0.  `outer` times:
+ *     pd = inside / sqrt(((It + Ix du) + Iy dv)^2 + 1e-6),
+ *     ps = alpha / sqrt(((Dx U)^2 + (Dy U)^2) + ((Dx V)^2 + (Dy V)^2) + 1e-6), U = u + du, V = v + dv,
+ *     wl = 1/2 (ps + ps_left) and wr, wt, wb likewise, 0 where the neighbour lies outside the image, ws = ((wl + wr) + wt) + wb,
+ *     a11 = (pd Ix) Ix + ws, a22 = (pd Iy) Iy + ws, a12 = (pd Ix) Iy, c1 = (pd Ix) It, c2 = (pd Iy) It;
+ *   then `sweeps` Jacobi sweeps, each reading only the previous sweep's (du, dv):
+ *     su = (((wl U_l + wr U_r) + wt U_t) + wb U_b) - ws u (sv likewise), b1 = su - c1, b2 = sv - c2, det = a11 a22 - a12 a12,
+ *     du = (a22 b1 - a12 b2) / det, dv = (a11 b2 - a12 b1) / det.
+ *   Then u += du, v += dv.
+ * gfl_optflow runs all of it; gfl_optflow_level runs step (4) alone on grey images Ia, Ib [P][H][W] from the starting flow in
+ * flow_inout [P][H][W][2], which it replaces (any workspace of gfl_optflow_workspace_bytes(P, H, W, min_side) bytes is large
+ * enough for it, whatever min_side).  The sweeps run fused, several per launch on a tile with a ring of as many pixels (the
+ * interior then has exactly the bits of that many plain sweeps), and a level that fits one workgroup runs a re-weighting's
+ * sweeps in one launch; GFL_OPTFLOW_FUSED=0 in the environment (read at every call) launches every sweep on its own
+ * instead, with the same bits.
+ * GFL_ERR_INVALID, before any launch: P < 1, H or W < 8, P H W > 2^30, an alpha that is not finite and > 0, warps, outer or
+ * sweeps < 1, min_side < 2, src_is_u8 not 0 or 1, a NULL pointer, float images that are not 4-byte aligned, a flow that is not
+ * 8-byte aligned, a workspace that is not 16-byte aligned.  GFL_ERR_WORKSPACE: workspace_bytes too small
+ * (gfl_optflow_workspace_bytes: 0 for arguments it rejects; needs no device).  No atomics, no allocation, no host
+ * synchronisation, everything on `stream`; the same inputs give the same bits, and a problem's result does not depend on
+ * the others in its call. */
+size_t gfl_optflow_workspace_bytes(int P, int H, int W, int min_side);
+int gfl_optflow(const void* a, const void* b, int src_is_u8, int P, int H, int W, float alpha, int warps, int outer, int sweeps,
+                int min_side, float* flow_out, void* workspace, size_t workspace_bytes, gfl_stream_t stream);
+int gfl_optflow_level(const float* Ia, const float* Ib, float* flow_inout, int P, int H, int W, float alpha, int warps,
+                      int outer, int sweeps, void* workspace, size_t workspace_bytes, gfl_stream_t stream);
 
 /* sizeof(gfl_fit_state), sizeof(gfl_fit_hyper): lets an FFI binding verify its struct mirrors */
 int gfl_abi_sizes(int* sizeof_fit_state, int* sizeof_fit_hyper);
