@@ -119,6 +119,13 @@ SIGNATURES = {
     "gfl_optflow_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "gfl_optflow": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "gfl_optflow_level": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "gfl_sfm_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "gfl_sfm_refit": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, ctypes.c_double, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "gfl_sfm_pose": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int] + [ctypes.c_double] * 6 + [_P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "gfl_sfm_triangulate": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int] + [ctypes.c_double] * 4 + [_P, _P, _P]),
+    "gfl_sfm_median": (c_int, [_P, _P, _P, _P, c_float, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "gfl_sfm_fuse": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
+    "gfl_sfm_fill": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, c_size_t, _P]),
     "gfl_abi_sizes": (c_int, [_P, _P]),
     "gfl_profile_enable": (c_int, [ctypes.c_uint]),
     "gfl_profile_read": (c_int, [_P, _P, c_int]),

@@ -115,6 +115,15 @@ def _parser():
                          "(gflow_amd.optflow, a classical variational estimate, before the clock starts) instead of reading "
                          "<seq>_flow_unimatch/*pred.flo, *pred_bwd.flo; --make-move-masks and --make-occ-masks then run on "
                          "the estimated flows")
+    ap.add_argument("--make-depth-camera", action="store_true",
+                    help="with --sequence: estimate every frame's depth and pose from the flows on the device (gflow_amd.sfm, "
+                         "classical two-view geometry, NOT MASt3R: depth only where the camera translates, moving and "
+                         "occluded regions filled from their surroundings; before the clock starts) instead of reading "
+                         "<seq>_depth_mast3r_s2/*.npy and <seq>_camera_mast3r_s2/*.json; with --make-flows "
+                         "--make-move-masks --make-occ-masks a sequence needs only its images")
+    ap.add_argument("--focal", type=float, default=None,
+                    help="with --make-depth-camera: the focal length in pixels of the native images (default: max(W, H), an "
+                         "assumption)")
     ap.add_argument("--metrics-csv", default=None,
                     help="rank 0 writes the blocks that were asked for as key,value lines under the reference's "
                          "metrics.csv keys")
@@ -124,6 +133,10 @@ def _parser():
 def _check_args(ap, args):
     if args.make_flows and not args.sequence:
         ap.error("--make-flows needs --sequence")
+    if args.make_depth_camera and not args.sequence:
+        ap.error("--make-depth-camera needs --sequence")
+    if args.focal is not None and not args.make_depth_camera:
+        ap.error("--focal needs --make-depth-camera")
     if args.track_backward and not args.track:
         ap.error("--track-backward needs --track")
     if args.track_vis and not (args.track or args.traj_num > 0):
@@ -179,7 +192,8 @@ def _load_clips(args, mine, lengths, dev):
                                           move_masks="epipolar" if args.make_move_masks else "files",
                                           occ_masks="flow" if args.make_occ_masks else "files", blur=args.blur,
                                           device=dev if args.prep == "device" else None,
-                                          flows="estimate" if args.make_flows else "files")
+                                          flows="estimate" if args.make_flows else "files",
+                                          depth_camera="estimate" if args.make_depth_camera else "files", focal=args.focal)
         else:
             clips[ci] = upload_clip(S.make_clip(lengths[ci], args.height, args.width, seed=ci, device=dev), dev)
     return clips

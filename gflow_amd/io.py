@@ -121,8 +121,13 @@ def read_mask(mask_path, resize=None):
 
 def read_depth(depth_path, resize=None, depth_scale=1.0, depth_offset=0.0):
     """read.py:60-70 -> (H,W) float."""
-    t = torch.tensor(np.load(depth_path), dtype=torch.float32).unsqueeze(0)
+    t = torch.tensor(_depth_array(depth_path), dtype=torch.float32).unsqueeze(0)
     return _resize_chw(t, resize).squeeze(0) * depth_scale + depth_offset
+
+
+def _depth_array(src):
+    """a frame's depth at its native resolution, wherever it comes from: the array of a .npy file, or an estimate's array"""
+    return src if isinstance(src, np.ndarray) else np.load(src)
 
 
 def read_camera(camera_paths):
@@ -158,7 +163,8 @@ def sequence_paths(sequence_path, frame_start=0, frame_range=-1, skip_interval=1
 
 
 def load_sequence(sequence_path, resize=None, frame_start=0, frame_range=-1, skip_interval=1, depth_offset=0.0,
-                  move_masks="files", occ_masks="files", blur=False, device=None, flows="files"):
+                  move_masks="files", occ_masks="files", blur=False, device=None, flows="files", depth_camera="files",
+                  focal=None):
     """Frames in the dict form ``gflow_amd.fit_video.fit_clip`` takes.  Frame i carries the flow
     i -> i+1 (fit_video.py:249: frame i+1 is fitted with flow_paths[i]) and the occlusion mask that
     fit_video.py:248 reads for it (img_occ_paths[i-1]).
@@ -174,6 +180,13 @@ def load_sequence(sequence_path, resize=None, frame_start=0, frame_range=-1, ski
     resolution, on the device (gflow_amd.optflow.pair_flows: ONE batched call).  An estimated flow then goes exactly the way
     a file's array goes (the resize that does not rescale the values, the blur), and move_masks="epipolar" and
     occ_masks="flow" run on the estimated flows.  A frame without a following image gets zeros, as a frame without a file.
+    ``depth_camera``: "files" reads ``<seq>_depth_mast3r_s2/*.npy`` and ``<seq>_camera_mast3r_s2/*.json``; "estimate" ignores
+    both folders and estimates the depth maps, the poses and the principal point from the flows at their NATIVE resolution,
+    on the device (gflow_amd.sfm.clip_depth_camera: classical two-view geometry, NOT MASt3R; the flows from the files or,
+    with flows="estimate", from the images; the move and occlusion masks, read or computed as ``move_masks`` and
+    ``occ_masks`` say, keep their pixels out of the geometry).  ``focal`` is then the focal length in pixels of the native
+    images (default: max(W, H), an assumption); the depth arrays, focal, pp and poses go exactly the way the files' values
+    go.  It needs consecutive frames (skip_interval = 1) and a forward flow between every two of them.
     ``blur``: the reference's option -- GaussianBlur(7, 5.0) after the resize on the image, the occlusion mask and the flow
     (fit_video.py:245-248), not on the depth or the move mask.
     ``device``: None prepares every file on the host with torch, one file at a time, and returns host tensors.  With a
@@ -187,14 +200,24 @@ def load_sequence(sequence_path, resize=None, frame_start=0, frame_range=-1, ski
         raise ValueError(f"load_sequence: move_masks must be \"files\" or \"epipolar\", got {move_masks!r}")
     if flows not in ("files", "estimate"):
         raise ValueError(f"load_sequence: flows must be \"files\" or \"estimate\", got {flows!r}")
+    if depth_camera not in ("files", "estimate"):
+        raise ValueError(f"load_sequence: depth_camera must be \"files\" or \"estimate\", got {depth_camera!r}")
+    if depth_camera == "files" and focal is not None:
+        raise ValueError("load_sequence: focal is the assumption of depth_camera=\"estimate\"; the files carry their own")
     p = sequence_paths(sequence_path, frame_start, frame_range, skip_interval)
-    focal, pp, poses = read_camera(p["camera"])
     n = len(p["img"])
     if flows == "estimate":
         fwd, bwd = _estimated_flows(sequence_path, frame_start, frame_range, skip_interval, device)
     else:
         fwd, bwd = [_FloFile(f) for f in p["flow"]], [_FloFile(f) for f in p["flow_bwd"]]
     fwd, bwd = fwd[:n], bwd[:n]
+    if depth_camera == "estimate":
+        if skip_interval != 1:
+            raise ValueError("load_sequence: depth_camera=\"estimate\" needs consecutive frames (skip_interval = 1)")
+        depth, focal, pp, poses = _estimated_depth_camera(p, fwd, bwd, n, move_masks, occ_masks, focal, device)
+        p = dict(p, depth=depth)
+    else:
+        focal, pp, poses = read_camera(p["camera"])
     if device is not None:
         frames = _load_frames_device(p, fwd, bwd, focal, pp, poses, resize, depth_offset, move_masks, occ_masks, blur,
                                      torch.device(device))
@@ -231,6 +254,54 @@ def _estimated_flows(sequence_path, frame_start, frame_range, skip_interval, dev
     fwd, bwd = pair_flows(img, pairs, device=device)
     fwd, bwd = fwd.cpu().numpy(), bwd.cpu().numpy()
     return ([_FloFile(array=np.ascontiguousarray(f)) for f in fwd], [_FloFile(array=np.ascontiguousarray(f)) for f in bwd])
+
+
+def _estimated_depth_camera(p, fwd_src, bwd_src, n, move_masks, occ_masks, focal, device):
+    """(depth arrays, focal, pp, poses) of the n frames as the files would give them, from gflow_amd.sfm.clip_depth_camera on
+    the native flows.  The backward flows are used when every pair has one; the exclusions are the move masks (on the forward
+    flows' grids) and the occlusion masks (``occ_bwd`` on the backward flows' grids, and with occ_masks="flow" ``occ`` on the
+    forward ones'), read where a file of the flows' shape is there, computed where the loader computes them."""
+    from .sfm import clip_depth_camera, warn_unreliable
+    if n < 1:
+        raise ValueError("load_sequence: depth_camera=\"estimate\" needs at least one frame")
+    fwd = [f.read() for f in fwd_src[:n]]
+    if len(fwd) < max(n - 1, 1) or any(f is None for f in fwd):
+        raise ValueError(f"load_sequence: depth_camera=\"estimate\" needs a forward flow between the {n} frames, found {len(fwd)}")
+    m = len(fwd)
+    bwd = [f.read() for f in bwd_src[:m]]
+    bwd = None if len(bwd) < m or any(b is None for b in bwd) else bwd
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda" or not torch.cuda.is_available():
+        raise RuntimeError("gflow_amd.io: depth_camera=\"estimate\" needs a HIP (cuda) device; there is no CPU fallback")
+    f_dev = torch.from_numpy(np.stack(fwd)).to(dev)
+    b_dev = None if bwd is None else torch.from_numpy(np.stack(bwd)).to(dev)
+    shape = tuple(f_dev.shape[1:3])
+    ex_f = torch.zeros((m,) + shape, dtype=torch.bool, device=dev)
+    ex_b = torch.zeros((m,) + shape, dtype=torch.bool, device=dev)
+    if move_masks == "epipolar":
+        from .move_seg import epipolar_move_mask
+        for i in range(m):
+            ex_f[i] = epipolar_move_mask(f_dev[i])["open"] != 0
+    else:
+        for i, path in enumerate(p["move"][:m]):
+            mask = read_mask(path)
+            if tuple(mask.shape) == shape:
+                ex_f[i] = mask.to(dev)
+    if occ_masks == "flow" and b_dev is not None:
+        from .occlusion import flow_occlusion
+        occ = flow_occlusion(f_dev, b_dev)
+        ex_f |= occ["occ"] != 0
+        ex_b |= occ["occ_bwd"] != 0
+    elif occ_masks == "files":
+        for i, path in enumerate(p["occ"][:m]):
+            mask = read_mask(path)
+            if tuple(mask.shape) == shape:
+                ex_b[i] = mask.to(dev)
+    res = clip_depth_camera(f_dev, b_dev, focal=focal, exclude_fwd=ex_f, exclude_bwd=ex_b, warn=False)
+    warn_unreliable(res["unreliable"][:n])                       # (a flow into an image behind the slice adds a frame)
+    depth = res["depth"][:n].cpu().numpy()
+    poses = res["extr"][:n].cpu().numpy()
+    return [np.ascontiguousarray(d) for d in depth], float(res["focal"]), list(res["pp"]), poses
 
 
 def _load_frames_host(p, flow_src, bwd_src, focal, pp, poses, resize, depth_offset, move_masks, occ_masks, blur):
@@ -308,7 +379,7 @@ def _load_frames_device(p, flow_src, bwd_src, focal, pp, poses, resize, depth_of
     n = len(p["img"])
     images = [_decode_image(ip) for ip in p["img"]]
     image = _prep_stacks([a for a, _ in images], device, resize, keys=[d for _, d in images], blur=blur)
-    depth = _prep_stacks([np.asarray(np.load(p["depth"][i]), dtype=np.float32)[..., None] for i in range(n)], device, resize,
+    depth = _prep_stacks([np.asarray(_depth_array(p["depth"][i]), dtype=np.float32)[..., None] for i in range(n)], device, resize,
                          mul=1.0, add=depth_offset)
     flows = [flow_src[i].read() if i < len(flow_src) else None for i in range(n)]
     flow = _prep_stacks(flows, device, resize, blur=blur)

@@ -28,6 +28,9 @@
  *       GFL_OPTFLOW_FUSED=0   every Jacobi sweep of gfl_optflow / gfl_optflow_level is a launch of its own (the comparison
  *                             path of DESIGN.md, "Optical flow"); the flows are bit-identical either way
  *                             (tests/test_gpu_optflow.py flips it in-process).
+ *     A fifth, likewise, belongs to gfl_sfm_fill alone:
+ *       GFL_SFM_FUSED=0       every Jacobi sweep of gfl_sfm_fill is a launch of its own; the depth is bit-identical either way
+ *                             (tests/test_gpu_sfm.py flips it in-process).
  *     (Rounds 3-4 had fourteen; the measured-and-rejected variants behind the others now live in tools/experiments/.)
  *   - return value: GFL_OK or a negative gfl_status; HIP launch errors are
  *     returned as GFL_ERR_HIP and the hipError_t is kept in gfl_last_hip_error();
@@ -112,8 +115,8 @@ typedef enum gfl_status {
  * gfl_epi_workspace_bytes; gfl_flow_occlusion was added WITHIN 312 (an additive entry: nothing that existed changed, so the
  * number stays; a binding that needs it looks the symbol up).  gfl_track_history, gfl_track_backward and
  * gfl_track_backward_workspace_bytes were added WITHIN 312 in the same way, and so were gfl_track_vis and gfl_prep_frames with
- * their workspace queries, the four gfl_jpeg_* entries, and gfl_optflow, gfl_optflow_level, gfl_optflow_workspace_bytes.
- * A binding checks gfl_version() >= GFL_VERSION of the header it was written for. */
+ * their workspace queries, the four gfl_jpeg_* entries, and gfl_optflow, gfl_optflow_level, gfl_optflow_workspace_bytes,
+ * and the seven gfl_sfm_* entries.  A binding checks gfl_version() >= GFL_VERSION of the header it was written for. */
 #define GFL_VERSION 312
 int gfl_version(void);
 /* out[10] = TILE, NEAREST, EXTENT, FOV_CLAMP, LOWPASS, EIG_FLOOR, RADIUS_SIGMA, ALPHA_MIN, ALPHA_MAX, T_MIN of this build */
@@ -919,6 +922,77 @@ int gfl_optflow(const void* a, const void* b, int src_is_u8, int P, int H, int W
                 int min_side, float* flow_out, void* workspace, size_t workspace_bytes, gfl_stream_t stream);
 int gfl_optflow_level(const float* Ia, const float* Ib, float* flow_inout, int P, int H, int W, float alpha, int warps,
                       int outer, int sweeps, void* workspace, size_t workspace_bytes, gfl_stream_t stream);
+
+/* ---- depth and camera from the flows (additive within 312; gflow_amd/sfm.py, INTEGRATION.md "Depth and camera from the
+ * flows") -----------------------------------------------------------------------------------------------------------------
+ * Classical two-view geometry for P pair problems of one shape at once: what a clip fit otherwise reads from MASt3R's
+ * depth and camera files, from the flows alone.  It is NOT MASt3R and is unpinned against it: depth is recovered only where
+ * the camera translates (parallax), moving and occluded regions are filled from their surroundings, and it has not been run
+ * on real video.  tests/sfm_ref.py restates every stage in float64.
+ *   flow [P][H][W][2] float32, in pixels: pixel (x, y) of view 1 -- centres at integer coordinates -- is seen at
+ *   (x, y) + flow in view 2.  A pixel is KNOWN when both components are finite.  The camera is fx, fy, cx, cy for both views.
+ * gfl_sfm_refit: F_init, F_out [P][9] float64 row-major with x2^T F x1 = 0 in pixel coordinates (they may be the same
+ *   array); exclude [P][H][W] uint8 or NULL, nonzero = leave the pixel out.  `rounds` times: e = the Sampson error
+ *   z^2 / (d1x^2 + d1y^2 + d2x^2 + d2y^2), z = x2^T F x1, d1 = F x1, d2 = F^T x2 (0 for a zero denominator) of every USABLE
+ *   pixel (known, not excluded, e finite); med = its exact lower median (rank (n - 1) / 2, by radix selection on the bit
+ *   pattern); inliers are e <= max(2.5^2 1.4826^2 med, e_floor); over them the Hartley-normalised 8-point fit (per view:
+ *   centroid to 0, mean distance to sqrt 2; the 45 unique sums of A^T A over the rows [x2 x1, x2 y1, x2, y2 x1, y2 y1, y2, x1,
+ *   y1, 1], its null vector by cyclic Jacobi, rank 2 by dropping F^T F's smallest eigenvector, de-normalised, ||F||_F = 1
+ *   with the entry of largest magnitude positive).  A pair with fewer than 8 inliers, or whose fit is not finite, keeps its
+ *   F.  Then, with the final F: median [P], counts [P][2] int32 = (usable pixels, inliers), inlier [P][H][W] uint8 0 / 1.
+ *   An F that is not finite leaves a pair without usable pixels (median NaN).  0 <= rounds <= 16.
+ * gfl_sfm_pose: E = K^T F K, K = [fx 0 cx; 0 fy cy; 0 0 1]; its singular vectors from Jacobi on E^T E, the singular values
+ *   taken as (1, 1, 0); the rotations U W V^T and U W^T V^T (det +1), the one with the LARGER TRACE first; t0 = u3 with its
+ *   entry of largest magnitude positive.  Candidate c = (rotation c / 2, +t0 for even c, -t0 for odd c).  An inlier votes for
+ *   c when both depths of its triangulation (below) are > 0; the winner has the most votes, the lowest c among equals.
+ *   parallax = the exact lower median over the inliers of |x2 - K (R x1) / (R x1)_z| in pixels (0 without inliers).
+ *   degenerate = usable < 8, or inliers < min_share usable, or F, R or t not finite, or not parallax >= min_parallax; then
+ *   t = 0, and R is kept if finite, else the identity.  R [P][9], t [P][3] (unit), parallax [P] float64; votes [P][4],
+ *   degenerate [P] int32.  counts, inlier: as gfl_sfm_refit wrote them.
+ * gfl_sfm_triangulate: a = R K^-1 (x, y, 1), b = K^-1 (x2, y2, 1), c = a x b: the least-squares solution of z1 a + t = z2 b is
+ *   z1 = c . (b x t) / |c|^2, z2 = c . (a x t) / |c|^2; rho = 1 / z1 and weight = |c|^2 / (|a|^2 |b|^2) = sin^2 of the angle,
+ *   evaluated in float64 and stored as float32 [P][H][W]; both 0 where z1 <= 0, z2 <= 0, the pixel is not an inlier or the
+ *   pair is degenerate.
+ * gfl_sfm_median: per row m of M, the exact lower median of the float32 quotient a / b (b NULL: of a) over the pixels with
+ *   wa > w_min and wb > w_min (a NULL weight passes) and a finite quotient; median [M] float64 (NaN for none), count [M]
+ *   int32.  All arrays [M][H][W] float32.  The baseline ratio of a frame is this with a = rho of its forward pair and b = rho
+ *   of its backward pair.
+ * gfl_sfm_fuse: rho = (wf (rf sf[t]) + wb (rb sb[t])) / (wf + wb), weight = wf + wb, rho = 0 where the weight is 0; float32,
+ *   every operation rounded on its own; scale_f, scale_b [T] float64 on the device (1 / baseline), rounded to float32.
+ * gfl_sfm_fill: pull -- level l + 1 is (ceil(H_l / 2), ceil(W_l / 2)) down to 1 x 1, a pixel the weighted mean of the fine
+ *   pixels (min(2X + dx, W_l - 1), min(2Y + dy, H_l - 1)), dx, dy in {0, 1}, its weight a quarter of their weights' sum (value 0
+ *   without weight); push -- from the coarsest level upward a pixel WITHOUT weight takes the bilinear sample of the filled
+ *   coarser level at (x / 2 - 1/4, y / 2 - 1/4) clamped to that grid; then `sweeps` Jacobi sweeps of
+ *   min sum w (rho - rho0)^2 + lambda sum_pq (rho_p - rho_q)^2 over the 4-neighbours inside the image: with S, k their sum
+ *   (left, right, top, bottom) and number, rho <- rho0 + lambda (S - k rho0) / (w + lambda k) where w > 0, else S / k (kept for
+ *   lambda = 0); lambda [T] float64 on the device; depth [T][H][W] = 1 / max(rho, rho_min).  The sweeps run four per launch on
+ *   a 32 x 32 LDS tile with a ring of four pixels (the interior then has exactly the bits of four plain sweeps);
+ *   GFL_SFM_FUSED=0 in the environment (read at every call) launches every sweep on its own, with the same bits.
+ * GFL_ERR_INVALID, before any launch: P (M, T) < 1 or > 65535, H or W < 8 or > 16384, P H W > 2^30, a camera value that is not
+ *   finite or a focal <= 0, rounds, sweeps, e_floor, w_min, rho_min, min_parallax or min_share out of range or not finite, a
+ *   NULL pointer other than exclude / b / wa / wb, a workspace that is not 16-byte aligned.  GFL_ERR_WORKSPACE:
+ *   workspace_bytes < gfl_sfm_workspace_bytes(P, H, W) (0 for arguments it rejects; needs no device).  ONE layout
+ *   serves every entry, so the query is the refit's need -- about 19 bytes per pixel and problem -- and gfl_sfm_median and
+ *   gfl_sfm_fill ask for more than they touch (fill leaves the 8-byte values and the histograms alone).  No allocation, no
+ *   host synchronisation, everything on `stream`.  No float atomics: the sums are per-workgroup float64 partials folded in
+ *   a fixed order, the counts integer atomics -- the same inputs give the same bits, and a problem's result does not depend
+ *   on the others in its call. */
+size_t gfl_sfm_workspace_bytes(int P, int H, int W);
+int gfl_sfm_refit(const float* flow, const double* F_init, const uint8_t* exclude, int P, int H, int W, int rounds,
+                  double e_floor, double* F_out, int32_t* counts, double* median, uint8_t* inlier, void* workspace,
+                  size_t workspace_bytes, gfl_stream_t stream);
+int gfl_sfm_pose(const float* flow, const double* F, const uint8_t* inlier, const int32_t* counts, int P, int H, int W, double fx,
+                 double fy, double cx, double cy, double min_parallax, double min_share, double* R, double* t, int32_t* votes,
+                 double* parallax, int32_t* degenerate, void* workspace, size_t workspace_bytes, gfl_stream_t stream);
+int gfl_sfm_triangulate(const float* flow, const uint8_t* inlier, const double* R, const double* t, const int32_t* degenerate,
+                        int P, int H, int W, double fx, double fy, double cx, double cy, float* rho, float* weight,
+                        gfl_stream_t stream);
+int gfl_sfm_median(const float* a, const float* b, const float* wa, const float* wb, float w_min, int M, int H, int W,
+                   double* median, int32_t* count, void* workspace, size_t workspace_bytes, gfl_stream_t stream);
+int gfl_sfm_fuse(const float* rho_f, const float* w_f, const float* rho_b, const float* w_b, const double* scale_f,
+                 const double* scale_b, int T, int H, int W, float* rho, float* weight, gfl_stream_t stream);
+int gfl_sfm_fill(const float* rho0, const float* weight, const double* lambda, int T, int H, int W, int sweeps, float rho_min,
+                 float* depth, void* workspace, size_t workspace_bytes, gfl_stream_t stream);
 
 /* sizeof(gfl_fit_state), sizeof(gfl_fit_hyper): lets an FFI binding verify its struct mirrors */
 int gfl_abi_sizes(int* sizeof_fit_state, int* sizeof_fit_hyper);
