@@ -8,35 +8,32 @@
 // evaluates the same expression.
 //
 // gfl_epi_fundamental
-//   count     known pixels (integer atomics)
 //   solve     one thread per hypothesis: Hartley-normalised 8-point, null vector by cyclic Jacobi on A^T A (9 x 9, fully
 //             unrolled so that the matrices live in registers), rank 2 by Jacobi on F^T F, de-normalise, scale, sign
-//   6 x (hist, select)   exact lower median of the Sampson errors per hypothesis by radix selection on the bit pattern
-//             (errors are >= +0, so the patterns order like the values), 11 bits a pass, 9 in the last: the errors are
-//             recomputed in every pass, never stored.  hist: grid (pixel chunks, hypotheses), F and the 2048 bins in LDS,
-//             LDS integer atomics, one global integer atomic per non-empty bin; select: one workgroup per hypothesis finds
-//             the bin that holds the wanted rank.  Integer sums do not depend on their order: the same bits on every call.
+//   6 x (hist, select)   exact lower median of the Sampson errors per hypothesis by radix selection on their order keys,
+//             11 bits a pass, 9 in the last: the errors are recomputed in every pass, never stored.  hist: grid (pixel
+//             chunks, hypotheses), F and the 2048 bins in LDS, LDS integer atomics, one global integer atomic per
+//             non-empty bin; select: one workgroup per hypothesis finds the bin that holds the wanted rank (pass 0 learns
+//             the number of known pixels from the row's total).  Integer sums do not depend on their order: the same bits
+//             on every call.
 //   final     medians, the smallest (ties: lowest index), F_best
 // gfl_epi_mask
 //   err (Sampson error x ((H + W) / 2)^2 per pixel, the maximum by an integer atomic on the bit pattern), norm (err / max,
 //   threshold), then erosions / dilations with disc footprints.
+// The Jacobi, the tail of the 8-point fit, the Sampson error and the selection are gfl_epipolar.hpp's.
 #include <algorithm>
 #include <cmath>
 
-#include "gfl_common.hpp"
+#include "gfl_epipolar.hpp"
 
 namespace gfl {
 
 constexpr int EPI_BLOCK = 256;
 constexpr int EPI_SOLVE_BLOCK = 64;
-constexpr int EPI_BINS = 2048;                                  // 11 bits
-constexpr int EPI_PASSES = 6;
 constexpr int EPI_PER_BLOCK = EPI_BLOCK * 16;                   // pixels per workgroup of the hist pass
 constexpr int EPI_OPEN_R = 2, EPI_ERODE_R = 5, EPI_DILATE_R = 3;
-static_assert(EPI_BINS * sizeof(uint32_t) + 9 * sizeof(double) <= 64 * 1024, "LDS budget");
-
-__host__ __device__ inline int epi_pass_shift(int pass) { return pass < 5 ? 53 - 11 * pass : 0; }
-__host__ __device__ inline int epi_pass_width(int pass) { return pass < 5 ? 11 : 9; }
+static_assert(EPI_BLOCK == SELECT_BLOCK, "the hist pass flushes its bins with the selection's workgroup");
+static_assert(SELECT_BINS * sizeof(uint32_t) + 9 * sizeof(double) <= 64 * 1024, "LDS budget");
 
 struct EpiPoint {
     double x1, y1, x2, y2;
@@ -57,85 +54,6 @@ __host__ __device__ inline EpiPoint epi_point(const float* __restrict__ flow, in
     p.x1 = (double)x1; p.y1 = (double)y1; p.x2 = (double)x2; p.y2 = (double)y2;
     p.known = std::isfinite(x2) && std::isfinite(y2);
     return p;
-}
-
-// move_seg.py:57-71: d1 = F h1, d2 = F^T h2, z = h2 . d1, z^2 / (d1x^2 + d1y^2 + d2x^2 + d2y^2); sums from the left, no
-// contraction.  A zero denominator (the pixel is the epipole on both sides, or F is zero) gives 0.
-__host__ __device__ inline double epi_sampson(const double* F, double x1, double y1, double x2, double y2) {
-#pragma clang fp contract(off)
-    const double d1x = (F[0] * x1 + F[1] * y1) + F[2];
-    const double d1y = (F[3] * x1 + F[4] * y1) + F[5];
-    const double d1z = (F[6] * x1 + F[7] * y1) + F[8];
-    const double d2x = (F[0] * x2 + F[3] * y2) + F[6];
-    const double d2y = (F[1] * x2 + F[4] * y2) + F[7];
-    const double z = (x2 * d1x + y2 * d1y) + d1z;
-    const double den = ((d1x * d1x + d1y * d1y) + d2x * d2x) + d2y * d2y;
-    return den == 0.0 ? 0.0 : (z * z) / den;
-}
-
-// Cyclic Jacobi on a symmetric N x N matrix (upper triangle of M is used and ends as the eigenvalues on the diagonal), V
-// ends as the eigenvectors in its columns.  Every index is a compile-time constant after unrolling.
-template <int N>
-__host__ __device__ inline void epi_jacobi(double (&M)[N * N], double (&V)[N * N]) {
-#pragma unroll
-    for (int i = 0; i < N * N; ++i) V[i] = 0.0;
-#pragma unroll
-    for (int i = 0; i < N; ++i) V[i * N + i] = 1.0;
-    for (int sweep = 0; sweep < 40; ++sweep) {
-        double off = 0.0, diag = 0.0;
-#pragma unroll
-        for (int p = 0; p < N; ++p) {
-            diag += fabs(M[p * N + p]);
-#pragma unroll
-            for (int q = p + 1; q < N; ++q) off += fabs(M[p * N + q]);
-        }
-        if (!(off > 1e-36 * diag)) break;                        // (also leaves on a NaN)
-#pragma unroll
-        for (int p = 0; p < N - 1; ++p) {
-#pragma unroll
-            for (int q = p + 1; q < N; ++q) {
-                const double apq = M[p * N + q];
-                if (apq != 0.0) {
-                    const double theta = (M[q * N + q] - M[p * N + p]) / (2.0 * apq);
-                    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                    M[p * N + p] -= t * apq;
-                    M[q * N + q] += t * apq;
-                    M[p * N + q] = 0.0;
-#pragma unroll
-                    for (int k = 0; k < N; ++k) {
-                        if (k != p && k != q) {
-                            const int kp = k < p ? k * N + p : p * N + k, kq = k < q ? k * N + q : q * N + k;
-                            const double akp = M[kp], akq = M[kq];
-                            M[kp] = c * akp - s * akq;
-                            M[kq] = s * akp + c * akq;
-                        }
-                    }
-#pragma unroll
-                    for (int k = 0; k < N; ++k) {
-                        const double vkp = V[k * N + p], vkq = V[k * N + q];
-                        V[k * N + p] = c * vkp - s * vkq;
-                        V[k * N + q] = s * vkp + c * vkq;
-                    }
-                }
-            }
-        }
-    }
-}
-
-// the column of V that belongs to the smallest diagonal entry of M (first among equals), without a run-time index
-template <int N>
-__host__ __device__ inline void epi_smallest(const double (&M)[N * N], const double (&V)[N * N], double (&v)[N]) {
-    double best = M[0];
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = V[i * N];
-#pragma unroll
-    for (int j = 1; j < N; ++j) {
-        const bool less = M[j * N + j] < best;
-        best = less ? M[j * N + j] : best;
-#pragma unroll
-        for (int i = 0; i < N; ++i) v[i] = less ? V[i * N + j] : v[i];
-    }
 }
 
 // Hartley: centroid to 0, mean distance to sqrt(2).  Returns the scale; c is the centroid.
@@ -162,7 +80,7 @@ __host__ __device__ inline bool epi_solve8(double (&x1)[8], double (&y1)[8], dou
     double c1x, c1y, c2x, c2y;
     const double s1 = epi_normalise(x1, y1, c1x, c1y), s2 = epi_normalise(x2, y2, c2x, c2y);
     // A^T A of the rows [x2 x1, x2 y1, x2, y2 x1, y2 y1, y2, x1, y1, 1]: x2^T F x1 = 0 with F row-major
-    double M[81], V[81];
+    double M[81];
 #pragma unroll
     for (int i = 0; i < 81; ++i) M[i] = 0.0;
 #pragma unroll
@@ -173,48 +91,7 @@ __host__ __device__ inline bool epi_solve8(double (&x1)[8], double (&y1)[8], dou
 #pragma unroll
             for (int j = i; j < 9; ++j) M[i * 9 + j] += a[i] * a[j];
     }
-    epi_jacobi<9>(M, V);
-    double f[9];
-    epi_smallest<9>(M, V, f);
-    // rank 2: drop the smallest singular value, F - (F v) v^T with v the eigenvector of F^T F's smallest eigenvalue
-    double G[9], W3[9], v[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) G[i * 3 + j] = f[i] * f[j] + f[3 + i] * f[3 + j] + f[6 + i] * f[6 + j];
-    epi_jacobi<3>(G, W3);
-    epi_smallest<3>(G, W3, v);
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const double fv = f[r * 3] * v[0] + f[r * 3 + 1] * v[1] + f[r * 3 + 2] * v[2];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) f[r * 3 + j] -= fv * v[j];
-    }
-    // T2^T Fn T1, T = [s 0 -s cx; 0 s -s cy; 0 0 1]
-    const double t1[9] = {s1, 0.0, -s1 * c1x, 0.0, s1, -s1 * c1y, 0.0, 0.0, 1.0};
-    const double t2[9] = {s2, 0.0, -s2 * c2x, 0.0, s2, -s2 * c2y, 0.0, 0.0, 1.0};
-    double ft[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) ft[i * 3 + j] = f[i * 3] * t1[j] + f[i * 3 + 1] * t1[3 + j] + f[i * 3 + 2] * t1[6 + j];
-    double norm2 = 0.0, big = 0.0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const double g = t2[i] * ft[j] + t2[3 + i] * ft[3 + j] + t2[6 + i] * ft[6 + j];
-            F[i * 3 + j] = g;
-            norm2 += g * g;
-            big = fabs(g) > fabs(big) ? g : big;                 // (first among equal magnitudes)
-        }
-    const double scale = (big < 0.0 ? -1.0 : 1.0) / sqrt(norm2);
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-        F[i] *= scale;
-        ok = ok && std::isfinite(F[i]);
-    }
+    const bool ok = fundamental_from_normal(M, s1, c1x, c1y, s2, c2x, c2y, F);
     if (!ok) {
 #pragma unroll
         for (int i = 0; i < 9; ++i) F[i] = 0.0;
@@ -223,18 +100,6 @@ __host__ __device__ inline bool epi_solve8(double (&x1)[8], double (&y1)[8], dou
 }
 
 // ---------------------------------------------------------------------------------------------------------- fundamental
-__global__ void __launch_bounds__(EPI_BLOCK) epi_count_kernel(const float* __restrict__ flow, int W, int H, int n,
-                                                              uint32_t* __restrict__ n_known) {
-    __shared__ uint32_t cnt;
-    if (threadIdx.x == 0) cnt = 0;
-    __syncthreads();
-    uint32_t mine = 0;
-    for (int i = blockIdx.x * EPI_BLOCK + threadIdx.x; i < n; i += gridDim.x * EPI_BLOCK) mine += epi_point(flow, i, W, H).known;
-    if (mine) atomicAdd(&cnt, mine);
-    __syncthreads();
-    if (threadIdx.x == 0 && cnt) atomicAdd(n_known, cnt);
-}
-
 __global__ void __launch_bounds__(EPI_SOLVE_BLOCK) epi_solve_kernel(const float* __restrict__ flow, int W, int H, int n,
                                                                     const int32_t* __restrict__ samples, int K,
                                                                     double* __restrict__ Fk, int32_t* __restrict__ degenerate) {
@@ -269,20 +134,18 @@ __global__ void __launch_bounds__(EPI_SOLVE_BLOCK) epi_solve_kernel(const float*
     degenerate[k] = ok ? 0 : 1;
 }
 
-// grid (pixel chunks, K).  Counts, per hypothesis, the errors whose bits above this pass's digit equal the prefix found so
-// far, by digit.
+// grid (pixel chunks, K).  Counts, per hypothesis, the errors whose key agrees with the prefix found so far, by digit.
 __global__ void __launch_bounds__(EPI_BLOCK) epi_hist_kernel(const float* __restrict__ flow, int W, int H, int n,
                                                              const double* __restrict__ Fk,
                                                              const int32_t* __restrict__ degenerate,
                                                              const unsigned long long* __restrict__ prefix,
                                                              uint32_t* __restrict__ hist, int pass) {
     __shared__ double sF[9];
-    __shared__ uint32_t bins[EPI_BINS];
+    __shared__ uint32_t bins[SELECT_BINS];
     const int k = blockIdx.y, tid = threadIdx.x, lane = tid & (WAVE - 1);
-    if (degenerate[k]) return;                                   // (the whole workgroup)
-    const int shift = epi_pass_shift(pass), width = epi_pass_width(pass), nbins = 1 << width;
+    if (degenerate[k]) return;                                   // (the whole workgroup: the row stays zero)
     if (tid < 9) sF[tid] = Fk[(size_t)k * 9 + tid];
-    for (int b = tid; b < nbins; b += EPI_BLOCK) bins[b] = 0;
+    for (int b = tid; b < (1 << select_width(pass)); b += EPI_BLOCK) bins[b] = 0;
     __syncthreads();
     double F[9];
 #pragma unroll
@@ -296,73 +159,14 @@ __global__ void __launch_bounds__(EPI_BLOCK) epi_hist_kernel(const float* __rest
         if (i < end) {
             const EpiPoint p = epi_point(flow, i, W, H);
             if (p.known) {
-                const unsigned long long bits = (unsigned long long)__double_as_longlong(epi_sampson(F, p.x1, p.y1, p.x2, p.y2));
-                const unsigned long long upper = pass == 0 ? 0ull : bits >> (shift + width);
-                active = upper == want;
-                digit = (uint32_t)(bits >> shift) & (uint32_t)(nbins - 1);
+                const double e = sampson_error(F, p.x1, p.y1, p.x2, p.y2);
+                __builtin_assume(__builtin_bit_cast(long long, e) >= 0);     // (>= +0: the key is the bit pattern, sign bit set)
+                active = select_digit(order_key(e), want, pass, digit);
             }
         }
-        // inliers share their leading bits: the lanes that agree with the first active lane add once
-        const unsigned long long any = __ballot(active);
-        if (any) {
-            const int leader = __ffsll((long long)any) - 1;
-            const uint32_t ld = (uint32_t)__shfl((int)digit, leader);
-            const unsigned long long same = __ballot(active && digit == ld);
-            if (lane == leader) atomicAdd(&bins[ld], (uint32_t)__popcll(same));
-            else if (active && digit != ld) atomicAdd(&bins[digit], 1u);
-        }
+        select_lane_add(bins, active, digit, lane);
     }
-    __syncthreads();
-    uint32_t* row = hist + (size_t)k * EPI_BINS;
-    for (int b = tid; b < nbins; b += EPI_BLOCK)
-        if (bins[b]) atomicAdd(&row[b], bins[b]);
-}
-
-// one workgroup per hypothesis: the bin that holds the wanted rank becomes the next digit of the prefix; the row of counts is
-// zeroed for the next pass
-__global__ void __launch_bounds__(EPI_BLOCK) epi_select_kernel(uint32_t* __restrict__ hist, const int32_t* __restrict__ degenerate,
-                                                               const uint32_t* __restrict__ n_known,
-                                                               unsigned long long* __restrict__ prefix,
-                                                               uint32_t* __restrict__ rank, int pass) {
-    __shared__ uint32_t scan[EPI_BLOCK];
-    const int k = blockIdx.x, tid = threadIdx.x;
-    if (degenerate[k]) return;
-    const int width = epi_pass_width(pass), nbins = 1 << width, per = nbins / EPI_BLOCK;   // 8 or 2
-    uint32_t* row = hist + (size_t)k * EPI_BINS;
-    const uint32_t r = pass == 0 ? (*n_known - 1u) / 2u : rank[k];     // (a hypothesis that is not degenerate has 8 known pixels)
-    const unsigned long long pref = pass == 0 ? 0ull : prefix[k];
-    uint32_t c[8], total = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        c[j] = j < per ? row[tid * per + j] : 0u;
-        total += c[j];
-    }
-    scan[tid] = total;
-    __syncthreads();
-    for (int s = 1; s < EPI_BLOCK; s <<= 1) {                   // inclusive scan
-        const uint32_t add = tid >= s ? scan[tid - s] : 0u;
-        __syncthreads();
-        scan[tid] += add;
-        __syncthreads();
-    }
-    const uint32_t before = scan[tid] - total;
-    if (r >= before && r < before + total) {                    // exactly one thread: the row's sum exceeds r
-        uint32_t cum = before;
-        int bin = 0;
-        bool found = false;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            if (!found && j < per) {
-                if (r < cum + c[j]) { bin = j; found = true; }
-                else cum += c[j];
-            }
-        }
-        prefix[k] = (pref << width) | (unsigned long long)(tid * per + bin);
-        rank[k] = r - cum;
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-        if (j < per) row[tid * per + j] = 0u;
+    select_flush(bins, hist + (size_t)k * SELECT_BINS, pass);
 }
 
 // one workgroup: the medians, the smallest of them (the lowest index among equals), its F
@@ -376,7 +180,7 @@ __global__ void __launch_bounds__(EPI_BLOCK) epi_final_kernel(const double* __re
     double v = INFINITY;
     int a = -1;
     for (int k = tid; k < K; k += EPI_BLOCK) {
-        const double m = degenerate[k] ? INFINITY : __longlong_as_double((long long)prefix[k]);
+        const double m = degenerate[k] ? INFINITY : order_unkey(prefix[k]);
         if (medians) medians[k] = m;
         if (!degenerate[k] && (a < 0 || m < v)) { v = m; a = k; }    // (ascending k: the first of equal medians stays)
     }
@@ -412,7 +216,7 @@ __global__ void __launch_bounds__(EPI_BLOCK) epi_err_kernel(const float* __restr
         const EpiPoint p = epi_point(flow, i, W, H);
         double e = 0.0;
         if (p.known) {
-            e = epi_sampson(F, p.x1, p.y1, p.x2, p.y2) * fac2;
+            e = sampson_error(F, p.x1, p.y1, p.x2, p.y2) * fac2;
             if (!std::isfinite(e)) e = 0.0;                      // (an F that is not finite)
         }
         err[i] = e;
@@ -466,7 +270,7 @@ __global__ void __launch_bounds__(EPI_BLOCK) epi_morph_kernel(const uint8_t* __r
 // the workspace of both entries: the regions of gfl_epi_mask first (they do not depend on K)
 struct EpiWorkspace {
     double* err; unsigned long long* max_bits; uint8_t* mask; uint8_t* tmp;
-    double* Fk; int32_t* degenerate; unsigned long long* prefix; uint32_t* rank; uint32_t* n_known; uint32_t* hist;
+    double* Fk; int32_t* degenerate; Select sel;
 };
 inline EpiWorkspace epi_carve(Arena& a, int W, int H, int K) {
     const size_t n = (size_t)W * H;
@@ -477,10 +281,7 @@ inline EpiWorkspace epi_carve(Arena& a, int W, int H, int K) {
     w.tmp = a.take<uint8_t>("tmp", n);
     w.Fk = a.take<double>("F", (size_t)K * 9);
     w.degenerate = a.take<int32_t>("degenerate", K);
-    w.prefix = a.take<unsigned long long>("prefix", K);
-    w.rank = a.take<uint32_t>("rank", K);
-    w.n_known = a.take<uint32_t>("n_known", 1);
-    w.hist = a.take<uint32_t>("hist", (size_t)K * EPI_BINS);
+    w.sel = select_carve(a, K);
     return w;
 }
 // (2^30 pixels at most: pixel indices and the strides added to them stay inside an int)
@@ -511,23 +312,19 @@ int gfl_epi_fundamental(const float* flow, int W, int H, const int32_t* samples,
     const int n = W * H;
     double* Fk = F_all ? F_all : w.Fk;
     hipStream_t s = (hipStream_t)stream;
-    int rc = check(hipMemsetAsync(w.n_known, 0, sizeof(uint32_t), s));
+    int rc = check(hipMemsetAsync(w.sel.hist, 0, (size_t)K * SELECT_BINS * sizeof(uint32_t), s));
     if (rc != GFL_OK) return rc;
-    rc = check(hipMemsetAsync(w.hist, 0, (size_t)K * EPI_BINS * sizeof(uint32_t), s));
-    if (rc != GFL_OK) return rc;
-    epi_count_kernel<<<epi_stride_grid(n), EPI_BLOCK, 0, s>>>(flow, W, H, n, w.n_known);
-    if ((rc = check_launch()) != GFL_OK) return rc;
     epi_solve_kernel<<<(K + EPI_SOLVE_BLOCK - 1) / EPI_SOLVE_BLOCK, EPI_SOLVE_BLOCK, 0, s>>>(flow, W, H, n, samples, K, Fk,
                                                                                            w.degenerate);
     if ((rc = check_launch()) != GFL_OK) return rc;
     const int chunks = (n + EPI_PER_BLOCK - 1) / EPI_PER_BLOCK;
-    for (int pass = 0; pass < EPI_PASSES; ++pass) {
-        epi_hist_kernel<<<dim3(chunks, K), EPI_BLOCK, 0, s>>>(flow, W, H, n, Fk, w.degenerate, w.prefix, w.hist, pass);
+    for (int pass = 0; pass < SELECT_PASSES; ++pass) {
+        epi_hist_kernel<<<dim3(chunks, K), EPI_BLOCK, 0, s>>>(flow, W, H, n, Fk, w.degenerate, w.sel.prefix, w.sel.hist, pass);
         if ((rc = check_launch()) != GFL_OK) return rc;
-        epi_select_kernel<<<K, EPI_BLOCK, 0, s>>>(w.hist, w.degenerate, w.n_known, w.prefix, w.rank, pass);
+        select_launch(w.sel, K, pass, s);
         if ((rc = check_launch()) != GFL_OK) return rc;
     }
-    epi_final_kernel<<<1, EPI_BLOCK, 0, s>>>(Fk, w.degenerate, w.prefix, K, medians, F_best, best);
+    epi_final_kernel<<<1, EPI_BLOCK, 0, s>>>(Fk, w.degenerate, w.sel.prefix, K, medians, F_best, best);
     return check_launch();
 }
 

@@ -16,37 +16,24 @@
 // cross products cancel: in float32 the error would grow with 1 / sin of the parallax angle) and stored as float32 -- the
 // kernels stay bound by the bytes they move.  Fusion, fill and sweeps are float32, products and sums rounded separately.
 // The only atomics are integer ones (histograms, votes, counts), whose sums do not depend on their order.
-// (The cyclic Jacobi is gfl_epi.hip's routine, restated here: that file's kernels keep their translation unit to themselves.)
+// The Jacobi, the tail of the 8-point fit, the Sampson error and the selection are gfl_epipolar.hpp's.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 
-#include "gfl_common.hpp"
+#include "gfl_epipolar.hpp"
 
 namespace gfl {
 
 constexpr int SFM_BLOCK = 256;
 constexpr int SFM_PER_BLOCK = SFM_BLOCK * 16;                   // pixels per workgroup of a histogram or sum pass
-constexpr int SFM_BINS = 2048;                                  // 11 bits
-constexpr int SFM_PASSES = 6;
 constexpr int SFM_NSUM = 48;                                    // a row of partial sums (45 used)
 constexpr int SFM_SUMS = 64;                                    // per pair: [0..4] count and coordinate sums, [5..6] distances, [8..52] A^T A
 constexpr int SFM_MAX_LEVELS = 16;
 constexpr int SFM_R = 32, SFM_S = 4, SFM_PPT = 4;               // fused sweeps: region side, sweeps per launch = ring, rows per lane
 constexpr int SFM_MAX_Z = 65535;
 
-__host__ __device__ inline int sfm_pass_shift(int pass) { return pass < 5 ? 53 - 11 * pass : 0; }
-__host__ __device__ inline int sfm_pass_width(int pass) { return pass < 5 ? 11 : 9; }
-
-// a double that is not a NaN as an unsigned key that orders like the value
-__host__ __device__ inline unsigned long long sfm_key(double v) {
-    const unsigned long long b = (unsigned long long)__builtin_bit_cast(long long, v);
-    return (b >> 63) ? ~b : (b | (1ull << 63));
-}
-__host__ __device__ inline double sfm_unkey(unsigned long long k) {
-    const unsigned long long b = (k >> 63) ? (k & ~(1ull << 63)) : ~k;
-    return __builtin_bit_cast(double, (long long)b);
-}
+static_assert(SFM_BLOCK == SELECT_BLOCK, "the hist pass flushes its bins with the selection's workgroup");
 
 // ------------------------------------------------------------------------------------------ exact lower median, M rows
 // val [M][n] float64, NaN = absent.  grid (chunks, M): counts the values whose key agrees with the prefix found so far, by digit.
@@ -54,11 +41,10 @@ __global__ void __launch_bounds__(SFM_BLOCK) sfm_hist_kernel(const double* __res
                                                              const unsigned long long* __restrict__ prefix,
                                                              const uint32_t* __restrict__ count, uint32_t* __restrict__ hist,
                                                              int pass) {
-    __shared__ uint32_t bins[SFM_BINS];
+    __shared__ uint32_t bins[SELECT_BINS];
     const int m = blockIdx.y, tid = threadIdx.x, lane = tid & (WAVE - 1);
     if (pass > 0 && count[m] == 0) return;                       // (the whole workgroup)
-    const int shift = sfm_pass_shift(pass), width = sfm_pass_width(pass), nbins = 1 << width;
-    for (int b = tid; b < nbins; b += SFM_BLOCK) bins[b] = 0;
+    for (int b = tid; b < (1 << select_width(pass)); b += SFM_BLOCK) bins[b] = 0;
     __syncthreads();
     const unsigned long long want = pass == 0 ? 0ull : prefix[m];
     const double* v = val + (size_t)m * n;
@@ -69,166 +55,22 @@ __global__ void __launch_bounds__(SFM_BLOCK) sfm_hist_kernel(const double* __res
         uint32_t digit = 0;
         if (i < end) {
             const double e = v[i];
-            if (e == e) {
-                const unsigned long long key = sfm_key(e);
-                const unsigned long long upper = pass == 0 ? 0ull : key >> (shift + width);
-                active = upper == want;
-                digit = (uint32_t)(key >> shift) & (uint32_t)(nbins - 1);
-            }
+            if (e == e) active = select_digit(order_key(e), want, pass, digit);
         }
-        // neighbours share their leading bits: the lanes that agree with the first active lane add once
-        const unsigned long long any = __ballot(active);
-        if (any) {
-            const int leader = __ffsll((long long)any) - 1;
-            const uint32_t ld = (uint32_t)__shfl((int)digit, leader);
-            const unsigned long long same = __ballot(active && digit == ld);
-            if (lane == leader) atomicAdd(&bins[ld], (uint32_t)__popcll(same));
-            else if (active && digit != ld) atomicAdd(&bins[digit], 1u);
-        }
+        select_lane_add(bins, active, digit, lane);
     }
-    __syncthreads();
-    uint32_t* row = hist + (size_t)m * SFM_BINS;
-    for (int b = tid; b < nbins; b += SFM_BLOCK)
-        if (bins[b]) atomicAdd(&row[b], bins[b]);
+    select_flush(bins, hist + (size_t)m * SELECT_BINS, pass);
 }
 
-// one workgroup per row: pass 0 learns the number of values (the rank is (count - 1) / 2); the bin that holds the wanted rank
-// becomes the next digit of the prefix; the row of counts is zeroed for the next pass
-__global__ void __launch_bounds__(SFM_BLOCK) sfm_select_kernel(uint32_t* __restrict__ hist, unsigned long long* __restrict__ prefix,
-                                                               uint32_t* __restrict__ rank, uint32_t* __restrict__ count, int pass) {
-    __shared__ uint32_t scan[SFM_BLOCK];
-    const int m = blockIdx.x, tid = threadIdx.x;
-    if (pass > 0 && count[m] == 0) return;
-    const int width = sfm_pass_width(pass), nbins = 1 << width, per = nbins / SFM_BLOCK;   // 8 or 2
-    uint32_t* row = hist + (size_t)m * SFM_BINS;
-    // read before the scan's barriers: the one thread that finds the bin stores both after them
-    const uint32_t r_in = pass == 0 ? 0u : rank[m];
-    const unsigned long long pref = pass == 0 ? 0ull : prefix[m];
-    uint32_t c[8], total = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        c[j] = j < per ? row[tid * per + j] : 0u;
-        total += c[j];
-    }
-    scan[tid] = total;
-    __syncthreads();
-    for (int s = 1; s < SFM_BLOCK; s <<= 1) {                   // inclusive scan
-        const uint32_t add = tid >= s ? scan[tid - s] : 0u;
-        __syncthreads();
-        scan[tid] += add;
-        __syncthreads();
-    }
-    const uint32_t all = scan[SFM_BLOCK - 1];
-    const uint32_t r = pass == 0 ? (all > 0 ? (all - 1u) / 2u : 0u) : r_in;
-    const uint32_t before = scan[tid] - total;
-    if (all > 0 && r >= before && r < before + total) {         // exactly one thread
-        uint32_t cum = before;
-        int bin = 0;
-        bool found = false;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            if (!found && j < per) {
-                if (r < cum + c[j]) { bin = j; found = true; }
-                else cum += c[j];
-            }
-        }
-        prefix[m] = (pref << width) | (unsigned long long)(tid * per + bin);
-        rank[m] = r - cum;
-    }
-    if (pass == 0 && tid == 0) count[m] = all;
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-        if (j < per) row[tid * per + j] = 0u;
-}
-
-struct SfmSelect { uint32_t* hist; unsigned long long* prefix; uint32_t* rank; uint32_t* count; };
-
-// the median of row m after the six passes (NaN for a row without values)
-__device__ inline double sfm_median_of(const unsigned long long* prefix, const uint32_t* count, int m) {
-    return count[m] ? sfm_unkey(prefix[m]) : (double)NAN;
-}
-
-static int sfm_run_select(const double* val, int M, int n, const SfmSelect& s, hipStream_t st) {
-    int rc = check(hipMemsetAsync(s.hist, 0, (size_t)M * SFM_BINS * sizeof(uint32_t), st));
+static int sfm_run_select(const double* val, int M, int n, const Select& s, hipStream_t st) {
+    int rc = check(hipMemsetAsync(s.hist, 0, (size_t)M * SELECT_BINS * sizeof(uint32_t), st));
     if (rc != GFL_OK) return rc;
     const int chunks = (n + SFM_PER_BLOCK - 1) / SFM_PER_BLOCK;
-    for (int pass = 0; pass < SFM_PASSES; ++pass) {
+    for (int pass = 0; pass < SELECT_PASSES; ++pass) {
         sfm_hist_kernel<<<dim3(chunks, M), SFM_BLOCK, 0, st>>>(val, n, s.prefix, s.count, s.hist, pass);
-        sfm_select_kernel<<<M, SFM_BLOCK, 0, st>>>(s.hist, s.prefix, s.rank, s.count, pass);
+        select_launch(s, M, pass, st);
     }
     return check_launch();
-}
-
-// ---------------------------------------------------------------------------------------------------- small dense algebra
-// Cyclic Jacobi on a symmetric N x N matrix (upper triangle of M is used and ends as the eigenvalues on the diagonal), V ends
-// as the eigenvectors in its columns.  Every index is a compile-time constant after unrolling.
-template <int N>
-__host__ __device__ inline void sfm_jacobi(double (&M)[N * N], double (&V)[N * N]) {
-#pragma unroll
-    for (int i = 0; i < N * N; ++i) V[i] = 0.0;
-#pragma unroll
-    for (int i = 0; i < N; ++i) V[i * N + i] = 1.0;
-    for (int sweep = 0; sweep < 40; ++sweep) {
-        double off = 0.0, diag = 0.0;
-#pragma unroll
-        for (int p = 0; p < N; ++p) {
-            diag += fabs(M[p * N + p]);
-#pragma unroll
-            for (int q = p + 1; q < N; ++q) off += fabs(M[p * N + q]);
-        }
-        if (!(off > 1e-36 * diag)) break;                        // (also leaves on a NaN)
-#pragma unroll
-        for (int p = 0; p < N - 1; ++p) {
-#pragma unroll
-            for (int q = p + 1; q < N; ++q) {
-                const double apq = M[p * N + q];
-                if (apq != 0.0) {
-                    const double theta = (M[q * N + q] - M[p * N + p]) / (2.0 * apq);
-                    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                    M[p * N + p] -= t * apq;
-                    M[q * N + q] += t * apq;
-                    M[p * N + q] = 0.0;
-#pragma unroll
-                    for (int k = 0; k < N; ++k) {
-                        if (k != p && k != q) {
-                            const int kp = k < p ? k * N + p : p * N + k, kq = k < q ? k * N + q : q * N + k;
-                            const double akp = M[kp], akq = M[kq];
-                            M[kp] = c * akp - s * akq;
-                            M[kq] = s * akp + c * akq;
-                        }
-                    }
-#pragma unroll
-                    for (int k = 0; k < N; ++k) {
-                        const double vkp = V[k * N + p], vkq = V[k * N + q];
-                        V[k * N + p] = c * vkp - s * vkq;
-                        V[k * N + q] = s * vkp + c * vkq;
-                    }
-                }
-            }
-        }
-    }
-}
-
-// the column of V that belongs to the smallest diagonal entry of M (first among equals), without a run-time index
-template <int N>
-__host__ __device__ inline void sfm_smallest(const double (&M)[N * N], const double (&V)[N * N], double (&v)[N]) {
-    double best = M[0];
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = V[i * N];
-#pragma unroll
-    for (int j = 1; j < N; ++j) {
-        const bool less = M[j * N + j] < best;
-        best = less ? M[j * N + j] : best;
-#pragma unroll
-        for (int i = 0; i < N; ++i) v[i] = less ? V[i * N + j] : v[i];
-    }
-}
-
-__host__ __device__ inline bool sfm_finite9(const double* F) {
-    bool ok = true;
-    for (int i = 0; i < 9; ++i) ok = ok && std::isfinite(F[i]);
-    return ok;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- refit
@@ -245,18 +87,6 @@ __device__ inline SfmPoint sfm_point(const float* __restrict__ flow, int i, int 
     return p;
 }
 
-// z = x2^T F x1, z^2 / (d1x^2 + d1y^2 + d2x^2 + d2y^2), d1 = F x1, d2 = F^T x2; a zero denominator gives 0
-__device__ inline double sfm_sampson(const double* F, const SfmPoint& p) {
-    const double d1x = (F[0] * p.x1 + F[1] * p.y1) + F[2];
-    const double d1y = (F[3] * p.x1 + F[4] * p.y1) + F[5];
-    const double d1z = (F[6] * p.x1 + F[7] * p.y1) + F[8];
-    const double d2x = (F[0] * p.x2 + F[3] * p.y2) + F[6];
-    const double d2y = (F[1] * p.x2 + F[4] * p.y2) + F[7];
-    const double z = (p.x2 * d1x + p.y2 * d1y) + d1z;
-    const double den = ((d1x * d1x + d1y * d1y) + d2x * d2x) + d2y * d2y;
-    return den == 0.0 ? 0.0 : (z * z) / den;
-}
-
 // val = the Sampson error of every known, unexcluded pixel, NaN elsewhere (and everywhere under an F that is not finite)
 __global__ void __launch_bounds__(SFM_BLOCK) sfm_error_kernel(const float* __restrict__ flow, const double* __restrict__ Fp,
                                                               const uint8_t* __restrict__ exclude, int W, int n,
@@ -265,7 +95,7 @@ __global__ void __launch_bounds__(SFM_BLOCK) sfm_error_kernel(const float* __res
     double F[9];
 #pragma unroll
     for (int i = 0; i < 9; ++i) F[i] = Fp[(size_t)p * 9 + i];
-    const bool ok = sfm_finite9(F);
+    const bool ok = finite9(F);
     const float* f = flow + (size_t)p * n * 2;
     const int start = blockIdx.x * SFM_PER_BLOCK, end = min(start + SFM_PER_BLOCK, n);
     for (int i = start + threadIdx.x; i < end; i += SFM_BLOCK) {
@@ -273,7 +103,7 @@ __global__ void __launch_bounds__(SFM_BLOCK) sfm_error_kernel(const float* __res
         if (ok && !(exclude && exclude[(size_t)p * n + i])) {
             const SfmPoint pt = sfm_point(f, i, W);
             if (pt.known) {
-                e = sfm_sampson(F, pt);
+                e = sampson_error(F, pt.x1, pt.y1, pt.x2, pt.y2);
                 if (!std::isfinite(e)) e = NAN;
             }
         }
@@ -287,7 +117,7 @@ __global__ void sfm_threshold_kernel(const unsigned long long* __restrict__ pref
                                      int32_t* __restrict__ counts) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= P) return;
-    const double med = sfm_median_of(prefix, count, p);
+    const double med = median_of(prefix, count, p);
     thr[p] = count[p] ? fmax(k2 * med, e_floor) : -1.0;          // (no usable pixel: nothing is an inlier)
     median[p] = med;
     counts[2 * p] = (int32_t)count[p];
@@ -370,7 +200,7 @@ __global__ void __launch_bounds__(WAVE) sfm_solve_kernel(const double* __restric
     if (!(cnt >= 8.0)) return;
     const double c1x = sm[1] / cnt, c1y = sm[2] / cnt, c2x = sm[3] / cnt, c2y = sm[4] / cnt;
     const double s1 = sqrt(2.0) / (sm[5] / cnt), s2 = sqrt(2.0) / (sm[6] / cnt);
-    double M[81], V[81];
+    double M[81], F[9];
 #pragma unroll
     for (int i = 0; i < 81; ++i) M[i] = 0.0;
     {
@@ -380,49 +210,7 @@ __global__ void __launch_bounds__(WAVE) sfm_solve_kernel(const double* __restric
 #pragma unroll
             for (int c = r; c < 9; ++c) M[r * 9 + c] = sm[8 + k++];
     }
-    sfm_jacobi<9>(M, V);
-    double f[9];
-    sfm_smallest<9>(M, V, f);
-    // rank 2: drop the smallest singular value, F - (F v) v^T with v the eigenvector of F^T F's smallest eigenvalue
-    double G[9], W3[9], v[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) G[i * 3 + j] = f[i] * f[j] + f[3 + i] * f[3 + j] + f[6 + i] * f[6 + j];
-    sfm_jacobi<3>(G, W3);
-    sfm_smallest<3>(G, W3, v);
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const double fv = f[r * 3] * v[0] + f[r * 3 + 1] * v[1] + f[r * 3 + 2] * v[2];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) f[r * 3 + j] -= fv * v[j];
-    }
-    // T2^T Fn T1, T = [s 0 -s cx; 0 s -s cy; 0 0 1]
-    const double t1[9] = {s1, 0.0, -s1 * c1x, 0.0, s1, -s1 * c1y, 0.0, 0.0, 1.0};
-    const double t2[9] = {s2, 0.0, -s2 * c2x, 0.0, s2, -s2 * c2y, 0.0, 0.0, 1.0};
-    double ft[9], F[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) ft[i * 3 + j] = f[i * 3] * t1[j] + f[i * 3 + 1] * t1[3 + j] + f[i * 3 + 2] * t1[6 + j];
-    double norm2 = 0.0, big = 0.0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const double g = t2[i] * ft[j] + t2[3 + i] * ft[3 + j] + t2[6 + i] * ft[6 + j];
-            F[i * 3 + j] = g;
-            norm2 += g * g;
-            big = fabs(g) > fabs(big) ? g : big;                 // (first among equal magnitudes)
-        }
-    const double scale = (big < 0.0 ? -1.0 : 1.0) / sqrt(norm2);
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-        F[i] *= scale;
-        ok = ok && std::isfinite(F[i]);
-    }
-    if (ok) {
+    if (fundamental_from_normal(M, s1, c1x, c1y, s2, c2x, c2y, F)) {
 #pragma unroll
         for (int i = 0; i < 9; ++i) Fio[(size_t)p * 9 + i] = F[i];
     }
@@ -512,8 +300,8 @@ __global__ void __launch_bounds__(WAVE) sfm_candidates_kernel(const double* __re
     for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int j = 0; j < 3; ++j) G[i * 3 + j] = (E[i] * E[j] + E[3 + i] * E[3 + j]) + E[6 + i] * E[6 + j];
-    sfm_jacobi<3>(G, V);
-    sfm_smallest<3>(G, V, v3);
+    jacobi_sym<3>(G, V);
+    smallest_column<3>(G, V, v3);
     // which column was the smallest: the other two, in cyclic order, span the plane of the two large singular values
     int js = 0;
     {
@@ -635,11 +423,11 @@ __global__ void sfm_flags_kernel(const double* __restrict__ Fp, const int32_t* _
                                  double* __restrict__ parallax, int32_t* __restrict__ degenerate) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= P) return;
-    double par = sfm_median_of(prefix, count, p);
+    double par = median_of(prefix, count, p);
     if (!(par == par)) par = 0.0;
     const int usable = counts[2 * p], inl = counts[2 * p + 1];
-    bool bad = usable < 8 || (double)inl < min_share * (double)usable || !sfm_finite9(Fp + (size_t)p * 9) || !(par >= min_parallax);
-    const bool rok = sfm_finite9(R + (size_t)p * 9);
+    bool bad = usable < 8 || (double)inl < min_share * (double)usable || !finite9(Fp + (size_t)p * 9) || !(par >= min_parallax);
+    const bool rok = finite9(R + (size_t)p * 9);
     bad = bad || !rok || !(std::isfinite(t[3 * p]) && std::isfinite(t[3 * p + 1]) && std::isfinite(t[3 * p + 2]));
     if (bad) {
         for (int i = 0; i < 3; ++i) t[(size_t)p * 3 + i] = 0.0;
@@ -704,7 +492,7 @@ __global__ void sfm_median_out_kernel(const unsigned long long* __restrict__ pre
                                       double* __restrict__ median, int32_t* __restrict__ counts) {
     const int m = blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= M) return;
-    median[m] = sfm_median_of(prefix, count, m);
+    median[m] = median_of(prefix, count, m);
     counts[m] = (int32_t)count[m];
 }
 
@@ -886,7 +674,7 @@ static int sfm_levels(int H, int W, int* hs, int* ws) {
 }
 
 struct SfmWorkspace {
-    double* val; SfmSelect sel; double* thr; double* partial; double* sums; double* cand;
+    double* val; Select sel; double* thr; double* partial; double* sums; double* cand;
     float* x0; float* x1; float* pv[SFM_MAX_LEVELS]; float* pw[SFM_MAX_LEVELS];
 };
 
@@ -895,10 +683,7 @@ static SfmWorkspace sfm_carve(Arena& a, int P, int H, int W) {
     const size_t chunks = (n + SFM_PER_BLOCK - 1) / SFM_PER_BLOCK;
     SfmWorkspace w;
     w.val = a.take<double>("sfm val", N);
-    w.sel.hist = a.take<uint32_t>("sfm hist", (size_t)P * SFM_BINS);
-    w.sel.prefix = a.take<unsigned long long>("sfm prefix", P);
-    w.sel.rank = a.take<uint32_t>("sfm rank", P);
-    w.sel.count = a.take<uint32_t>("sfm count", P);
+    w.sel = select_carve(a, P);
     w.thr = a.take<double>("sfm thr", P);
     w.partial = a.take<double>("sfm partial", (size_t)P * chunks * SFM_NSUM);
     w.sums = a.take<double>("sfm sums", (size_t)P * SFM_SUMS);

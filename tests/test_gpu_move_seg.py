@@ -1,7 +1,8 @@
 """The move mask from the flow on the device (``-m gpu``; gfl_epi_fundamental, gfl_epi_mask, gflow_amd/move_seg.py) through
 the C ABI, every output pre-filled with garbage, against the float64 restatement (tests/move_seg_ref.py) on the scenes of
 tests/test_move_seg_host.py: 40 x 56 and 37 x 53 (no multiple of a workgroup's share) with K = 64, a third with unknown
-pixels and broken samples, a fourth of 8 x 8 where disk(5) covers most of the image.
+pixels and broken samples, a fourth of 8 x 8 where disk(5) covers most of the image; and 2 x 4 and 3 x 4 with eight known
+pixels, where the median's rank rests on the count that the selection's first pass finds.
 
 Bounds.  F_CONST: ||F_device - F_restatement|| <= F_CONST * eps64 * lambda_max / lambda_1 -- the form eigenvector perturbation
 theory gives for a null vector taken from A^T A; the theory does not give the constant, so it is measured: the largest ratio
@@ -230,6 +231,47 @@ def test_zero_flow_and_all_degenerate():
         assert np.isposinf(fit["medians"]).all()
     rc, got = _mask(nothing, skew)
     assert rc == 0 and not any(a.any() for a in got.values())
+
+
+# ------------------------------------------------------------------------------------------- 5b: the smallest images, the rank
+def _tiny_case(H, W, seed, unknown=()):
+    flow = np.random.default_rng(seed).uniform(-1.5, 1.5, (H, W, 2)).astype(np.float32)
+    flow.reshape(-1, 2)[list(unknown), 0] = np.inf
+    return flow, np.setdiff1d(np.arange(H * W), unknown).astype(np.int32)
+
+
+def _check_tiny(flow, samples, got):
+    """the median's rank comes from the count the selection's first pass finds: (8 - 1) // 2 of the eight known pixels"""
+    assert got["best"] == 0 and np.isfinite(got["F_all"][0]).all() and got["F_all"][0].any()
+    want = R.median_of(flow, got["F_all"][0])
+    print(f"tiny {flow.shape[0]}x{flow.shape[1]}: median {got['medians'][0]:.3e}, the restatement's {want:.3e}")
+    assert got["medians"][0] == want
+    np.testing.assert_array_equal(got["F"], got["F_all"][0])
+    rc, again = _fundamental(flow, samples)
+    assert rc == 0 and again["best"] == 0
+    for name in ("F_all", "medians", "F"):
+        assert again[name].tobytes() == got[name].tobytes(), name
+
+
+def test_eight_pixels_one_hypothesis():
+    for seed in (0, 1, 2):
+        flow, known = _tiny_case(2, 4, seed)
+        assert known.tolist() == list(range(8))
+        rc, got = _fundamental(flow, known[None])
+        assert rc == 0
+        _check_tiny(flow, known[None], got)
+
+
+def test_eight_known_of_twelve_and_a_degenerate_hypothesis():
+    for seed in (0, 1, 2):
+        flow, known = _tiny_case(3, 4, seed, unknown=(1, 5, 6, 10))
+        assert known.size == 8
+        samples = np.stack([known, known])
+        samples[1, 0] = 1                                        # an unknown pixel: degenerate
+        rc, got = _fundamental(flow, samples)
+        assert rc == 0
+        assert np.isposinf(got["medians"][1]) and not got["F_all"][1].any()
+        _check_tiny(flow, samples, got)
 
 
 # ----------------------------------------------------------------------------------------------------------- 6: repeatability
