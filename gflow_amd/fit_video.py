@@ -54,7 +54,8 @@ def _parser():
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("--sequence", action="append", default=None,
                     help="path of a prepared sequence folder (images + the reference's sibling folders, "
-                         "gflow_amd/io.py); may be given several times, one clip each; default: synthetic clips")
+                         "gflow_amd/io.py), or of a Motion-JPEG .avi file that stands for the folder of its frames; may be "
+                         "given several times, one clip each; default: synthetic clips")
     ap.add_argument("--resize", type=int, default=None, help="shorter image side after loading a --sequence")
     ap.add_argument("--blur", action="store_true",
                     help="with --sequence: GaussianBlur(7, 5.0) on the image, the occlusion mask and the flow after the resize "
@@ -62,6 +63,10 @@ def _parser():
     ap.add_argument("--prep", choices=("host", "device"), default="host",
                     help="with --sequence: where the decoded files are converted, resized and blurred -- on the host with "
                          "torch, one file at a time, or as whole stacks on this rank's device (gflow_amd.prep)")
+    ap.add_argument("--decode", choices=("host", "device"), default="host",
+                    help="with --sequence: where the image files are decoded -- PIL on the host, or the JPEG files as one stack "
+                         "on this rank's device (gflow_amd.video.decode_jpeg: the same bits; implies --prep device).  A "
+                         "--sequence that is a .avi file is always decoded and prepared on the device")
     ap.add_argument("--deterministic", action="store_true",
                     help="bit-identical results for identical inputs (the library's deterministic mode, INTEGRATION.md)")
     ap.add_argument("--track", action="store_true",
@@ -191,7 +196,9 @@ def _load_clips(args, mine, lengths, dev):
             clips[ci] = gio.load_sequence(args.sequence[ci], resize=args.resize,
                                           move_masks="epipolar" if args.make_move_masks else "files",
                                           occ_masks="flow" if args.make_occ_masks else "files", blur=args.blur,
-                                          device=dev if args.prep == "device" else None,
+                                          device=dev if (args.prep == "device" or args.decode == "device"
+                                                         or gio.is_video(args.sequence[ci])) else None,
+                                          decode=args.decode,
                                           flows="estimate" if args.make_flows else "files",
                                           depth_camera="estimate" if args.make_depth_camera else "files", focal=args.focal)
         else:

@@ -11,12 +11,17 @@ Mirrors ``gflow/utils/read.py`` and ``gflow/utils/conversion.py`` and the direct
     <seq>_epipolar/*_open.png        move mask                           (fit_video.py:96-97)
     <seq>_camera_mast3r_s2/*.json    {"focal", "pp", "pose"}              (read.py:72-89)
 
+A clip can also be ONE video file: a ``sequence_path`` that is a file ending in ``.avi`` (Motion-JPEG, as gflow_amd.video
+writes it) stands for the folder of its frames, named ``frame_00000``, ``frame_00001``, ...; the sibling folders are then
+``<path without .avi>_flow_unimatch`` and so on.  Its frames are decoded on the device (gflow_amd.video.read_avi_frames).
+
 ``Resize(n, antialias=True)`` of torchvision (shorter side to n, bilinear with antialiasing) is
 ``torch.nn.functional.interpolate(..., mode="bilinear", antialias=True)``; imageio / torchvision are
 not needed, PIL reads and writes the PNGs.
 """
 import json
 import os
+import warnings
 from pathlib import Path
 
 import numpy as np
@@ -143,10 +148,37 @@ def read_camera(camera_paths):
 
 
 # ----------------------------------------------------------------- sequence level
+class AviFrame:
+    """frame ``index`` of the Motion-JPEG AVI ``path``: what stands in a clip's image list where a file's path would"""
+
+    def __init__(self, path, index):
+        self.path, self.index = str(path), int(index)
+        self.name = f"frame_{self.index:05d}"
+
+    def __repr__(self):
+        return f"{self.path}:{self.name}"
+
+
+def is_video(sequence_path):
+    """is the sequence ONE video file (a file ending in .avi) instead of a folder of images?"""
+    sp = str(sequence_path)
+    return sp.lower().endswith(".avi") and os.path.isfile(sp)
+
+
+def _frame_name(ip):
+    return ip.name if isinstance(ip, AviFrame) else os.path.basename(ip).split(".")[0]
+
+
 def sequence_paths(sequence_path, frame_start=0, frame_range=-1, skip_interval=1):
-    """The file lists of fit_video.py:79-99, same globbing, slicing and ordering."""
+    """The file lists of fit_video.py:79-99, same globbing, slicing and ordering.  For a video file ``img`` lists its frames
+    (AviFrame) and the sibling folders hang on the path without its ``.avi``."""
     sp = str(sequence_path).rstrip("/")
-    img = sorted(Path(sp).glob("*.png")) + sorted(Path(sp).glob("*.jpg"))
+    if is_video(sp):
+        from .video import read_avi
+        img = [AviFrame(sp, i) for i in range(len(read_avi(sp)["frames"]))]
+        sp = sp[:-4]
+    else:
+        img = sorted(Path(sp).glob("*.png")) + sorted(Path(sp).glob("*.jpg"))
     if frame_range == -1:
         frame_range = len(img) - 1
     cut = lambda lst, n=frame_range: lst[frame_start:frame_start + n][::skip_interval]
@@ -164,7 +196,7 @@ def sequence_paths(sequence_path, frame_start=0, frame_range=-1, skip_interval=1
 
 def load_sequence(sequence_path, resize=None, frame_start=0, frame_range=-1, skip_interval=1, depth_offset=0.0,
                   move_masks="files", occ_masks="files", blur=False, device=None, flows="files", depth_camera="files",
-                  focal=None):
+                  focal=None, decode="host"):
     """Frames in the dict form ``gflow_amd.fit_video.fit_clip`` takes.  Frame i carries the flow
     i -> i+1 (fit_video.py:249: frame i+1 is fitted with flow_paths[i]) and the occlusion mask that
     fit_video.py:248 reads for it (img_occ_paths[i-1]).
@@ -193,7 +225,18 @@ def load_sequence(sequence_path, resize=None, frame_start=0, frame_range=-1, ski
     device the files are only decoded on the host: the raw arrays of one kind are stacked, uploaded once and prepared there
     (gflow_amd.prep.prep_frames), and the frames hold device tensors of the same shapes and dtypes (``extr`` stays on the
     host, ``occ_count`` is set from one read-back for the whole clip).  The device's resize is the same filter with exact
-    weights ("Frame preparation"): without ``resize`` and ``blur`` both paths give the same bits."""
+    weights ("Frame preparation"): without ``resize`` and ``blur`` both paths give the same bits.
+    ``decode``: "host" opens every image file with PIL; "device" (needs ``device``) decodes the JPEG files that
+    gflow_amd.video.parse_jpeg accepts in one gflow_amd.video.decode_jpeg call per shape -- the same bits, so the frames are
+    the same tensors -- and leaves PNGs and refused JPEGs to PIL, with one warning per clip that says how many.  A video
+    file's frames (``sequence_path`` a ``.avi`` file) are always decoded on the device: without ``device`` it raises."""
+    if decode not in ("host", "device"):
+        raise ValueError(f"load_sequence: decode must be \"host\" or \"device\", got {decode!r}")
+    if decode == "device" and device is None:
+        raise ValueError("load_sequence: decode=\"device\" needs device=")
+    if is_video(sequence_path) and device is None:
+        raise RuntimeError(f"gflow_amd.io: {sequence_path}: a video file is decoded on a HIP (cuda) device, pass device=; there "
+                           "is no CPU fallback")
     if occ_masks not in ("files", "flow"):
         raise ValueError(f"load_sequence: occ_masks must be \"files\" or \"flow\", got {occ_masks!r}")
     if move_masks not in ("files", "epipolar"):
@@ -207,7 +250,7 @@ def load_sequence(sequence_path, resize=None, frame_start=0, frame_range=-1, ski
     p = sequence_paths(sequence_path, frame_start, frame_range, skip_interval)
     n = len(p["img"])
     if flows == "estimate":
-        fwd, bwd = _estimated_flows(sequence_path, frame_start, frame_range, skip_interval, device)
+        fwd, bwd = _estimated_flows(sequence_path, frame_start, frame_range, skip_interval, device, decode)
     else:
         fwd, bwd = [_FloFile(f) for f in p["flow"]], [_FloFile(f) for f in p["flow_bwd"]]
     fwd, bwd = fwd[:n], bwd[:n]
@@ -220,7 +263,7 @@ def load_sequence(sequence_path, resize=None, frame_start=0, frame_range=-1, ski
         focal, pp, poses = read_camera(p["camera"])
     if device is not None:
         frames = _load_frames_device(p, fwd, bwd, focal, pp, poses, resize, depth_offset, move_masks, occ_masks, blur,
-                                     torch.device(device))
+                                     torch.device(device), decode)
     else:
         frames = _load_frames_host(p, fwd, bwd, focal, pp, poses, resize, depth_offset, move_masks, occ_masks, blur)
     if move_masks == "epipolar":
@@ -240,10 +283,10 @@ class _FloFile:
         return _read_flo(self.path) if self.array is None else self.array
 
 
-def _estimated_flows(sequence_path, frame_start, frame_range, skip_interval, device):
+def _estimated_flows(sequence_path, frame_start, frame_range, skip_interval, device, decode="host"):
     """(forward, backward) _FloFile lists as sequence_paths would list the files of a folder that holds the flows of EVERY
     pair of consecutive images (the one ``python -m gflow_amd.optflow`` writes): file k is the pair (image k, image k + 1)."""
-    from .optflow import pair_flows
+    from .optflow import clip_flows, pair_flows
     sp = str(sequence_path).rstrip("/")
     img = sequence_paths(sp, frame_range=1 << 30)["img"]
     if frame_range == -1:
@@ -251,7 +294,20 @@ def _estimated_flows(sequence_path, frame_start, frame_range, skip_interval, dev
     pairs = list(range(max(len(img) - 1, 0)))[frame_start:frame_start + frame_range][::skip_interval]
     if not pairs:
         return [], []
-    fwd, bwd = pair_flows(img, pairs, device=device)
+    if decode == "device" or is_video(sp):
+        # the decoded stack instead of paths: only the images the pairs touch (i and i + 1 stay neighbours in it)
+        used = sorted(set(pairs) | {i + 1 for i in pairs})
+        where = {i: j for j, i in enumerate(used)}
+        dev = torch.device(device)
+        arrays = [a if torch.is_tensor(a) else torch.from_numpy(np.array(a)).to(dev)
+                  for a, _ in _decode_images([img[i] for i in used], decode, dev)]
+        if len({(tuple(a.shape), a.dtype) for a in arrays}) != 1 or arrays[0].dtype != torch.uint8:
+            raise ValueError("load_sequence: flows=\"estimate\" from device-decoded images needs 8-bit images of one shape")
+        stack = torch.stack(arrays)
+        stack = stack.expand(-1, -1, -1, 3).contiguous() if stack.shape[-1] == 1 else stack
+        fwd, bwd = clip_flows(stack, pairs=[where[i] for i in pairs])
+    else:
+        fwd, bwd = pair_flows(img, pairs, device=device)
     fwd, bwd = fwd.cpu().numpy(), bwd.cpu().numpy()
     return ([_FloFile(array=np.ascontiguousarray(f)) for f in fwd], [_FloFile(array=np.ascontiguousarray(f)) for f in bwd])
 
@@ -307,7 +363,7 @@ def _estimated_depth_camera(p, fwd_src, bwd_src, n, move_masks, occ_masks, focal
 def _load_frames_host(p, flow_src, bwd_src, focal, pp, poses, resize, depth_offset, move_masks, occ_masks, blur):
     frames = []
     for i, ip in enumerate(p["img"]):
-        fr = dict(image=image_path_to_tensor(ip, resize, blur), focal=focal, pp=pp, name=os.path.basename(ip).split(".")[0])
+        fr = dict(image=image_path_to_tensor(ip, resize, blur), focal=focal, pp=pp, name=_frame_name(ip))
         fr["depth"] = read_depth(p["depth"][i], resize, depth_offset=depth_offset).unsqueeze(-1)
         H, W = fr["image"].shape[:2]
         from_file = move_masks == "files" and i < len(p["move"])
@@ -345,6 +401,43 @@ def _decode_image(path):
     return np.ascontiguousarray(img if img.dtype == np.uint8 else img.astype(np.float32)), div
 
 
+def _decode_images(paths, decode, device):
+    """[(array or device tensor (H, W, C <= 3), divisor)] of a clip's images, as _decode_image gives them.  A video file's
+    frames, and with decode="device" the JPEG files the device decoder takes, come from gflow_amd.video.decode_jpeg as
+    device tensors (one call per shape); every other file from PIL, with one warning that counts them."""
+    from .video import decode_jpeg, parse_jpeg, read_avi
+    out = [None] * len(paths)
+    groups, avi, on_host = {}, {}, 0
+    for i, ip in enumerate(paths):
+        if isinstance(ip, AviFrame):
+            if ip.path not in avi:
+                avi[ip.path] = read_avi(ip.path)["frames"]
+            data, name = avi[ip.path][ip.index], repr(ip)
+        elif decode == "device" and str(ip).lower().endswith((".jpg", ".jpeg")):
+            with open(ip, "rb") as f:
+                data, name = f.read(), str(ip)
+        else:
+            data = None
+        if data is not None:
+            try:
+                p = parse_jpeg(data, name)
+                groups.setdefault((p["width"], p["height"], p["components"], p["hs"], p["vs"]), []).append((i, data, name))
+                continue
+            except ValueError:
+                if isinstance(ip, AviFrame):
+                    raise
+        out[i] = _decode_image(ip)
+        on_host += decode == "device"
+    for members in groups.values():
+        stack = decode_jpeg([d for _, d, _ in members], device, names=[n for _, _, n in members])
+        for j, (i, _, _) in enumerate(members):
+            out[i] = (stack[j], 255.0)
+    if on_host:
+        warnings.warn(f"load_sequence(decode=\"device\"): {on_host} of {len(paths)} images were decoded on the host (PNG files, "
+                      "or JPEG files outside the device decoder's scope)")
+    return out
+
+
 def _decode_mask(path):
     """(H, W, C) uint8 or float32 as read_mask reads the file"""
     from PIL import Image
@@ -364,20 +457,26 @@ def _prep_stacks(arrays, device, resize, keys=None, **kw):
     groups = {}
     for i, a in enumerate(arrays):
         if a is not None:
-            groups.setdefault((a.shape, a.dtype.str, None if keys is None else keys[i]), []).append(i)
+            kind = "|u1" if a.dtype == torch.uint8 else str(a.dtype) if torch.is_tensor(a) else a.dtype.str
+            groups.setdefault((tuple(a.shape), kind, None if keys is None else keys[i]), []).append(i)
     for (_, _, key), idx in groups.items():
-        stack = torch.from_numpy(np.stack([arrays[i] for i in idx])).to(device)
+        if any(torch.is_tensor(arrays[i]) for i in idx):       # (decoded on the device: already there)
+            stack = torch.stack([arrays[i] if torch.is_tensor(arrays[i]) else torch.from_numpy(np.array(arrays[i])).to(device)
+                                 for i in idx])
+        else:
+            stack = torch.from_numpy(np.stack([arrays[i] for i in idx])).to(device)
         res = prep_frames(stack, resize, **(kw if key is None else dict(kw, div=key)))
         for j, i in enumerate(idx):
             out[i] = res[j]
     return out
 
 
-def _load_frames_device(p, flow_src, bwd_src, focal, pp, poses, resize, depth_offset, move_masks, occ_masks, blur, device):
+def _load_frames_device(p, flow_src, bwd_src, focal, pp, poses, resize, depth_offset, move_masks, occ_masks, blur, device,
+                        decode="host"):
     if device.type != "cuda":
         raise RuntimeError("gflow_amd.io: load_sequence(device=...) needs a HIP (cuda) device; there is no CPU fallback")
     n = len(p["img"])
-    images = [_decode_image(ip) for ip in p["img"]]
+    images = _decode_images(p["img"], decode, device)
     image = _prep_stacks([a for a, _ in images], device, resize, keys=[d for _, d in images], blur=blur)
     depth = _prep_stacks([np.asarray(_depth_array(p["depth"][i]), dtype=np.float32)[..., None] for i in range(n)], device, resize,
                          mul=1.0, add=depth_offset)
@@ -405,7 +504,7 @@ def _load_frames_device(p, flow_src, bwd_src, focal, pp, poses, resize, depth_of
                 occ[i + 1] = masks[j]
     frames = []
     for i, ip in enumerate(p["img"]):
-        fr = dict(image=image[i], focal=focal, pp=pp, name=os.path.basename(ip).split(".")[0], depth=depth[i])
+        fr = dict(image=image[i], focal=focal, pp=pp, name=_frame_name(ip), depth=depth[i])
         H, W = fr["image"].shape[:2]
         fr["move_mask"] = move[i] if move[i] is not None else torch.zeros(H, W, dtype=torch.bool, device=device)
         if i < len(flow_src):

@@ -13,9 +13,21 @@ out in include/gflow_hip.h, "video files") turn a whole stack into the entropy-c
 
     python -m gflow_amd.video --frames DIR --out FILE.avi [--fps 5] [--quality 90] [--gpu 0]
 
-The AVI writer and reader and ``jpeg_header`` need no device; ``encode_jpeg`` has no CPU path.
+The way back ("Decoding video files") is gfl_jpeg_decode (csrc/gfl_jpeg_dec.hip over csrc/gfl_jpeg_dec.hpp): the
+host parses the headers and finds the restart intervals (``parse_jpeg``: pure Python and numpy), the device decodes a whole
+stack, with the bits ``PIL.Image.open`` gives for the same files:
+
+    parse_jpeg(data)                                  # dict: size, sampling, tables, DRI, the scan's bytes, the units
+    images = decode_jpeg(files)                       # list of .jpg files as bytes -> (T, H, W, C) uint8 on the device
+    images = read_avi_frames("clip.avi")              # read_avi + decode_jpeg, in stacks of `chunk` frames
+
+    python -m gflow_amd.video --unpack FILE.avi --out DIR [--gpu 0]        # the frames as PNG files
+
+The AVI writer and reader, ``jpeg_header`` and ``parse_jpeg`` need no device; ``encode_jpeg`` and ``decode_jpeg`` have no CPU
+path.
 """
 import argparse
+import ctypes
 import os
 import struct
 
@@ -142,6 +154,271 @@ def encode_jpeg(images, quality=90):
     head = jpeg_header(W, H, C, quality)
     data, off = encode_scans(images, quality)
     return [head + data[off[t]:off[t + 1]].tobytes() + EOI for t in range(T)]
+
+
+# ------------------------------------------------------------------------------------------------------------- decoding
+# the mirrors of gfl_jpeg_unit and gfl_jpeg_frame_tables (include/gflow_hip.h states the layout; _check_mirrors the sizes)
+UNIT_DTYPE = np.dtype([("frame", "<i4"), ("first_mcu", "<i4"), ("n_mcu", "<i4"), ("n_bytes", "<i4"), ("offset", "<i8")])
+TABLES_DTYPE = np.dtype([("q", "u1", (4, 64)), ("qsel", "u1", 4), ("dcsel", "u1", 4), ("acsel", "u1", 4), ("first_unit", "<i4"),
+                         ("n_units", "<i4"), ("huff", [("bits", "u1", 16), ("vals", "u1", 256)], 4)])
+UNIT_STATUS = {1: "the unit record is out of range", 2: "a code that matches no Huffman code", 3: "a coefficient index past 63",
+               4: "the data ended early", 5: "data left behind the last MCU", 6: "a symbol out of range", -1: "never run"}
+_SOF_NAMES = {0xC1: "extended sequential coding", 0xC2: "progressive coding", 0xC3: "lossless coding"}
+_mirrors_checked = False
+
+
+def _check_mirrors(lib):
+    global _mirrors_checked
+    if not _mirrors_checked:
+        a, b = ctypes.c_int(), ctypes.c_int()
+        L.check(lib.gfl_jpeg_decode_struct_bytes(ctypes.byref(a), ctypes.byref(b)), "jpeg decode struct sizes")
+        if (a.value, b.value) != (UNIT_DTYPE.itemsize, TABLES_DTYPE.itemsize):
+            raise RuntimeError(f"gflow_amd.video: the library's gfl_jpeg_unit / gfl_jpeg_frame_tables are {a.value} / {b.value} "
+                               f"bytes, the binding's {UNIT_DTYPE.itemsize} / {TABLES_DTYPE.itemsize}: rebuild the library")
+        _mirrors_checked = True
+
+
+def parse_jpeg(data, name="JPEG data"):
+    """The headers of one baseline JPEG file (``data``: bytes) and where its entropy-coded data lies; no device, nothing is
+    decoded.  Returns dict(width, height, components, hs, vs -- the luminance sampling; sampling, component_ids, qsel, dcsel,
+    acsel -- per component; quant -- {id: (64,) uint8, natural order}; huffman -- {(class, id): (BITS[16], HUFFVAL)}; dri;
+    jfif, adobe_transform; scan -- (start, end) of the entropy-coded bytes in ``data``; mcus -- (per row, per column);
+    units -- (n, 4) int64 rows (first MCU, MCU count, byte offset in ``data``, byte count), one per restart interval).
+    Raises ValueError, naming ``name``, for everything gfl_jpeg_decode does not take: anything but SOF0 with 8-bit samples and
+    8-bit quantisers, one interleaved scan of 1 component or of 3 that libjpeg reads as YCbCr with chroma 1x1 and luminance
+    1x1, 2x1 or 2x2 -- and for restart markers that do not count 0 .. 7 in order."""
+    def refuse(why):
+        raise ValueError(f"gflow_amd.video: {name}: {why}")
+
+    data = bytes(data)
+    n = len(data)
+    if n < 4 or data[:2] != b"\xff\xd8":
+        refuse("not a JPEG file (no SOI)")
+    pos, quant, huff, dri, sof, jfif, adobe, sos = 2, {}, {}, 0, None, False, None, None
+    while sos is None:
+        if pos + 2 > n:
+            refuse("no scan (the file ends inside its headers)")
+        if data[pos] != 0xFF:
+            refuse(f"byte {pos} is not a marker")
+        while pos < n and data[pos] == 0xFF:                   # (fill bytes may precede a marker)
+            pos += 1
+        if pos >= n:
+            refuse("no scan (the file ends inside its headers)")
+        m = data[pos]
+        pos += 1
+        if m == 0x01 or 0xD0 <= m <= 0xD7:
+            continue
+        if m == 0xD9:
+            refuse("no scan (EOI after the headers)")
+        if pos + 2 > n:
+            refuse("no scan (the file ends inside its headers)")
+        length = struct.unpack_from(">H", data, pos)[0]
+        if length < 2 or pos + length > n:
+            refuse(f"the segment of marker FF{m:02X} runs past the end of the file")
+        seg = data[pos + 2:pos + length]
+        pos += length
+        if m == 0xC0:
+            if sof is not None:
+                refuse("two frame headers")
+            if len(seg) < 6 or len(seg) != 6 + 3 * seg[5]:
+                refuse("a frame header of the wrong length")
+            P, H, W, nf = seg[0], *struct.unpack_from(">HH", seg, 1), seg[5]
+            if P != 8:
+                refuse(f"{P}-bit samples (8-bit only)")
+            if nf not in (1, 3):
+                refuse(f"{nf} components (1 or 3 only)")
+            if W < 1 or H < 1:
+                refuse(f"a frame of {W}x{H} (the height in a DNL segment is not supported)")
+            sof = dict(W=W, H=H, comps=[(seg[6 + 3 * c], seg[7 + 3 * c] >> 4, seg[7 + 3 * c] & 15, seg[8 + 3 * c]) for c in range(nf)])
+        elif 0xC1 <= m <= 0xCF and m not in (0xC4, 0xC8):
+            refuse("arithmetic coding" if m >= 0xC9 else _SOF_NAMES.get(m, f"differential coding (SOF{m - 0xC0})") + " (baseline SOF0 only)")
+        elif m == 0xDB:
+            at = 0
+            while at < len(seg):
+                pq, tq = seg[at] >> 4, seg[at] & 15
+                if pq != 0:
+                    refuse("a 16-bit quantisation table (8-bit only)")
+                if tq > 3 or at + 65 > len(seg):
+                    refuse("a malformed DQT segment")
+                nat = np.zeros(64, dtype=np.uint8)
+                nat[list(ZIGZAG)] = np.frombuffer(seg, dtype=np.uint8, count=64, offset=at + 1)
+                quant[tq] = nat
+                at += 65
+        elif m == 0xC4:
+            at = 0
+            while at < len(seg):
+                tc, th = seg[at] >> 4, seg[at] & 15
+                if tc > 1 or th > 1 or at + 17 > len(seg):
+                    refuse("a Huffman table with class or id above 1, or a malformed DHT segment (baseline: ids 0 and 1)")
+                bits = tuple(seg[at + 1:at + 17])
+                if sum(bits) > 256 or at + 17 + sum(bits) > len(seg):
+                    refuse("a malformed DHT segment")
+                huff[(tc, th)] = (bits, bytes(seg[at + 17:at + 17 + sum(bits)]))
+                at += 17 + sum(bits)
+        elif m == 0xDD:
+            if len(seg) != 2:
+                refuse("a malformed DRI segment")
+            dri = struct.unpack(">H", seg)[0]
+        elif m == 0xE0 and seg[:5] == b"JFIF\0":
+            jfif = True
+        elif m == 0xEE and seg[:5] == b"Adobe" and len(seg) >= 12:
+            adobe = seg[11]
+        elif m == 0xDA:
+            if sof is None:
+                refuse("a scan before the frame header")
+            sos = seg
+    comps = sof["comps"]
+    C, W, H = len(comps), sof["W"], sof["H"]
+    if len(sos) < 1 or len(sos) != 4 + 2 * sos[0]:
+        refuse("a scan header of the wrong length")
+    if sos[0] != C:
+        refuse(f"a scan of {sos[0]} of the {C} components (several scans; one interleaved scan only)")
+    if [sos[1 + 2 * c] for c in range(C)] != [cid for cid, _, _, _ in comps]:
+        refuse("the scan lists the components in another order than the frame")
+    if tuple(sos[1 + 2 * C:]) != (0, 63, 0):
+        refuse("a scan that is not the whole spectrum at full precision (progressive parameters)")
+    dcsel, acsel = [sos[2 + 2 * c] >> 4 for c in range(C)], [sos[2 + 2 * c] & 15 for c in range(C)]
+    sampling = [(h, v) for _, h, v, _ in comps]
+    if C == 1 and sampling[0] != (1, 1):
+        refuse(f"a single component sampled {sampling[0][0]}x{sampling[0][1]} (1x1 only)")
+    if C == 3 and (sampling[1] != (1, 1) or sampling[2] != (1, 1) or sampling[0] not in ((1, 1), (2, 1), (2, 2))):
+        refuse("sampling factors " + ", ".join(f"{h}x{v}" for h, v in sampling) + " (chroma 1x1 with luminance 1x1, 2x1 or 2x2 only)")
+    if C == 3:
+        if adobe is not None and adobe != 1:
+            refuse(f"an Adobe APP14 marker with transform {adobe}: not YCbCr")
+        if adobe is None and not jfif and bytes(cid for cid, _, _, _ in comps) == b"RGB":
+            refuse("components R, G, B without JFIF: libjpeg reads them as RGB, not YCbCr")
+    for c, (_, _, _, tq) in enumerate(comps):
+        if tq not in quant or dcsel[c] > 1 or acsel[c] > 1 or (0, dcsel[c]) not in huff or (1, acsel[c]) not in huff:
+            refuse(f"component {c} uses a table the file does not define")
+    hs, vs = sampling[0]
+    mx, my = -(-W // (8 * hs)), -(-H // (8 * vs))
+    # the scan: up to the first marker that is neither a stuffed FF nor RSTm -- EOI in a whole file
+    a = np.frombuffer(data, dtype=np.uint8)[pos:]
+    ff = np.flatnonzero(a[:-1] == 0xFF) if a.size > 1 else np.zeros(0, dtype=np.int64)
+    nxt = a[ff + 1]
+    is_rst = (nxt >= 0xD0) & (nxt <= 0xD7)
+    other = ff[(nxt != 0) & ~is_rst]
+    end = int(other[0]) if other.size else int(a.size)
+    if other.size and a[end + 1] != 0xD9:
+        refuse("fill bytes inside the scan" if a[end + 1] == 0xFF else
+               f"marker FF{a[end + 1]:02X} after the scan (several scans or tables between them)")
+    rst = ff[is_rst]
+    rst = rst[rst < end]
+    n_mcu = mx * my
+    if dri == 0:
+        if rst.size:
+            refuse("restart markers in a file without DRI")
+        units = np.array([[0, n_mcu, pos, end]], dtype=np.int64)
+    else:
+        n_int = -(-n_mcu // dri)
+        if rst.size > n_int - 1:
+            refuse(f"{rst.size} restart markers for {n_int} restart intervals")
+        if not np.array_equal(a[rst + 1].astype(np.int64) - 0xD0, np.arange(rst.size) & 7):
+            refuse("restart markers that do not count 0 .. 7 in order")
+        starts = np.full(n_int, end, dtype=np.int64)           # (a scan that ends early: the intervals behind are empty)
+        ends = np.full(n_int, end, dtype=np.int64)
+        starts[0] = 0
+        starts[1:rst.size + 1] = rst + 2
+        ends[:rst.size] = rst
+        first = np.arange(n_int, dtype=np.int64) * dri
+        units = np.stack([first, np.minimum(dri, n_mcu - first), pos + starts, ends - starts], axis=1)
+    return dict(width=W, height=H, components=C, hs=hs, vs=vs, sampling=sampling, component_ids=[c[0] for c in comps],
+                qsel=[c[3] for c in comps], dcsel=dcsel, acsel=acsel, quant=quant, huffman=huff, dri=dri, jfif=jfif,
+                adobe_transform=adobe, scan=(pos, pos + end), mcus=(mx, my), units=units)
+
+
+def decode_arrays(files, parsed):
+    """What gfl_jpeg_decode takes, on the host, from ``files`` (bytes each) and their ``parse_jpeg`` results (one shape):
+    (units -- UNIT_DTYPE, tables -- TABLES_DTYPE [T], bytes -- every frame's scan, concatenated, uint8)."""
+    T = len(files)
+    tables = np.zeros(T, dtype=TABLES_DTYPE)
+    units, scans, at = [], [], 0
+    for t, (data, p) in enumerate(zip(files, parsed)):
+        ft = tables[t]
+        for i, q in p["quant"].items():
+            ft["q"][i] = q
+        C = p["components"]
+        ft["qsel"][:C], ft["dcsel"][:C], ft["acsel"][:C] = p["qsel"], p["dcsel"], p["acsel"]
+        for (cls, i), (bits, vals) in p["huffman"].items():
+            ft["huff"][2 * cls + i]["bits"] = bits
+            ft["huff"][2 * cls + i]["vals"][:len(vals)] = np.frombuffer(vals, dtype=np.uint8)
+        u = np.zeros(len(p["units"]), dtype=UNIT_DTYPE)
+        u["frame"], u["first_mcu"], u["n_mcu"], u["n_bytes"] = t, p["units"][:, 0], p["units"][:, 1], p["units"][:, 3]
+        u["offset"] = p["units"][:, 2] - p["scan"][0] + at
+        ft["first_unit"], ft["n_units"] = sum(len(x) for x in units), len(u)
+        units.append(u)
+        scans.append(np.frombuffer(data, dtype=np.uint8)[p["scan"][0]:p["scan"][1]])
+        at += p["scan"][1] - p["scan"][0]
+    return np.concatenate(units), tables, np.concatenate(scans) if scans else np.zeros(0, dtype=np.uint8)
+
+
+def decode_jpeg(files, device=None, names=None):
+    """``files`` -- a list of complete baseline JPEG files as bytes, all of one size, component count and sampling (their
+    tables and restart intervals may differ) -- as a (T, H, W, C) uint8 stack on ``device`` (default: the current HIP device;
+    without one this raises: there is no CPU path).  C = 3: RGB; C = 1: grey.  The bits are those of
+    ``np.asarray(PIL.Image.open(file))``.  One upload, one library call, one read-back of the units' status: a unit that
+    went wrong raises ValueError naming its frame (``names[t]`` if given) and unit.  Raises ValueError too for a file
+    ``parse_jpeg`` refuses."""
+    files = [bytes(f) for f in files]
+    T = len(files)
+    if device is None and torch.cuda.is_available():
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = torch.device("cpu" if device is None else device)
+    if device.type != "cuda" or not torch.cuda.is_available():
+        raise RuntimeError("gflow_amd.video: decode_jpeg needs a HIP (cuda) device; there is no CPU fallback")
+    if T == 0:
+        return torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=device)
+    label = lambda t: f"frame {t}" + (f" ({names[t]})" if names is not None else "")
+    parsed = [parse_jpeg(f, label(t)) for t, f in enumerate(files)]
+    key = lambda p: (p["width"], p["height"], p["components"], p["hs"], p["vs"])
+    for t, p in enumerate(parsed):
+        if key(p) != key(parsed[0]):
+            raise ValueError(f"gflow_amd.video: {label(t)} is {key(p)} (width, height, components, sampling), {label(0)} is "
+                             f"{key(parsed[0])}: one call decodes one shape")
+    W, H, C, hs, vs = key(parsed[0])
+    units, tables, data = decode_arrays(files, parsed)
+    images, st = decode_stack(units, tables, data, W, H, C, hs, vs, device)
+    bad = np.flatnonzero(st)
+    if bad.size:
+        u = int(bad[0])
+        t = int(units["frame"][u])
+        raise ValueError(f"gflow_amd.video: {label(t)}, unit {u - int(tables['first_unit'][t])} of {int(tables['n_units'][t])}: "
+                         f"{UNIT_STATUS.get(int(st[u]), f'status {int(st[u])}')} ({bad.size} of {len(units)} units of the call "
+                         "went wrong)")
+    return images
+
+
+def decode_stack(units, tables, data, W, H, C, hs, vs, device):
+    """gfl_jpeg_decode on host arrays (``decode_arrays``): ((T, H, W, C) uint8 on ``device``, the units' status as a host
+    int32 array).  One upload, one call, one read-back; nothing is raised for a unit that went wrong."""
+    device = torch.device(device)
+    if device.type != "cuda" or not torch.cuda.is_available():
+        raise RuntimeError("gflow_amd.video: decode_stack needs a HIP (cuda) device; there is no CPU fallback")
+    T = len(tables)
+    units, tables = np.ascontiguousarray(units, dtype=UNIT_DTYPE), np.ascontiguousarray(tables, dtype=TABLES_DTYPE)
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    lib = L.load()
+    _check_mirrors(lib)
+    need = lib.gfl_jpeg_decode_workspace_bytes(T, C, W, H, hs, vs, len(units))
+    if need == 0:
+        raise ValueError(f"gflow_amd.video: unsupported stack T={T} H={H} W={W} C={C} sampling {hs}x{vs}")
+    # ONE upload: the units, the tables and the bytes behind each other, each on a 16-byte boundary
+    parts = [units.view(np.uint8).reshape(-1), tables.view(np.uint8).reshape(-1), data]
+    offs = np.cumsum([0] + [(len(x) + 15) // 16 * 16 for x in parts])
+    host = np.zeros(int(offs[-1]) + 16, dtype=np.uint8)
+    for o, x in zip(offs, parts):
+        host[o:o + len(x)] = x
+    with torch.cuda.device(device):
+        blob = torch.from_numpy(host).to(device)
+        images = torch.empty((T, H, W, C), dtype=torch.uint8, device=device)
+        status = torch.empty(len(units), dtype=torch.int32, device=device)
+        ws = L.scratch(need, device)
+        at = lambda i: ctypes.c_void_p(blob.data_ptr() + int(offs[i]))
+        L.check(lib.gfl_jpeg_decode(at(2), len(data), at(0), len(units), at(1), T, C, W, H, hs, vs, L.ptr(images), L.ptr(status),
+                                    L.ptr(ws), ws.numel(), L.stream()), "jpeg decode")
+        st = status.cpu().numpy()
+    return images, st
 
 
 # ---------------------------------------------------------------------------------------------------------- the container
@@ -289,15 +566,44 @@ def read_avi(path):
                 stream_length=strh[9])
 
 
+def read_avi_frames(path, device=None, chunk=64, select=None):
+    """The frames of a Motion-JPEG AVI as a (T, H, W, C) uint8 stack on the device: ``read_avi``, then ``decode_jpeg`` in
+    stacks of ``chunk`` frames.  ``select``: the indices of the frames to decode (default: all, in order)."""
+    frames = read_avi(path)["frames"]
+    idx = list(range(len(frames))) if select is None else [int(i) for i in select]
+    chunk = max(int(chunk), 1)
+    stacks = [decode_jpeg([frames[i] for i in idx[a:a + chunk]], device, names=[f"{path}, frame {i}" for i in idx[a:a + chunk]])
+              for a in range(0, len(idx), chunk)]
+    return torch.cat(stacks) if stacks else decode_jpeg([], device)
+
+
+def _unpack(path, out, chunk=64):
+    from PIL import Image
+    os.makedirs(out, exist_ok=True)
+    frames = read_avi(path)["frames"]
+    for a in range(0, len(frames), chunk):
+        stack = decode_jpeg(frames[a:a + chunk], names=[f"{path}, frame {i}" for i in range(a, min(a + chunk, len(frames)))])
+        for i, img in enumerate(stack.cpu().numpy()):
+            Image.fromarray(img[..., 0] if img.shape[-1] == 1 else img).save(os.path.join(out, f"frame_{a + i:05d}.png"))
+    print(f"{len(frames)} frames of {path} -> {out}")
+    return 0
+
+
 def main(argv=None):
     from PIL import Image
-    ap = argparse.ArgumentParser(description="a folder of images as a Motion-JPEG AVI, coded on the device")
-    ap.add_argument("--frames", required=True, help="directory of image files (taken in sorted order, one shape)")
-    ap.add_argument("--out", required=True, help="the .avi file")
+    ap = argparse.ArgumentParser(description="a folder of images as a Motion-JPEG AVI, coded on the device (--frames), or "
+                                 "the frames of such a file, decoded on the device, as PNG files (--unpack)")
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("--frames", help="directory of image files (taken in sorted order, one shape)")
+    src.add_argument("--unpack", metavar="FILE.avi", help="a Motion-JPEG AVI whose frames go to --out as frame_00000.png, ...")
+    ap.add_argument("--out", required=True, help="the .avi file (--frames) or the directory of PNG files (--unpack)")
     ap.add_argument("--fps", type=float, default=5)
     ap.add_argument("--quality", type=int, default=90)
     ap.add_argument("--gpu", type=int, default=0)
     args = ap.parse_args(argv)
+    if args.unpack:
+        torch.cuda.set_device(args.gpu)
+        return _unpack(args.unpack, args.out)
     names = sorted(n for n in os.listdir(args.frames) if n.lower().endswith((".png", ".jpg", ".jpeg", ".bmp")))
     if not names:
         raise ValueError(f"{args.frames}: no image files")

@@ -882,6 +882,53 @@ int gfl_jpeg_sizes(const uint8_t* images, int T, int C, int W, int H, const uint
 int gfl_jpeg_emit(const uint8_t* images, int T, int C, int W, int H, const uint16_t* qtables, uint8_t* out, int64_t out_bytes,
                   void* workspace, size_t workspace_bytes, gfl_stream_t stream);
 
+/* Decoding (additive within 312; gflow_amd.video.decode_jpeg, INTEGRATION.md "Decoding video files"; the arithmetic lives
+ * in csrc/gfl_jpeg_dec.hpp, which a host compiler takes too: tools/jpeg_dec_host.cpp).  T baseline sequential JPEG images
+ * (SOF0, 8 bits, one interleaved scan) of ONE shape, component count and sampling -> images [T][H][W][C] uint8, with the
+ * bits libjpeg's default path gives (slow-integer IDCT, fancy upsampling, 16-bit fixed-point YCbCr -> RGB).
+ *   C = 1: one grey component, hs = vs = 1.  C = 3: Y sampled hs x vs = 1x1, 2x1 or 2x2 (4:4:4, 4:2:2, 4:2:0), Cb and Cr
+ *   1x1; an MCU is the hs * vs blocks of Y row by row, then Cb, then Cr, and covers 8 hs x 8 vs pixels; MCUs run row by row.
+ * The host parses the files.  It passes every frame's entropy-coded data (markers removed, FF 00 stuffing left in) in
+ * `bytes`, and cuts it into UNITS: a unit is one restart interval of one frame (a file without DRI is one unit), a
+ * byte-aligned bit stream whose DC predictors start at 0.
+ *   gfl_jpeg_unit, 24 bytes: frame; first_mcu, n_mcu: the MCUs it codes, in scan order of its frame; n_bytes, offset: its
+ *     data is bytes[offset, offset + n_bytes).
+ *   gfl_jpeg_frame_tables, 1364 bytes, one per frame: q[i]: quantiser table i, 64 entries in NATURAL (row-major) order;
+ *     qsel / dcsel / acsel[c]: the table ids of component c (< 4, < 2, < 2); first_unit, n_units: the frame's units are
+ *     units[first_unit, first_unit + n_units); huff[0], [1]: the DC tables 0 and 1, huff[2], [3]: the AC tables, each as
+ *     the BITS and HUFFVAL lists of a DHT segment (unused entries 0).
+ * Two stages.  Entropy: a lane per unit, the frame's Huffman tables (T.81 F.2.2.3: maxcode / valptr) in LDS, quantised
+ * coefficients as int16 into the workspace (zeroed first).  Pixels: coef * q, the two-pass 13-bit LL&M inverse DCT (DESCALE
+ * by 11, then by 18), + 128, clamp; then triangle upsampling of the cropped chroma planes and the colour transform.
+ * Malformed data never becomes a bad address: a reader never looks past its unit's bytes (behind them it supplies 1-bits),
+ * every coefficient index is checked, and a unit that goes wrong stops and says so in unit_status [n_units] int32:
+ *   0 fine; 1 the unit record is out of range (nothing decoded); 2 a code that matches no Huffman code; 3 a coefficient
+ *   index past 63; 4 the data ended early; 5 data left behind the last MCU; 6 a symbol out of range; -1 never run (no frame
+ *   lists the unit).  A block is stored only once it is decoded whole: the blocks behind stay zero.
+ * GFL_ERR_INVALID, before any launch: a NULL pointer, T or n_units < 1, n_bytes < 0, C / hs / vs not as above, W or H
+ *   outside 1 .. 65535, more than 2^30 blocks, a workspace that is not 16-byte aligned.  GFL_ERR_WORKSPACE: workspace_bytes <
+ *   gfl_jpeg_decode_workspace_bytes (0 for arguments it rejects; needs no device).  No allocation, no host synchronisation.
+ * gfl_jpeg_decode_struct_bytes: sizeof of the two structs, for a binding to check its mirror against. */
+typedef struct gfl_jpeg_unit {
+    int32_t frame, first_mcu, n_mcu, n_bytes;
+    int64_t offset;
+} gfl_jpeg_unit;
+typedef struct gfl_jpeg_huff_spec {
+    uint8_t bits[16];
+    uint8_t vals[256];
+} gfl_jpeg_huff_spec;
+typedef struct gfl_jpeg_frame_tables {
+    uint8_t q[4][64];
+    uint8_t qsel[4], dcsel[4], acsel[4];
+    int32_t first_unit, n_units;
+    gfl_jpeg_huff_spec huff[4];
+} gfl_jpeg_frame_tables;
+size_t gfl_jpeg_decode_workspace_bytes(int T, int C, int W, int H, int hs, int vs, int64_t n_units);
+int gfl_jpeg_decode(const uint8_t* bytes, int64_t n_bytes, const gfl_jpeg_unit* units, int64_t n_units,
+                    const gfl_jpeg_frame_tables* tables, int T, int C, int W, int H, int hs, int vs, uint8_t* images,
+                    int32_t* unit_status, void* workspace, size_t workspace_bytes, gfl_stream_t stream);
+int gfl_jpeg_decode_struct_bytes(int* sizeof_unit, int* sizeof_frame_tables);
+
 /* ---- optical flow (additive within 312; gflow_amd/optflow.py, INTEGRATION.md "Flows from the images") --------------------
  * The flow a -> b on a's grid, in pixels, of P pairs of images: a classical coarse-to-fine variational estimate (robust data
  * term on the grey value, robust isotropic smoothness), NOT a learned one.  All arithmetic is float32 in the order written,
