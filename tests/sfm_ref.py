@@ -29,8 +29,9 @@ def points(flow):
     return x1, y1, x1 + f[..., 0], y1 + f[..., 1], known
 
 
-def fit8(x1, y1, x2, y2):
-    """the Hartley-normalised 8-point fit of the given correspondences (1-D arrays)"""
+def fit8(x1, y1, x2, y2, perturb=None):
+    """the Hartley-normalised 8-point fit of the given correspondences (1-D arrays); ``perturb`` maps the normalised A^T A to
+    the matrix whose null vector is taken (the sensitivity probe)"""
     def hartley(x, y):
         cx, cy = x.mean(), y.mean()
         s = np.sqrt(2.0) / np.sqrt((x - cx) ** 2 + (y - cy) ** 2).mean()
@@ -38,7 +39,8 @@ def fit8(x1, y1, x2, y2):
     u1, v1, T1 = hartley(x1, y1)
     u2, v2, T2 = hartley(x2, y2)
     A = np.stack([u2 * u1, u2 * v1, u2, v2 * u1, v2 * v1, v2, u1, v1, np.ones_like(u1)], axis=1)
-    _, vecs = np.linalg.eigh(A.T @ A)
+    M = A.T @ A
+    _, vecs = np.linalg.eigh(M if perturb is None else perturb(M))
     f = vecs[:, 0].reshape(3, 3)
     U, S, Vt = np.linalg.svd(f)
     f = U @ np.diag([S[0], S[1], 0.0]) @ Vt
@@ -68,8 +70,17 @@ def initial_F(flow, exclude=None, hypotheses=64, seed=0):
 
 
 # ------------------------------------------------------------------------------------------------------- a. the refit
-def refit(flow, F_init, exclude=None, rounds=2, e_floor=E_FLOOR):
-    """dict(F (3, 3), counts (usable, inliers), median, inlier (H, W) uint8, err (H, W) with NaN where not usable, thr)"""
+def _margin(e, thr):
+    """the smallest relative distance of a usable pixel's error e from the inlier threshold thr"""
+    e = e[np.isfinite(e)]
+    if e.size == 0 or not thr > 0:
+        return float("inf")
+    return float(np.abs(e - thr).min() / thr)
+
+
+def refit(flow, F_init, exclude=None, rounds=2, e_floor=E_FLOOR, perturb=None):
+    """dict(F (3, 3), counts (usable, inliers), median, inlier (H, W) uint8, err (H, W) with NaN where not usable, thr, margins
+    [rounds + 1]: the threshold margin of every round's inlier decision, the final F's last)"""
     x1, y1, x2, y2, known = points(flow)
     use = known if exclude is None else known & (np.asarray(exclude) == 0)
     F = np.asarray(F_init, dtype=np.float64).reshape(3, 3).copy()
@@ -82,27 +93,28 @@ def refit(flow, F_init, exclude=None, rounds=2, e_floor=E_FLOOR):
         med, n = lower_median(e)
         return e, med, n, (max(K2 * med, e_floor) if n else -1.0)
 
+    margins = []
     for _ in range(rounds):
         e, med, n, thr = evaluate(F)
+        margins.append(_margin(e, thr))
         with np.errstate(invalid="ignore"):
             inl = e <= thr
         if inl.sum() >= 8:
             with np.errstate(all="ignore"):
-                Fn = fit8(x1[inl], y1[inl], x2[inl], y2[inl])
+                Fn = fit8(x1[inl], y1[inl], x2[inl], y2[inl], perturb)
             if np.isfinite(Fn).all():
                 F = Fn
     e, med, n, thr = evaluate(F)
+    margins.append(_margin(e, thr))
     with np.errstate(invalid="ignore"):
         inl = e <= thr
-    return dict(F=F, counts=(n, int(inl.sum())), median=med, inlier=inl.astype(np.uint8), err=e, thr=thr)
+    return dict(F=F, counts=(n, int(inl.sum())), median=med, inlier=inl.astype(np.uint8), err=e, thr=thr, margins=margins)
 
 
 def threshold_margin(res):
-    """the smallest relative distance of a usable pixel's error from the inlier threshold"""
-    e = res["err"][np.isfinite(res["err"])]
-    if e.size == 0 or not res["thr"] > 0:
-        return float("inf")
-    return float(np.abs(e - res["thr"]).min() / res["thr"])
+    """the smallest relative distance of a usable pixel's error from the inlier threshold, over every round of the refit: an
+    inlier that flips in an intermediate round moves F at the 1e-4 level"""
+    return min(res["margins"])
 
 
 # --------------------------------------------------------------------------------------------------------- b. the pose
@@ -191,12 +203,63 @@ def triangulate(flow, inlier, R, t, degenerate, intr):
     return rho, w
 
 
-def two_view(flow, intr, F_init, exclude=None, rounds=2, e_floor=E_FLOOR, min_parallax=0.1, min_share=0.2):
+def two_view(flow, intr, F_init, exclude=None, rounds=2, e_floor=E_FLOOR, min_parallax=0.1, min_share=0.2, perturb=None):
     """stages a - c of one pair"""
-    fit = refit(flow, F_init, exclude, rounds, e_floor)
+    fit = refit(flow, F_init, exclude, rounds, e_floor, perturb)
     ps = pose(flow, fit["F"], fit["inlier"], fit["counts"], intr, min_parallax, min_share)
     rho, w = triangulate(flow, fit["inlier"], ps["R"], ps["t"], ps["degenerate"], intr)
     return dict(fit, **ps, rho=rho, weight=w)
+
+
+def cheirality(flow, tv, intr):
+    """what the exact comparison of a pair's votes and weights rests on -- dict(margin, sin2, sin2_any (H, W), NaN off the
+    inliers).  margin: the smallest min(|z1|, |z2|) / max(|z1|, |z2|) over the inliers and the four candidates (R, t): no depth
+    may sit on zero, where its sign is the rounding's.  sin2: sin^2 of the angle between the two bearings under the pair's R
+    (the weight before the cheirality test); sin2_any: the smaller of the two candidate rotations'.  Both depths are quotients
+    by it, so their relative error is 2^-52 / sin2: at the epipole itself sin2 is the rounding's, and so is the vote.  Depths
+    that are not finite vote for nothing on either side and are left out of the margin."""
+    x1, y1, x2, y2, _ = points(flow)
+    inl = np.asarray(tv["inlier"]) != 0
+    sin2, sin2_any = np.full(x1.shape, np.nan), np.full(x1.shape, np.nan)
+    if not np.isfinite(tv["F"]).all() or not inl.any():
+        return dict(margin=float("inf"), sin2=sin2, sin2_any=sin2_any)
+    clean = lambda w: np.where(np.isfinite(w), w, 0.0)
+    with np.errstate(all="ignore"):
+        Ra, Rb, t0 = essential_candidates(tv["F"], intr)
+        b1, b2 = bearings(x1[inl], y1[inl], intr), bearings(x2[inl], y2[inl], intr)
+        margin, w = np.inf, np.full(b1.shape[0], np.inf)
+        for Rc in (Ra, Rb):
+            z1, z2, wc = depths(b1 @ Rc.T, b2, t0)                  # (-t0 gives the same depths with the other sign)
+            w = np.fmin(w, clean(wc))
+            z = np.stack([np.abs(z1), np.abs(z2)])
+            ok = np.isfinite(z).all(0) & (z.max(0) > 0)
+            if ok.any():
+                margin = min(margin, float((z.min(0)[ok] / z.max(0)[ok]).min()))
+        sin2[inl] = clean(depths(b1 @ np.asarray(tv["R"]).T, b2, t0)[2])
+    sin2_any[inl] = w
+    return dict(margin=margin, sin2=sin2, sin2_any=sin2_any)
+
+
+def sensitivity(flow, intr, F_init, exclude=None, repeats=8, seed=0, **kw):
+    """how far the restatement's own answer moves under another summation order and another eigen-solver: ``two_view`` again
+    ``repeats`` times with every entry of the normalised A^T A (kept symmetric) multiplied by 1 + d, d uniform in +-2^-50.
+    dict(F, R, t, parallax): the largest change of the normalised F, of R, of t and of the parallax.  It sets the float64
+    bounds of the device comparison and never sees the device."""
+    rng = np.random.default_rng(seed)
+
+    def perturb(M):
+        d = np.triu(rng.uniform(-2.0 ** -50, 2.0 ** -50, M.shape))
+        return M * (1.0 + d + np.triu(d, 1).T)
+
+    base = two_view(flow, intr, F_init, exclude, **kw)
+    out = dict(F=0.0, R=0.0, t=0.0, parallax=0.0)
+    for _ in range(repeats):
+        tv = two_view(flow, intr, F_init, exclude, perturb=perturb, **kw)
+        out["F"] = max(out["F"], float(np.abs(normalise_F(tv["F"]) - normalise_F(base["F"])).max()))
+        out["R"] = max(out["R"], float(np.abs(tv["R"] - base["R"]).max()))
+        out["t"] = max(out["t"], float(np.abs(tv["t"] - base["t"]).max()))
+        out["parallax"] = max(out["parallax"], abs(tv["parallax"] - base["parallax"]))
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------ d. the ratios
@@ -362,10 +425,12 @@ def depth_seen_from(H, W, intr, R, t, iterations=60):
     return ((bearings(ux, uy, intr) * surface(ux, uy, W)[..., None]) @ np.asarray(R).T + np.asarray(t))[..., 2]
 
 
-def make_scene3(H=36, W=48, f=40.0, rvec=(0.01, -0.02, 0.005), tdir=(0.08, 0.02, 0.03), baselines=(0.08, 0.12)):
+def make_scene3(H=36, W=48, f=40.0, rvec=(0.01, -0.02, 0.005), tdir=(0.08, 0.02, 0.03), baselines=(0.08, 0.12), pp=None):
     """three views of one static surface (the middle view sees it as ``surface``): x_{i+1} = R x_i + baselines[i] tdir / |tdir|.
-    dict(fwd [2], bwd [2] float32 flows, intr, extr (3, 3, 4) true world-to-camera with view 0 the world, R, tdir, baselines)"""
-    intr = (float(f), float(f), float(round(W / 2)), float(round(H / 2)))
+    dict(fwd [2], bwd [2] float32 flows, intr, extr (3, 3, 4) true world-to-camera with view 0 the world, R, tdir, baselines);
+    ``pp``: the principal point (default: the rounded centre)"""
+    cx, cy = (round(W / 2), round(H / 2)) if pp is None else pp
+    intr = (float(f), float(f), float(cx), float(cy))
     R = rodrigues(rvec)
     tdir = np.asarray(tdir, dtype=np.float64) / np.linalg.norm(tdir)
     t01, t12 = baselines[0] * tdir, baselines[1] * tdir
@@ -383,8 +448,8 @@ def make_scene3(H=36, W=48, f=40.0, rvec=(0.01, -0.02, 0.005), tdir=(0.08, 0.02,
                 depth=[d0, d1, d2])
 
 
-def exact_flow(depth, intr, R, t):
-    """the float32 flow of a static scene of the given depth under x' = R x + t (no occlusion handling), and the depth in
+def flow64(depth, intr, R, t):
+    """the float64 flow of a static scene of the given depth under x' = R x + t (no occlusion handling), and the depth in
     the second view"""
     H, W = depth.shape
     y, x = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
@@ -392,16 +457,143 @@ def exact_flow(depth, intr, R, t):
     X = bearings(x, y, intr) * depth[..., None]
     X2 = X @ np.asarray(R).T + np.asarray(t)
     u, v = fx * X2[..., 0] / X2[..., 2] + cx, fy * X2[..., 1] / X2[..., 2] + cy
-    return np.stack([u - x, v - y], axis=-1).astype(np.float32), X2[..., 2]
+    return np.stack([u - x, v - y], axis=-1), X2[..., 2]
+
+
+def exact_flow(depth, intr, R, t):
+    """``flow64`` rounded to float32"""
+    flow, z2 = flow64(depth, intr, R, t)
+    return flow.astype(np.float32), z2
+
+
+def make_scene_general(H, W, intr, rvec, t, noise=None):
+    """the analytic static scene under any camera ``intr = (fx, fy, cx, cy)`` and motion: dict(flow, depth, intr, R, t).
+    ``noise = (sigma, seed)``: seeded Gaussian noise of sigma px, added to the float64 flow before it is rounded to float32."""
+    intr = tuple(float(v) for v in intr)
+    depth = scene_depth(H, W)
+    R = rodrigues(rvec)
+    flow, _ = flow64(depth, intr, R, t)
+    if noise is not None:
+        sigma, seed = noise
+        flow = flow + np.random.default_rng(seed).normal(scale=sigma, size=flow.shape)
+    return dict(flow=flow.astype(np.float32), depth=depth, intr=intr, R=R, t=np.asarray(t, dtype=np.float64))
 
 
 def make_scene(H=36, W=48, f=40.0, rvec=(0.01, -0.02, 0.005), t=(0.08, 0.02, 0.03)):
     """the analytic static scene of the tests: dict(flow, depth, intr, R, t)"""
-    intr = (float(f), float(f), float(round(W / 2)), float(round(H / 2)))
-    depth = scene_depth(H, W)
-    R = rodrigues(rvec)
-    flow, _ = exact_flow(depth, intr, R, t)
-    return dict(flow=flow, depth=depth, intr=intr, R=R, t=np.asarray(t, dtype=np.float64))
+    return make_scene_general(H, W, (f, f, round(W / 2), round(H / 2)), rvec, t)
+
+
+# ---------------------------------------------------------------------------------------- motions, cameras, sizes: the cases
+# what each motion reaches in gfl_sfm.hip (asserted on the restatement by tests/test_sfm_host.py and again, with the device's
+# starting matrix, by tests/test_gpu_sfm.py): the winner of the cheirality vote, or the flag
+ROT = (0.01, -0.02, 0.005)
+MOTIONS = {                      # tag: (rvec, t, winner)
+    "base": (ROT, (0.08, 0.02, 0.03), 0),
+    "neg-x": (ROT, (-0.08, 0.02, 0.03), 1),
+    "pos-y": (ROT, (0.02, 0.08, 0.03), 0),
+    "neg-y": (ROT, (0.02, -0.08, 0.03), 1),
+    "fwd": ((0.0, 0.0, 0.0), (0.0, 0.0, 0.1), 0),                  # the epipole is the principal point
+    "back": (ROT, (0.01, 0.0, -0.1), 1),                           # the epipole is inside the image as well
+    "roll": ((0.0, 0.0, 3.0), (0.08, 0.02, 0.03), 2),              # 172 degrees about the axis: the true R has the smaller trace
+    "roll-neg": ((0.0, 0.0, 3.0), (-0.08, 0.02, 0.03), 3),
+    "small": (ROT, (0.004, 0.001, 0.0015), 0),                     # parallax under min_parallax: degenerate, R kept, t = 0
+    "noisy": (ROT, (0.08, 0.02, 0.03), 0),                         # sigma = 0.3 px: thr = K2 median, above the floor
+}
+NOISE = (0.3, 7)
+SIZES = ((8, 8), (33, 47), (64, 65), (91, 91))                    # 64 x 65: two workgroups of 4096 pixels, the second with 64;
+PER_WORKGROUP = 4096                                              # 91 x 91: three
+EPIPOLE_W = 1e-6                   # below this sin^2 the kernels' stated 1 / sin <= 1e3 fails: rho is not compared there
+# Two rotations that differ by 1e-11 (the bound of the comparison) turn a = R x1 by as much, and a x b by a relative
+# 1e-11 / sin: below sin^2 = 1e-14 by more than 1e-4.  There -- at the epipole's own pixel, where sin^2 is 1e-17 .. 1e-21, the
+# square of R's distance from the truth -- the sign of a depth is the rounding's: the pixel's vote and weight are not pinned.
+UNDECIDED_W = 1e-14
+MIN_PARALLAX = 0.1
+
+
+def camera(kind, H, W):
+    """"centred": f = 40 max(H, W) / 48 and the rounded centre; "general": fx != fy and a principal point off the centre and off
+    the pixel grid"""
+    f = 40.0 * max(H, W) / 48.0
+    if kind == "centred":
+        return (f, f, float(round(W / 2)), float(round(H / 2)))
+    return (1.3 * f, 0.9 * f, W / 2 - 3.25, H / 2 + 2.5)
+
+
+CASES = [(m, H, W, cam) for (m, sizes, cam) in (
+    ("base", SIZES, "centred"), ("base", SIZES[1:2], "general"), ("noisy", SIZES, "general"),
+    ("roll", (SIZES[0], SIZES[3]), "centred"), ("roll", SIZES[2:3], "general"),
+    ("roll-neg", SIZES[1:2], "general"), ("roll-neg", SIZES[2:3], "centred"),
+    ("neg-x", SIZES[1:2], "centred"), ("neg-x", SIZES[2:3], "general"),
+    ("pos-y", SIZES[0:1], "centred"), ("pos-y", SIZES[1:2], "general"),
+    ("neg-y", SIZES[0:1], "centred"), ("neg-y", SIZES[2:3], "general"),
+    ("back", SIZES[1:2], "centred"), ("back", SIZES[2:3], "general"),
+    ("small", SIZES[1:2], "centred"), ("small", SIZES[2:3], "general"),
+    ("fwd", SIZES, "centred"), ("fwd", (SIZES[1], SIZES[3]), "general")) for (H, W) in sizes]
+
+
+def case_id(case):
+    return "{}-{}x{}-{}".format(*case)
+
+
+def case_scene(case):
+    """the scene of (motion, H, W, camera kind)"""
+    motion, H, W, cam = case
+    rvec, t, _ = MOTIONS[motion]
+    return make_scene_general(H, W, camera(cam, H, W), rvec, t, NOISE if motion == "noisy" else None)
+
+
+def case_kw(case):
+    """the keywords of ``two_view`` for the case: ``small`` moves the image by 0.074 px at 33 x 47, under the default
+    min_parallax of 0.1 px, and by 0.10 - 0.13 px at 64 x 65 with its longer focal lengths, where the threshold is 0.2 px"""
+    motion, H, W, _ = case
+    return dict(min_parallax=0.2) if motion == "small" and (H, W) == (64, 65) else {}
+
+
+def epipole_cap(H, W):
+    """how many inliers may lie so near the epipole that sin^2 < EPIPOLE_W"""
+    return max(1, int(0.005 * H * W))
+
+
+def check_case(case, flow, intr, ref):
+    """asserts on the restatement's result ``ref`` that the case reaches what it is there for; returns dict(left_out (H, W)
+    bool: the inliers with sin^2 < EPIPOLE_W, undecided (H, W) bool: those with sin^2 < UNDECIDED_W)"""
+    motion, H, W, cam = case
+    tag = case_id(case)
+    n = H * W
+    assert flow.shape == (H, W, 2) and (n + PER_WORKGROUP - 1) // PER_WORKGROUP == {64: 1, 1551: 1, 4160: 2, 8281: 3}[n], tag
+    assert (intr[0] != intr[1] and intr[2] != round(W / 2) and intr[3] != round(H / 2)) == (cam == "general"), tag
+    assert threshold_margin(ref) > 1e-9, (tag, ref["margins"])
+    ch = cheirality(flow, ref, intr)
+    assert ch["margin"] > 1e-9, (tag, ch["margin"])
+    assert np.isfinite(ref["F"]).all() and ref["counts"][0] == n, tag
+    winner = MOTIONS[motion][2]
+    votes = ref["votes"]
+    if motion == "noisy":
+        assert ref["thr"] > E_FLOOR and ref["thr"] == K2 * ref["median"], (tag, ref["thr"])
+        if n > 64:
+            assert 8 <= n - ref["counts"][1] <= n // 20, (tag, ref["counts"])       # a scattered subset is left out
+    else:
+        assert ref["thr"] == E_FLOOR and ref["counts"][1] == n, (tag, ref["thr"], ref["counts"])
+    min_parallax = case_kw(case).get("min_parallax", MIN_PARALLAX)
+    assert abs(ref["parallax"] / min_parallax - 1.0) > 0.01, (tag, ref["parallax"])      # the flag does not hang on a rounding
+    if motion == "small":                                          # degenerate by parallax alone: a finite F, every pixel kept
+        assert ref["degenerate"] and 0.05 < ref["parallax"] < min_parallax and not ref["t"].any(), (tag, ref["parallax"])
+        assert np.isfinite(ref["R"]).all() and not ref["weight"].any(), tag
+    else:
+        assert not ref["degenerate"], (tag, ref["parallax"])
+    if not (motion == "noisy" and n == 64):                        # (8 x 8 under 0.3 px of noise: the votes may split)
+        assert int(np.argmax(votes)) == winner and votes[winner] > 2 * np.delete(votes, winner).max(), (tag, votes)
+    with np.errstate(invalid="ignore"):
+        left_out, undecided = ch["sin2"] < EPIPOLE_W, ch["sin2_any"] < UNDECIDED_W
+    if motion in ("fwd", "back"):
+        assert left_out.sum() <= epipole_cap(H, W), (tag, left_out.sum())
+        assert undecided.sum() <= 1 and not (undecided & ~left_out).any(), (tag, undecided.sum())
+    elif motion == "small":                                        # (no parallax: sin^2 is small everywhere, and nothing has weight)
+        assert not undecided.any(), tag
+    else:
+        assert not left_out.any() and not undecided.any(), (tag, left_out.sum())
+    return dict(left_out=left_out, undecided=undecided)
 
 
 def add_block(flow, y0=10, x0=14, size=12, offset=(3.0, -2.0)):

@@ -1,13 +1,14 @@
 """The move mask from the flow on the device (``-m gpu``; gfl_epi_fundamental, gfl_epi_mask, gflow_amd/move_seg.py) through
 the C ABI, every output pre-filled with garbage, against the float64 restatement (tests/move_seg_ref.py) on the scenes of
-tests/test_move_seg_host.py: 40 x 56 and 37 x 53 (no multiple of a workgroup's share) with K = 64, a third with unknown
+tests/test_move_seg_host.py: 40 x 56, 37 x 53 (no multiple of a workgroup's share) and 64 x 65 (two shares) with K = 64, a third with unknown
 pixels and broken samples, a fourth of 8 x 8 where disk(5) covers most of the image; and 2 x 4 and 3 x 4 with eight known
 pixels, where the median's rank rests on the count that the selection's first pass finds.
 
 Bounds.  F_CONST: ||F_device - F_restatement|| <= F_CONST * eps64 * lambda_max / lambda_1 -- the form eigenvector perturbation
 theory gives for a null vector taken from A^T A; the theory does not give the constant, so it is measured: the largest ratio
 on these scenes was 0.454 (0.413 at 40 x 56, 0.454 at 37 x 53, 0.337 at 8 x 8; one hypothesis of 192 left out), and F_CONST
-is ten times that.  MEDIAN_REL: the largest relative difference measured between the device's medians and the restatement's
+is ten times that.  (64 x 65, added later for its two workgroups of EPI_PER_BLOCK = 4096 pixels -- the second has 64 --, gave
+0.574 with one hypothesis of 64 left out: F_CONST stays what the first three scenes made it.)  MEDIAN_REL: the largest relative difference measured between the device's medians and the restatement's
 medians of the device's own F was 0 -- all 192, and the 60 of the scene with unknown pixels, equal bit for bit -- so ten
 times that is 0 and the test asks for equality.  It is not near 1e-12, the level cancellation in z would give two
 differently ordered sums, because both sides evaluate the one expression include/gflow_hip.h writes down, in its order,
@@ -29,7 +30,7 @@ MEDIAN_REL = 10 * 0.0
 ERR_NORM_REL = 2.0 ** -23
 RATIO_MIN, LEFT_OUT_MAX = 1e-9, 0.05
 K = 64
-SCENES = [(40, 56, 0), (37, 53, 1), (8, 8, 0)]
+SCENES = [(40, 56, 0), (37, 53, 1), (8, 8, 0), (64, 65, 2)]      # 64 x 65: two workgroups of EPI_PER_BLOCK = 4096 pixels, the second with 64
 GARBAGE_F64, GARBAGE_U8, GARBAGE_I32 = -1234.5678e100, 0xA5, -77
 
 

@@ -5,7 +5,10 @@ tests/test_gpu_sfm.py.
 The scene is analytic and static: 36 x 48, f = 40, depth 2 + 0.5 sin(0.2 x) cos(0.15 y) + 0.4 x / W, rotation vector
 (0.01, -0.02, 0.005), translation (0.08, 0.02, 0.03), exact flows rounded to float32.  Every bound below is 100 x what the
 restatement itself gives on that input (the figure is written beside it): the margin covers other LAPACK builds and
-summation orders."""
+summation orders.
+
+The motions, cameras and sizes that tests/test_gpu_sfm.py compares on the device (sfm_ref.CASES) are held here, on the
+restatement alone, to reach the branch each is there for: that makes the choice of inputs checkable without a device."""
 import json
 import os
 
@@ -106,6 +109,62 @@ def test_forward_flows_alone_chain_through_the_medians():
     # the smoothed median depths of neighbouring frames agree to a few per cent: so does the baseline ratio
     assert abs(res["baseline"][1] / res["baseline"][0] - 1.5) < 0.05
     assert np.all(res["depth"][2] == 1.0)
+
+
+@pytest.mark.parametrize("case", R.CASES, ids=R.case_id)
+def test_every_case_reaches_what_it_is_there_for(case):
+    """the motions, cameras and sizes of tests/test_gpu_sfm.py on the restatement alone: the winner of the vote, the branch
+    of the threshold, the flag, both margins and the cap on pixels near the epipole (sfm_ref.check_case); and the
+    restatement recovers the true pose of every exact, non-degenerate case: R to 1e-6, t / |t| to 1e-5"""
+    motion, H, W, cam = case
+    sc = R.case_scene(case)
+    with np.errstate(all="ignore"):
+        tv = R.two_view(sc["flow"], sc["intr"], R.initial_F(sc["flow"]), **R.case_kw(case))
+    info = R.check_case(case, sc["flow"], sc["intr"], tv)
+    assert len(tv["margins"]) == 3 and R.threshold_margin(tv) == min(tv["margins"])
+    if cam == "centred" and motion == "fwd":                       # the epipole is a pixel's centre
+        assert info["left_out"][round(H / 2), round(W / 2)] and info["undecided"].sum() == 1
+    if motion == "noisy":
+        assert np.abs(sc["flow"] - R.case_scene((("base",) + case[1:]))["flow"]).max() > 0.3
+        return
+    dR, dt = np.abs(tv["R"] - sc["R"]).max(), np.abs(tv["t"] - sc["t"] / np.linalg.norm(sc["t"])).max()
+    print(f"{R.case_id(case)}: R {dR:.2e} t {dt:.2e} votes {tv['votes']} parallax {tv['parallax']:.3f}")
+    assert dR < 1e-6                                               # (a degenerate pair keeps its R)
+    assert tv["degenerate"] or dt < 1e-5
+
+
+def test_the_cases_cover_what_the_kernels_branch_on():
+    motions = {c[0] for c in R.CASES}
+    assert motions == set(R.MOTIONS) and {R.MOTIONS[m][2] for m in motions} == {0, 1, 2, 3}
+    for m in motions:                                              # the general camera under every motion
+        assert any(c[0] == m and c[3] == "general" for c in R.CASES), m
+    for size in R.SIZES:                                           # every size under base, noisy and a rolled view
+        for group in (("base",), ("noisy",), ("roll", "roll-neg"), ("fwd",)):
+            assert any(c[0] in group and c[1:3] == size for c in R.CASES), (size, group)
+    assert sorted({-(-H * W // R.PER_WORKGROUP) for (H, W) in R.SIZES}) == [1, 2, 3] and 64 * 65 - R.PER_WORKGROUP == 64
+    assert len(set(R.CASES)) == len(R.CASES) <= 32
+
+
+def test_the_scene_builders_keep_their_defaults():
+    """make_scene and make_scene3 through the general builder: the bits they always gave"""
+    sc = R.make_scene()
+    depth = R.scene_depth(36, 48)
+    flow, _ = R.exact_flow(depth, (40.0, 40.0, 24.0, 18.0), R.rodrigues((0.01, -0.02, 0.005)), (0.08, 0.02, 0.03))
+    assert sc["intr"] == (40.0, 40.0, 24.0, 18.0) and sc["flow"].dtype == np.float32 and np.array_equal(sc["flow"], flow)
+    assert np.array_equal(R.make_scene_general(36, 48, sc["intr"], (0.01, -0.02, 0.005), (0.08, 0.02, 0.03), noise=(0.0, 1))["flow"], flow)
+    noisy = R.make_scene_general(36, 48, sc["intr"], (0.01, -0.02, 0.005), (0.08, 0.02, 0.03), noise=(0.3, 1))["flow"]
+    assert noisy.dtype == np.float32 and 0.25 < (noisy - flow).std() < 0.35
+    assert R.make_scene3()["intr"] == (40.0, 40.0, 24.0, 18.0) and R.make_scene3(pp=(20.75, 20.5))["intr"] == (40.0, 40.0, 20.75, 20.5)
+
+
+def test_the_sensitivity_probe():
+    """8 repeats under relative 2^-50 perturbations of A^T A: small against the recovery of the pose, not zero, repeatable"""
+    sc = R.make_scene()
+    F0 = R.initial_F(sc["flow"])
+    a, b = R.sensitivity(sc["flow"], sc["intr"], F0), R.sensitivity(sc["flow"], sc["intr"], F0)
+    assert a == b and sorted(a) == ["F", "R", "parallax", "t"]
+    assert all(0 < v < 1e-9 for v in a.values()), a
+    assert R.sensitivity(sc["flow"], sc["intr"], F0, repeats=0) == dict(F=0.0, R=0.0, t=0.0, parallax=0.0)
 
 
 def test_numpy_ties(scene):
