@@ -35,9 +35,11 @@ def _targets(H, W, seed):
     return img, dep
 
 
-def _engine(raw, s, img, dep, pose=None, **hyper):
+def _engine(raw, s, img, dep, pose=None, cu_count=0, deterministic=False, **hyper):
+    """``cu_count``, ``deterministic``: FitEngine's (the number of tile queues, tests/test_gpu_queue_counts.py; the mode)."""
     from gflow_amd.fused import FitEngine
-    eng = FitEngine(s["W"], s["H"], capacity=max(2 * raw["xyz"].shape[0], 1024), device=DEV, bg=hyper.pop("bg", 0.0))
+    eng = FitEngine(s["W"], s["H"], capacity=max(2 * raw["xyz"].shape[0], 1024), device=DEV, bg=hyper.pop("bg", 0.0),
+                    cu_count=cu_count, deterministic=deterministic)
     eng.set_splats({k: v.to(DEV) for k, v in raw.items()})
     eng.intr.copy_(s["intr"].to(DEV))
     if pose is not None:
@@ -64,14 +66,26 @@ def test_fused_forward_matches_oracle_and_operator_path(setup):
     _check_fused_forward(*setup)
 
 
-def _check_fused_forward(s, raw, img, dep, tag=""):
-    import gflow_amd.render as R
-    eng = _engine(raw, s, img, dep, pose=POSE, bg=0.2)
-    eng.forward()
-    eng.check_overflow()
+def _forward_oracle(s, raw):
+    """What _check_fused_forward holds an engine against, on the CPU: the activated rows, the extrinsic POSE stands for, the
+    oracle's render of them over bg 0.2 and the pairs its bounding rectangles bin.  A caller that checks several engines
+    computes it once and hands it to every check (``oracle=``); nothing in it is written afterwards."""
     act = FO.activate(raw)
     extr = LO.pose_to_extr(POSE)
     oc = MO.render_multiple([*act, s["intr"], extr, 0.2, s["W"], s["H"]], ["rgb", "depth_map", "uv", "depth"])
+    vis = oc["depth"] != 0
+    tiles = MO.ewa_project(act[0], MO.compute_cov3d(act[1], act[2], vis), s["intr"], extr, oc["uv"], s["W"], s["H"],
+                           vis)[2]
+    return act, extr, oc, int(tiles.sum())
+
+
+def _check_fused_forward(s, raw, img, dep, tag="", oracle=None, **engine):
+    """``engine``: _engine's ``cu_count`` / ``deterministic``; ``oracle``: a _forward_oracle(s, raw) made earlier."""
+    import gflow_amd.render as R
+    eng = _engine(raw, s, img, dep, pose=POSE, bg=0.2, **engine)
+    eng.forward()
+    eng.check_overflow()
+    act, extr, oc, pairs_api = oracle if oracle is not None else _forward_oracle(s, raw)
     ref4 = torch.cat([oc["rgb"], oc["depth_map"]])
     close_frac(eng.render, ref4, 1e-4, 1e-5, bad_frac=3e-4, hard=2e-2, what=tag + "fused render vs oracle")
     close_frac(eng.uv, oc["uv"], 1e-5, 1e-3, what=tag + "uv")
@@ -83,10 +97,7 @@ def _check_fused_forward(s, raw, img, dep, tag=""):
     api4 = torch.cat([og["rgb"], og["depth_map"]])
     close_frac(eng.render, api4, 2e-5, 2e-6, bad_frac=1e-4, hard=2e-2, what=tag + "fused vs operator path")
     # the exact-disc culling only ever drops pairs: K_fused <= K_api, same image
-    vis = oc["depth"] != 0
-    tiles = MO.ewa_project(act[0], MO.compute_cov3d(act[1], act[2], vis), s["intr"], extr, oc["uv"], s["W"], s["H"],
-                           vis)[2]
-    assert 0 < eng.K <= int(tiles.sum())
+    assert 0 < eng.K <= pairs_api
     # determinism
     r1 = eng.render.clone()
     ids1 = eng.ids[:eng.K].clone()
@@ -98,18 +109,29 @@ def test_fused_gradients_match_oracle(setup):
     _check_fused_gradients(*setup)
 
 
-def _check_fused_gradients(s, raw, img, dep, tag="", rows=None):
-    lam = dict(lambda_rgb=1.0, lambda_depth=0.1, lambda_var=10.0)
-    eng = _engine(raw, s, img, dep, pose=POSE, lr=1e-3, lr_camera=1e-3, total_iters=100, **lam)
-    eng.iteration()
-    eng.check_overflow()
-    # oracle
+_GRAD_LAMBDAS = dict(lambda_rgb=1.0, lambda_depth=0.1, lambda_var=10.0)
+
+
+def _gradient_oracle(s, raw, img, dep):
+    """What _check_fused_gradients holds an engine against: the oracle's fit loss at POSE, backpropagated -- the leaves with
+    their gradients (rows, pose, depth affine) and the loss terms.  As _forward_oracle: computed once by a caller that checks
+    several engines, read only."""
+    lam = _GRAD_LAMBDAS
     rc = {k: v.clone().requires_grad_(True) for k, v in raw.items()}
     pose = POSE.clone().requires_grad_(True)
     ab = torch.tensor([1.0, 0.0], requires_grad=True)
     frame = dict(image=img, depth=dep)
     loss, info = FO.fit_loss(rc, pose, ab, s["intr"], frame, 0.0, lam["lambda_rgb"], lam["lambda_depth"], lam["lambda_var"])
     loss.backward()
+    return rc, pose, ab, info
+
+
+def _check_fused_gradients(s, raw, img, dep, tag="", rows=None, oracle=None, **engine):
+    """``engine``: _engine's ``cu_count`` / ``deterministic``; ``oracle``: a _gradient_oracle(s, raw, img, dep) made earlier."""
+    eng = _engine(raw, s, img, dep, pose=POSE, lr=1e-3, lr_camera=1e-3, total_iters=100, **_GRAD_LAMBDAS, **engine)
+    eng.iteration()
+    eng.check_overflow()
+    rc, pose, ab, info = oracle if oracle is not None else _gradient_oracle(s, raw, img, dep)
     l_rgb, l_depth = eng.loss_terms()
     assert abs(l_rgb.item() - info["l_rgb"].item()) <= 1e-4 * abs(info["l_rgb"].item())
     assert abs(l_depth.item() - info["l_depth"].item()) <= 1e-4 * abs(info["l_depth"].item())
@@ -120,6 +142,8 @@ def _check_fused_gradients(s, raw, img, dep, tag="", rows=None):
         ref = rc[k].grad.reshape(n, b - a)
         got = g_all[:, a:b].cpu()
         rel = (got - ref).norm() / ref.norm()
+        if engine:
+            observe(f"{tag}d_{k}: relative L2 {rel:.2e} (bound 0.002)")
         assert rel < 2e-3, f"{tag}d_{k}: relative L2 error {rel:.2e}"
         close_frac(got, ref, 5e-3, 5e-4 * ref.abs().max().item(), bad_frac=1e-2, what=f"{tag}d_{k}")
         if rows is not None:
@@ -774,10 +798,16 @@ def _copy_engine_state(src, dst):
 def test_four_iterations_in_one_call_track_four_single_iterations(setup):
     """gfl_fit_iterations(count = 4), launched one by one and replayed as ONE graph, against four single iterations (the
     iterations of a call but the first bin into reserved tile regions; the single ones do too, through FitEngine)."""
+    _check_four_iterations_in_one_call(setup)
+
+
+def _check_four_iterations_in_one_call(setup, **engine):
+    """``engine``: _engine's ``cu_count`` / ``deterministic`` (tests/test_gpu_queue_counts.py: the queue counts at which no
+    tile regions are reserved)"""
     s, raw, img, dep = setup
     hyper = dict(lambda_rgb=1.0, lambda_depth=0.1, lambda_var=10.0, lr=4e-3, lr_camera=0.0, total_iters=100)
-    a = _engine(raw, s, img, dep, pose=POSE, **hyper)
-    b = _engine(raw, s, img, dep, pose=POSE, **hyper)
+    a = _engine(raw, s, img, dep, pose=POSE, **hyper, **engine)
+    b = _engine(raw, s, img, dep, pose=POSE, **hyper, **engine)
     for use_graph in (False, True, True):
         a.iteration(count=4, use_graph=use_graph)
         for _ in range(4):
@@ -872,12 +902,17 @@ def test_reserved_tile_regions_give_the_lists_of_the_exact_binning_path(setup, w
     """An iteration that follows a full iteration bins into the tile regions that one's last launch reserved (one launch in
     place of preprocess + column scan + scatter).  Held against the exact path on the SAME rows: records, every tile's sorted
     list, the render and the transmittance bit for bit; the stepped rows to the order of the backward's LDS adds."""
+    _check_reserved_tile_regions(setup, with_scale_term)
+
+
+def _check_reserved_tile_regions(setup, with_scale_term, **engine):
+    """``engine``: _engine's ``cu_count`` / ``deterministic`` (tests/test_gpu_queue_counts.py)"""
     s, raw, img, dep = setup
     hyper = dict(lambda_rgb=1.0, lambda_depth=0.1, lambda_var=10.0, lr=4e-3, lr_camera=0.0, total_iters=100)
     if with_scale_term:
         hyper["lambda_scale"] = 0.5
-    a = _engine(raw, s, img, dep, pose=POSE, **hyper)
-    b = _engine(raw, s, img, dep, pose=POSE, **hyper)
+    a = _engine(raw, s, img, dep, pose=POSE, **hyper, **engine)
+    b = _engine(raw, s, img, dep, pose=POSE, **hyper, **engine)
     if not _reserved_on(a):
         pytest.skip("reserved tile regions are switched off (GFL_RESERVED=0)")
     if with_scale_term:

@@ -29,15 +29,22 @@ def test_render_operator_values_and_gradients_match_oracle(bg):
     _check_render_operator(random_scene(3000, 200, 136, seed=11, sigma_px=2.5), bg)
 
 
-def _check_render_operator(s, bg, tag="", rows=None):
-    import gflow_amd.render as R
+def _render_oracle(s, bg):
+    """What _check_render_operator holds render() against: the loss weights, the oracle's leaves with their gradients and its
+    outputs.  A caller that checks several engines computes it once (``oracle=``); nothing in it is written afterwards."""
     n, W, H = s["xyz"].shape[0], s["W"], s["H"]
     w = _weights(H, W, n, 5)
-    # oracle
     leaves_c = {k: s[k].clone().requires_grad_(True) for k in NAMES}
     extr_c = s["extr"].clone().requires_grad_(True)
     oc = MO.render_multiple([*[leaves_c[k] for k in NAMES], s["intr"], extr_c, bg, W, H], ["rgb", "uv", "depth", "depth_map"])
     _loss(oc, w).backward()
+    return w, leaves_c, extr_c, oc
+
+
+def _check_render_operator(s, bg, tag="", rows=None, oracle=None):
+    import gflow_amd.render as R
+    W, H = s["W"], s["H"]
+    w, leaves_c, extr_c, oc = oracle if oracle is not None else _render_oracle(s, bg)
     # fused operator
     leaves_g = {k: s[k].clone().to(DEV).requires_grad_(True) for k in NAMES}
     extr_g = s["extr"].clone().to(DEV).requires_grad_(True)
