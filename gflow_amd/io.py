@@ -22,6 +22,7 @@ not needed, PIL reads and writes the PNGs.
 import json
 import os
 import warnings
+from dataclasses import dataclass
 from pathlib import Path
 
 import numpy as np
@@ -126,13 +127,8 @@ def read_mask(mask_path, resize=None):
 
 def read_depth(depth_path, resize=None, depth_scale=1.0, depth_offset=0.0):
     """read.py:60-70 -> (H,W) float."""
-    t = torch.tensor(_depth_array(depth_path), dtype=torch.float32).unsqueeze(0)
+    t = torch.tensor(np.load(depth_path), dtype=torch.float32).unsqueeze(0)
     return _resize_chw(t, resize).squeeze(0) * depth_scale + depth_offset
-
-
-def _depth_array(src):
-    """a frame's depth at its native resolution, wherever it comes from: the array of a .npy file, or an estimate's array"""
-    return src if isinstance(src, np.ndarray) else np.load(src)
 
 
 def read_camera(camera_paths):
@@ -151,9 +147,10 @@ def read_camera(camera_paths):
 class AviFrame:
     """frame ``index`` of the Motion-JPEG AVI ``path``: what stands in a clip's image list where a file's path would"""
 
-    def __init__(self, path, index):
+    def __init__(self, path, index, data=None):
         self.path, self.index = str(path), int(index)
         self.name = f"frame_{self.index:05d}"
+        self.data = data                           # the frame's JPEG bytes, as sequence_paths took them from the parsed file
 
     def __repr__(self):
         return f"{self.path}:{self.name}"
@@ -169,29 +166,44 @@ def _frame_name(ip):
     return ip.name if isinstance(ip, AviFrame) else os.path.basename(ip).split(".")[0]
 
 
-def sequence_paths(sequence_path, frame_start=0, frame_range=-1, skip_interval=1):
-    """The file lists of fit_video.py:79-99, same globbing, slicing and ordering.  For a video file ``img`` lists its frames
-    (AviFrame) and the sibling folders hang on the path without its ``.avi``."""
+def _every_path(sequence_path):
+    """the file lists of a sequence before they are sliced; a video file is parsed here, once"""
     sp = str(sequence_path).rstrip("/")
     if is_video(sp):
         from .video import read_avi
-        img = [AviFrame(sp, i) for i in range(len(read_avi(sp)["frames"]))]
+        img = [AviFrame(sp, i, data) for i, data in enumerate(read_avi(sp)["frames"])]
         sp = sp[:-4]
     else:
         img = sorted(Path(sp).glob("*.png")) + sorted(Path(sp).glob("*.jpg"))
-    if frame_range == -1:
-        frame_range = len(img) - 1
-    cut = lambda lst, n=frame_range: lst[frame_start:frame_start + n][::skip_interval]
     flow_dir = Path(sp + "_flow_unimatch")
     return dict(
-        img=cut(img),
-        depth=cut(sorted(Path(sp + "_depth_mast3r_s2").glob("*.npy"))),
-        occ=cut(sorted(flow_dir.glob("*occ_bwd.png")) + sorted(flow_dir.glob("*occ_bwd.jpg")), frame_range - 1),
-        flow=cut(sorted(flow_dir.glob("*pred.flo"))),
-        flow_bwd=cut(sorted(flow_dir.glob("*pred_bwd.flo"))),
-        move=cut(sorted(Path(sp + "_epipolar").glob("*_open.png"))),
-        camera=cut(sorted(Path(sp + "_camera_mast3r_s2").glob("*.json"))),
+        img=img,
+        depth=sorted(Path(sp + "_depth_mast3r_s2").glob("*.npy")),
+        occ=sorted(flow_dir.glob("*occ_bwd.png")) + sorted(flow_dir.glob("*occ_bwd.jpg")),
+        flow=sorted(flow_dir.glob("*pred.flo")),
+        flow_bwd=sorted(flow_dir.glob("*pred_bwd.flo")),
+        move=sorted(Path(sp + "_epipolar").glob("*_open.png")),
+        camera=sorted(Path(sp + "_camera_mast3r_s2").glob("*.json")),
     )
+
+
+def _slicer(n_images, frame_start, frame_range, skip_interval):
+    """the slice fit_video.py:79-99 takes of every list (``less``: the occlusion masks' list is one shorter)"""
+    if frame_range == -1:
+        frame_range = n_images - 1
+    return lambda lst, less=0: lst[frame_start:frame_start + frame_range - less][::skip_interval]
+
+
+def sequence_paths(sequence_path, frame_start=0, frame_range=-1, skip_interval=1):
+    """The file lists of fit_video.py:79-99, same globbing, slicing and ordering.  For a video file ``img`` lists its frames
+    (AviFrame) and the sibling folders hang on the path without its ``.avi``."""
+    every = _every_path(sequence_path)
+    cut = _slicer(len(every["img"]), frame_start, frame_range, skip_interval)
+    return {k: cut(v, k == "occ") for k, v in every.items()}
+
+
+_OPTIONS = dict(decode=("host", "device"), occ_masks=("files", "flow"), move_masks=("files", "epipolar"),
+                flows=("files", "estimate"), depth_camera=("files", "estimate"))
 
 
 def load_sequence(sequence_path, resize=None, frame_start=0, frame_range=-1, skip_interval=1, depth_offset=0.0,
@@ -230,189 +242,203 @@ def load_sequence(sequence_path, resize=None, frame_start=0, frame_range=-1, ski
     gflow_amd.video.parse_jpeg accepts in one gflow_amd.video.decode_jpeg call per shape -- the same bits, so the frames are
     the same tensors -- and leaves PNGs and refused JPEGs to PIL, with one warning per clip that says how many.  A video
     file's frames (``sequence_path`` a ``.avi`` file) are always decoded on the device: without ``device`` it raises."""
-    if decode not in ("host", "device"):
-        raise ValueError(f"load_sequence: decode must be \"host\" or \"device\", got {decode!r}")
+    given = dict(decode=decode, occ_masks=occ_masks, move_masks=move_masks, flows=flows, depth_camera=depth_camera)
+    for name, (a, b) in _OPTIONS.items():
+        if given[name] not in (a, b):
+            raise ValueError(f"load_sequence: {name} must be \"{a}\" or \"{b}\", got {given[name]!r}")
     if decode == "device" and device is None:
         raise ValueError("load_sequence: decode=\"device\" needs device=")
     if is_video(sequence_path) and device is None:
         raise RuntimeError(f"gflow_amd.io: {sequence_path}: a video file is decoded on a HIP (cuda) device, pass device=; there "
                            "is no CPU fallback")
-    if occ_masks not in ("files", "flow"):
-        raise ValueError(f"load_sequence: occ_masks must be \"files\" or \"flow\", got {occ_masks!r}")
-    if move_masks not in ("files", "epipolar"):
-        raise ValueError(f"load_sequence: move_masks must be \"files\" or \"epipolar\", got {move_masks!r}")
-    if flows not in ("files", "estimate"):
-        raise ValueError(f"load_sequence: flows must be \"files\" or \"estimate\", got {flows!r}")
-    if depth_camera not in ("files", "estimate"):
-        raise ValueError(f"load_sequence: depth_camera must be \"files\" or \"estimate\", got {depth_camera!r}")
     if depth_camera == "files" and focal is not None:
         raise ValueError("load_sequence: focal is the assumption of depth_camera=\"estimate\"; the files carry their own")
-    p = sequence_paths(sequence_path, frame_start, frame_range, skip_interval)
-    n = len(p["img"])
-    if flows == "estimate":
-        fwd, bwd = _estimated_flows(sequence_path, frame_start, frame_range, skip_interval, device, decode)
-    else:
-        fwd, bwd = [_FloFile(f) for f in p["flow"]], [_FloFile(f) for f in p["flow_bwd"]]
-    fwd, bwd = fwd[:n], bwd[:n]
-    if depth_camera == "estimate":
-        if skip_interval != 1:
-            raise ValueError("load_sequence: depth_camera=\"estimate\" needs consecutive frames (skip_interval = 1)")
-        depth, focal, pp, poses = _estimated_depth_camera(p, fwd, bwd, n, move_masks, occ_masks, focal, device)
-        p = dict(p, depth=depth)
-    else:
-        focal, pp, poses = read_camera(p["camera"])
-    if device is not None:
-        frames = _load_frames_device(p, fwd, bwd, focal, pp, poses, resize, depth_offset, move_masks, occ_masks, blur,
-                                     torch.device(device), decode)
-    else:
-        frames = _load_frames_host(p, fwd, bwd, focal, pp, poses, resize, depth_offset, move_masks, occ_masks, blur)
+    if depth_camera == "estimate" and skip_interval != 1:
+        raise ValueError("load_sequence: depth_camera=\"estimate\" needs consecutive frames (skip_interval = 1)")
+    # the device everything below works on: the frames', or the current one where only an estimate needs it
+    dev = None
+    if device is not None or "estimate" in (flows, depth_camera):
+        if not torch.cuda.is_available() or (device is not None and torch.device(device).type != "cuda"):
+            raise RuntimeError("gflow_amd.io: load_sequence with device=, flows=\"estimate\" or depth_camera=\"estimate\" needs a "
+                               "HIP (cuda) device; there is no CPU fallback")
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    clip = _resolve(sequence_path, frame_start, frame_range, skip_interval, move_masks, occ_masks, flows, depth_camera, focal,
+                    decode, dev)
+    prep = _HostPrep(resize, blur, depth_offset) if device is None else _DevicePrep(dev, resize, blur, depth_offset)
+    frames = _assemble(clip, prep)
     if move_masks == "epipolar":
         from .move_seg import clip_move_masks
-        clip_move_masks(frames, n_flows=len(fwd))
+        clip_move_masks(frames, n_flows=len(clip.fwd))
     return frames
 
 
-class _FloFile:
-    """a frame's flow at its native resolution, wherever it comes from: read() is the (h, w, 2) float32 array of a .flo
-    file (None on a bad magic number) or of an estimate"""
+# ---- 1. resolve: the clip's sources at their native resolution, every file opened once
+@dataclass
+class _Clip:
+    """The n frames' sources as arrays -- or device tensors, where something was decoded or estimated there."""
+    names: list
+    images: list                                   # ((H, W, C <= 3) uint8 or float32, the divisor that makes it [0, 1])
+    fwd: list                                      # (h, w, 2) of pair i, None for a bad file; shorter than n: no more pairs
+    bwd: list
+    depth: list                                    # (H, W)
+    move: list                                     # (H, W, C) as _decode_mask gives it, None without a file
+    occ: list                                      # of PAIR i, as an image with its divisor; None without one
+    focal: float
+    pp: list
+    poses: np.ndarray
 
-    def __init__(self, path=None, array=None):
-        self.path, self.array = path, array
 
-    def read(self):
-        return _read_flo(self.path) if self.array is None else self.array
-
-
-def _estimated_flows(sequence_path, frame_start, frame_range, skip_interval, device, decode="host"):
-    """(forward, backward) _FloFile lists as sequence_paths would list the files of a folder that holds the flows of EVERY
-    pair of consecutive images (the one ``python -m gflow_amd.optflow`` writes): file k is the pair (image k, image k + 1)."""
-    from .optflow import clip_flows, pair_flows
-    sp = str(sequence_path).rstrip("/")
-    img = sequence_paths(sp, frame_range=1 << 30)["img"]
-    if frame_range == -1:
-        frame_range = len(img) - 1
-    pairs = list(range(max(len(img) - 1, 0)))[frame_start:frame_start + frame_range][::skip_interval]
-    if not pairs:
-        return [], []
-    if decode == "device" or is_video(sp):
-        # the decoded stack instead of paths: only the images the pairs touch (i and i + 1 stay neighbours in it)
-        used = sorted(set(pairs) | {i + 1 for i in pairs})
-        where = {i: j for j, i in enumerate(used)}
-        dev = torch.device(device)
-        arrays = [a if torch.is_tensor(a) else torch.from_numpy(np.array(a)).to(dev)
-                  for a, _ in _decode_images([img[i] for i in used], decode, dev)]
-        if len({(tuple(a.shape), a.dtype) for a in arrays}) != 1 or arrays[0].dtype != torch.uint8:
-            raise ValueError("load_sequence: flows=\"estimate\" from device-decoded images needs 8-bit images of one shape")
-        stack = torch.stack(arrays)
-        stack = stack.expand(-1, -1, -1, 3).contiguous() if stack.shape[-1] == 1 else stack
-        fwd, bwd = clip_flows(stack, pairs=[where[i] for i in pairs])
+def _resolve(sequence_path, frame_start, frame_range, skip_interval, move_masks, occ_masks, flows, depth_camera, focal, decode,
+             dev):
+    """In dependency order: images -> flows -> native occlusion -> the geometry's exclusion masks -> depth and camera."""
+    every = _every_path(sequence_path)
+    cut = _slicer(len(every["img"]), frame_start, frame_range, skip_interval)
+    p = {k: cut(v, k == "occ") for k, v in every.items()}
+    n = len(p["img"])
+    # images: the slice's and, for estimated flows, the ones its pairs touch (the last pair reaches one image past the slice)
+    mine = cut(list(range(len(every["img"]))))
+    pairs = cut(list(range(max(len(every["img"]) - 1, 0)))) if flows == "estimate" else []
+    touched = sorted(set(pairs) | {i + 1 for i in pairs})
+    used = sorted(set(mine) | set(touched))
+    decoded = dict(zip(used, _decode_images([every["img"][i] for i in used], decode, dev)))
+    # flows: pair k of the list is (image k, image k + 1), as in a folder that holds the flows of EVERY pair
+    if flows == "files":
+        fwd = [_read_flo(f) for f in p["flow"][:n]]
+        bwd = [_read_flo(f) for f in p["flow_bwd"][:n]] if occ_masks == "flow" or depth_camera == "estimate" else []
+    elif pairs:
+        from .optflow import clip_flows
+        where = {i: j for j, i in enumerate(touched)}              # (i and i + 1 stay neighbours in the stack)
+        stack = _image_stack([decoded[i] for i in touched], dev, decode == "device" or is_video(sequence_path))
+        fwd, bwd = (list(f[:n]) for f in clip_flows(stack, pairs=[where[i] for i in pairs]))
     else:
-        fwd, bwd = pair_flows(img, pairs, device=device)
-    fwd, bwd = fwd.cpu().numpy(), bwd.cpu().numpy()
-    return ([_FloFile(array=np.ascontiguousarray(f)) for f in fwd], [_FloFile(array=np.ascontiguousarray(f)) for f in bwd])
-
-
-def _estimated_depth_camera(p, fwd_src, bwd_src, n, move_masks, occ_masks, focal, device):
-    """(depth arrays, focal, pp, poses) of the n frames as the files would give them, from gflow_amd.sfm.clip_depth_camera on
-    the native flows.  The backward flows are used when every pair has one; the exclusions are the move masks (on the forward
-    flows' grids) and the occlusion masks (``occ_bwd`` on the backward flows' grids, and with occ_masks="flow" ``occ`` on the
-    forward ones'), read where a file of the flows' shape is there, computed where the loader computes them."""
-    from .sfm import clip_depth_camera, warn_unreliable
-    if n < 1:
-        raise ValueError("load_sequence: depth_camera=\"estimate\" needs at least one frame")
-    fwd = [f.read() for f in fwd_src[:n]]
-    if len(fwd) < max(n - 1, 1) or any(f is None for f in fwd):
-        raise ValueError(f"load_sequence: depth_camera=\"estimate\" needs a forward flow between the {n} frames, found {len(fwd)}")
+        fwd, bwd = [], []
     m = len(fwd)
-    bwd = [f.read() for f in bwd_src[:m]]
-    bwd = None if len(bwd) < m or any(b is None for b in bwd) else bwd
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    if dev.type != "cuda" or not torch.cuda.is_available():
-        raise RuntimeError("gflow_amd.io: depth_camera=\"estimate\" needs a HIP (cuda) device; there is no CPU fallback")
-    f_dev = torch.from_numpy(np.stack(fwd)).to(dev)
-    b_dev = None if bwd is None else torch.from_numpy(np.stack(bwd)).to(dev)
-    shape = tuple(f_dev.shape[1:3])
-    ex_f = torch.zeros((m,) + shape, dtype=torch.bool, device=dev)
-    ex_b = torch.zeros((m,) + shape, dtype=torch.bool, device=dev)
-    if move_masks == "epipolar":
-        from .move_seg import epipolar_move_mask
-        for i in range(m):
-            ex_f[i] = epipolar_move_mask(f_dev[i])["open"] != 0
-    else:
-        for i, path in enumerate(p["move"][:m]):
-            mask = read_mask(path)
-            if tuple(mask.shape) == shape:
-                ex_f[i] = mask.to(dev)
-    if occ_masks == "flow" and b_dev is not None:
-        from .occlusion import flow_occlusion
-        occ = flow_occlusion(f_dev, b_dev)
-        ex_f |= occ["occ"] != 0
-        ex_b |= occ["occ_bwd"] != 0
-    elif occ_masks == "files":
-        for i, path in enumerate(p["occ"][:m]):
-            mask = read_mask(path)
-            if tuple(mask.shape) == shape:
-                ex_b[i] = mask.to(dev)
-    res = clip_depth_camera(f_dev, b_dev, focal=focal, exclude_fwd=ex_f, exclude_bwd=ex_b, warn=False)
-    warn_unreliable(res["unreliable"][:n])                       # (a flow into an image behind the slice adds a frame)
-    depth = res["depth"][:n].cpu().numpy()
-    poses = res["extr"][:n].cpu().numpy()
-    return [np.ascontiguousarray(d) for d in depth], float(res["focal"]), list(res["pp"]), poses
-
-
-def _load_frames_host(p, flow_src, bwd_src, focal, pp, poses, resize, depth_offset, move_masks, occ_masks, blur):
-    frames = []
-    for i, ip in enumerate(p["img"]):
-        fr = dict(image=image_path_to_tensor(ip, resize, blur), focal=focal, pp=pp, name=_frame_name(ip))
-        fr["depth"] = read_depth(p["depth"][i], resize, depth_offset=depth_offset).unsqueeze(-1)
-        H, W = fr["image"].shape[:2]
-        from_file = move_masks == "files" and i < len(p["move"])
-        fr["move_mask"] = read_mask(p["move"][i], resize) if from_file else torch.zeros(H, W, dtype=torch.bool)
-        fr["flow"] = _flow_to_tensor(flow_src[i].read(), resize, blur) if i < len(flow_src) else torch.zeros(H, W, 2)
-        if occ_masks == "files" and i >= 1 and i - 1 < len(p["occ"]):
-            fr["occ_mask"] = image_path_to_tensor(p["occ"][i - 1], resize, blur)
-        if i < len(poses):
-            fr["extr"] = torch.tensor(poses[i], dtype=torch.float32)
-        frames.append(fr)
+    estimate = depth_camera == "estimate"
+    if estimate and n < 1:
+        raise ValueError("load_sequence: depth_camera=\"estimate\" needs at least one frame")
+    if estimate and (m < max(n - 1, 1) or any(f is None for f in fwd)):
+        raise ValueError(f"load_sequence: depth_camera=\"estimate\" needs a forward flow between the {n} frames, found {m}")
+    # the frames need the occlusion of the pairs 0 .. n - 2.  The geometry takes every pair there is (a flow into an image
+    # behind the slice adds one), and the backward flows only if each of them has one
+    both = estimate and len(bwd) >= m and all(b is not None for b in bwd[:m])
+    frames_reach = max(n - 1, 0)
+    occ, checked, occ_files = [], None, []
     if occ_masks == "flow":
-        from .occlusion import clip_occ_masks
-        n_pairs = min(len(frames) - 1, len(flow_src), len(bwd_src))
-        # (the reference resizes a flow without rescaling its values: the check must not see fr["flow"] of a resized clip)
-        native = resize is None and not blur
-        fwd = [frames[i]["flow"] if native else _flow_to_tensor(flow_src[i].read()) for i in range(n_pairs)]
-        bwd = [_flow_to_tensor(bwd_src[i].read()) for i in range(n_pairs)]
-        clip_occ_masks(frames, bwd, fwd_flows=fwd, resize=resize)
-        if blur:                                   # (no frame had a mask before: the files are ignored)
-            for fr in frames:
-                if "occ_mask" in fr:
-                    fr["occ_mask"] = _blur_chw(fr["occ_mask"].permute(2, 0, 1), True).permute(1, 2, 0)
-    return frames
+        # the check sees the flows at their NATIVE resolution (resizing a flow does not rescale its values)
+        from .occlusion import flow_occlusion
+        idx = [i for i in range(min(m if both else frames_reach, m, len(bwd))) if fwd[i] is not None and bwd[i] is not None]
+        if idx:
+            checked = flow_occlusion(_stack([fwd[i] for i in idx], dev), _stack([bwd[i] for i in idx], dev))
+            masks = (checked["occ_bwd"] != 0).to(torch.uint8).unsqueeze(-1)
+            occ = [None] * (idx[-1] + 1)
+            for j, i in enumerate(idx):
+                occ[i] = (masks[j], 1.0)
+    else:
+        occ_files = [_open_image(f) for f in p["occ"][:m if estimate else frames_reach]]
+        occ = [_image_array(a) for a in occ_files]
+    move = [None] * n
+    if move_masks == "files":
+        move = [_decode_mask(p["move"][i]) if i < len(p["move"]) else None for i in range(n)]
+    if estimate:
+        f_dev, b_dev = _stack(fwd, dev), _stack(bwd[:m], dev) if both else None
+        ex_f, ex_b = _exclusions(f_dev, move[:m], [_mask_array(a) for a in occ_files], checked if both else None,
+                                 move_masks == "epipolar")
+        from .sfm import clip_depth_camera, warn_unreliable
+        res = clip_depth_camera(f_dev, b_dev, focal=focal, exclude_fwd=ex_f, exclude_bwd=ex_b, warn=False)
+        warn_unreliable(res["unreliable"][:n])
+        depth, focal, pp, poses = list(res["depth"][:n]), float(res["focal"]), list(res["pp"]), res["extr"][:n].cpu().numpy()
+    else:
+        depth = [np.load(p["depth"][i]) for i in range(n)]
+        focal, pp, poses = read_camera(p["camera"])
+    return _Clip([_frame_name(ip) for ip in p["img"]], [decoded[i] for i in mine], fwd, bwd, depth, move, occ, focal, pp, poses)
 
 
-# ---- the device path: decode on the host, prepare whole stacks on the device
+def _exclusions(fwd, move, occ, checked, epipolar):
+    """(exclude_fwd, exclude_bwd) (m, h, w) bool for gflow_amd.sfm.clip_depth_camera: the move masks keep pixels of the forward
+    grids out of the geometry, the occlusion masks (occ_bwd) pixels of the backward grids and, from a check, (occ) of the
+    forward ones.  ``move`` / ``occ``: the mask files' arrays, used where one has the flows' shape; ``checked``: the
+    flow_occlusion result of all m pairs; ``epipolar``: the move masks are computed from the native flows instead."""
+    shape, dev = tuple(fwd.shape[1:3]), fwd.device
+    ex_f, ex_b = (torch.zeros(tuple(fwd.shape[:3]), dtype=torch.bool, device=dev) for _ in range(2))
+    if epipolar:
+        from .move_seg import epipolar_move_mask
+        for i in range(len(fwd)):
+            ex_f[i] = epipolar_move_mask(fwd[i])["open"] != 0
+    for ex, arrays in ((ex_f, move), (ex_b, occ)):
+        for i, a in enumerate(arrays):
+            mask = None if a is None else _mask_to_tensor(a)
+            if mask is not None and tuple(mask.shape) == shape:
+                ex[i] = mask.to(dev)
+    if checked is not None:
+        ex_f |= checked["occ"] != 0
+        ex_b |= checked["occ_bwd"] != 0
+    return ex_f, ex_b
+
+
+def _stack(arrays, device):
+    """one (T, ...) tensor of arrays of one shape, with ONE upload to ``device`` (None: it stays on the host); tensors that
+    are on the device already are not uploaded again"""
+    if any(torch.is_tensor(a) for a in arrays):
+        return torch.stack([a if torch.is_tensor(a) else torch.from_numpy(np.array(a)).to(device) for a in arrays])
+    stack = torch.from_numpy(np.stack(arrays))
+    return stack if device is None else stack.to(device)
+
+
+def _kind(a):
+    return tuple(a.shape), "|u1" if a.dtype == torch.uint8 else str(a.dtype) if torch.is_tensor(a) else a.dtype.str
+
+
+def _image_stack(images, dev, device_decode):
+    """the (T, H, W, 3) stack gflow_amd.optflow.clip_flows takes, from decoded images: uint8, or float in [0, 1]"""
+    arrays = [a if torch.is_tensor(a) or a.dtype == np.uint8 else (a / np.float32(div)).astype(np.float32) for a, div in images]
+    kinds = {_kind(a) for a in arrays}
+    if device_decode and (len(kinds) != 1 or _kind(arrays[0])[1] != "|u1"):
+        raise ValueError("load_sequence: flows=\"estimate\" from device-decoded images needs 8-bit images of one shape")
+    if len(kinds) != 1:
+        raise ValueError("optflow: the images of a sequence must have one shape and one bit depth")
+    stack = _stack(arrays, dev)
+    return stack.expand(-1, -1, -1, 3).contiguous() if stack.shape[-1] == 1 else stack
+
+
+def _open_image(path):
+    from PIL import Image
+    return np.asarray(Image.open(path))
+
+
+def _mask_array(mask):
+    """(H, W, C) uint8 or float32 as read_mask takes a file's array"""
+    if mask.ndim == 2:
+        mask = mask[..., None]
+    elif mask.ndim != 3:
+        raise ValueError("The mask should be 2D or 3D")
+    return np.ascontiguousarray(mask if mask.dtype == np.uint8 else mask.astype(np.float32))
+
+
+def _image_array(img):
+    """(array (H, W, C <= 3) uint8 or float32, the divisor that makes it [0, 1]) as image_path_to_tensor takes a file's array"""
+    return np.ascontiguousarray(_mask_array(img)[..., :3]), _image_div(img.dtype)
+
+
 def _decode_image(path):
     """(array (H, W, C <= 3) uint8 or float32, the divisor that makes it [0, 1]) as image_path_to_tensor reads the file"""
-    from PIL import Image
-    img = np.asarray(Image.open(path))
-    div = _image_div(img.dtype)
-    if img.ndim == 2:
-        img = img[..., None]
-    img = img[..., :3]
-    return np.ascontiguousarray(img if img.dtype == np.uint8 else img.astype(np.float32)), div
+    return _image_array(_open_image(path))
+
+
+def _decode_mask(path):
+    """(H, W, C) uint8 or float32 as read_mask reads the file"""
+    return _mask_array(_open_image(path))
 
 
 def _decode_images(paths, decode, device):
     """[(array or device tensor (H, W, C <= 3), divisor)] of a clip's images, as _decode_image gives them.  A video file's
     frames, and with decode="device" the JPEG files the device decoder takes, come from gflow_amd.video.decode_jpeg as
     device tensors (one call per shape); every other file from PIL, with one warning that counts them."""
-    from .video import decode_jpeg, parse_jpeg, read_avi
+    from .video import decode_jpeg, parse_jpeg
     out = [None] * len(paths)
-    groups, avi, on_host = {}, {}, 0
+    groups, on_host = {}, 0
     for i, ip in enumerate(paths):
         if isinstance(ip, AviFrame):
-            if ip.path not in avi:
-                avi[ip.path] = read_avi(ip.path)["frames"]
-            data, name = avi[ip.path][ip.index], repr(ip)
+            data, name = ip.data, repr(ip)
         elif decode == "device" and str(ip).lower().endswith((".jpg", ".jpeg")):
             with open(ip, "rb") as f:
                 data, name = f.read(), str(ip)
@@ -438,90 +464,115 @@ def _decode_images(paths, decode, device):
     return out
 
 
-def _decode_mask(path):
-    """(H, W, C) uint8 or float32 as read_mask reads the file"""
-    from PIL import Image
-    mask = np.asarray(Image.open(path))
-    if mask.ndim == 2:
-        mask = mask[..., None]
-    elif mask.ndim != 3:
-        raise ValueError("The mask should be 2D or 3D")
-    return np.ascontiguousarray(mask if mask.dtype == np.uint8 else mask.astype(np.float32))
+# ---- 2. prepare: native arrays -> the frames' tensors (None passes through); a host and a device preparer, one interface
+def _np(a):
+    return a.cpu().numpy() if torch.is_tensor(a) else a
 
 
-def _prep_stacks(arrays, device, resize, keys=None, **kw):
-    """prep_frames over a list of (H, W, C) arrays (None: no file): the arrays of one shape and dtype (and ``keys`` entry,
-    the divisor) go up as ONE stack and come back as views of one result.  Returns the list of device tensors."""
-    from .prep import prep_frames
-    out = [None] * len(arrays)
-    groups = {}
-    for i, a in enumerate(arrays):
-        if a is not None:
-            kind = "|u1" if a.dtype == torch.uint8 else str(a.dtype) if torch.is_tensor(a) else a.dtype.str
-            groups.setdefault((tuple(a.shape), kind, None if keys is None else keys[i]), []).append(i)
-    for (_, _, key), idx in groups.items():
-        if any(torch.is_tensor(arrays[i]) for i in idx):       # (decoded on the device: already there)
-            stack = torch.stack([arrays[i] if torch.is_tensor(arrays[i]) else torch.from_numpy(np.array(arrays[i])).to(device)
-                                 for i in idx])
-        else:
-            stack = torch.from_numpy(np.stack([arrays[i] for i in idx])).to(device)
-        res = prep_frames(stack, resize, **(kw if key is None else dict(kw, div=key)))
-        for j, i in enumerate(idx):
-            out[i] = res[j]
-    return out
+def _mask_to_tensor(mask, resize=None):
+    """what read_mask makes of a file's (H, W, C) array"""
+    t = _resize_chw(torch.from_numpy(np.array(mask)).float().permute(2, 0, 1), resize)
+    if t.shape[-1] > 1:
+        t = t.sum(dim=0)
+    return t.squeeze() > 0
 
 
-def _load_frames_device(p, flow_src, bwd_src, focal, pp, poses, resize, depth_offset, move_masks, occ_masks, blur, device,
-                        decode="host"):
-    if device.type != "cuda":
-        raise RuntimeError("gflow_amd.io: load_sequence(device=...) needs a HIP (cuda) device; there is no CPU fallback")
-    n = len(p["img"])
-    images = _decode_images(p["img"], decode, device)
-    image = _prep_stacks([a for a, _ in images], device, resize, keys=[d for _, d in images], blur=blur)
-    depth = _prep_stacks([np.asarray(_depth_array(p["depth"][i]), dtype=np.float32)[..., None] for i in range(n)], device, resize,
-                         mul=1.0, add=depth_offset)
-    flows = [flow_src[i].read() if i < len(flow_src) else None for i in range(n)]
-    flow = _prep_stacks(flows, device, resize, blur=blur)
-    move = [None] * n
-    if move_masks == "files":
-        move = _prep_stacks([_decode_mask(p["move"][i]) if i < len(p["move"]) else None for i in range(n)], device, resize,
-                            as_mask=True)
-    occ = [None] * n
-    if occ_masks == "files":
-        files = [_decode_image(p["occ"][i - 1]) if 1 <= i <= len(p["occ"]) else (None, None) for i in range(n)]
-        occ = _prep_stacks([a for a, _ in files], device, resize, keys=[d for _, d in files], blur=blur)
-    else:
-        from .occlusion import flow_occlusion
+class _HostPrep:
+    """the readers' torch code on one decoded array at a time -> host tensors"""
+
+    def __init__(self, resize, blur, depth_offset):
+        self.resize, self.blur, self.depth_offset = resize, blur, depth_offset
+
+    def _each(self, fn, arrays):
+        return [None if a is None else fn(a) for a in arrays]
+
+    def image(self, images):
+        to_chw = lambda a, div: torch.from_numpy(np.array(_np(a))).permute(2, 0, 1).float() / div
+        return self._each(lambda x: _blur_chw(_resize_chw(to_chw(*x), self.resize), self.blur).permute(1, 2, 0), images)
+
+    occ_mask = image
+
+    def flow(self, flows):
+        return self._each(lambda a: _flow_to_tensor(_np(a), self.resize, self.blur), flows)
+
+    def depth(self, depths):
+        to_chw = lambda a: torch.tensor(_np(a), dtype=torch.float32).unsqueeze(0)
+        return self._each(lambda a: (_resize_chw(to_chw(a), self.resize).squeeze(0) + self.depth_offset).unsqueeze(-1), depths)
+
+    def move_mask(self, masks):
+        return self._each(lambda a: _mask_to_tensor(a, self.resize), masks)
+
+    def occ_counts(self, masks):
+        return [None] * len(masks)                 # (fit_video.upload_clip counts them when it uploads the frames)
+
+
+class _DevicePrep:
+    """whole stacks on the device (gflow_amd.prep.prep_frames) -> device tensors of the host preparer's shapes and dtypes"""
+
+    def __init__(self, device, resize, blur, depth_offset):
+        self.device, self.resize, self.blur, self.depth_offset = device, resize, blur, depth_offset
+
+    def _stacks(self, arrays, keys=None, **kw):
+        """prep_frames over a list of (H, W, C) arrays: those of one shape and dtype (and ``keys`` entry, the divisor) go up
+        as ONE stack and come back as views of one result"""
         from .prep import prep_frames
-        # the check sees the flows at their native resolution (resizing a flow does not rescale its values)
-        bwd = [bwd_src[i].read() for i in range(min(n - 1, len(flow_src), len(bwd_src)))]
-        pairs = [i for i, b in enumerate(bwd) if b is not None and flows[i] is not None]
-        if pairs:
-            res = flow_occlusion(torch.from_numpy(np.stack([flows[i] for i in pairs])).to(device),
-                                 torch.from_numpy(np.stack([bwd[i] for i in pairs])).to(device))["occ_bwd"]
-            masks = prep_frames((res != 0).to(torch.uint8).unsqueeze(-1).contiguous(), resize, blur=blur)
-            for j, i in enumerate(pairs):
-                occ[i + 1] = masks[j]
+        out = [None] * len(arrays)
+        groups = {}
+        for i, a in enumerate(arrays):
+            if a is not None:
+                groups.setdefault(_kind(a) + (None if keys is None else keys[i],), []).append(i)
+        for (_, _, key), idx in groups.items():
+            res = prep_frames(_stack([arrays[i] for i in idx], self.device), self.resize,
+                              **(kw if key is None else dict(kw, div=key)))
+            for j, i in enumerate(idx):
+                out[i] = res[j]
+        return out
+
+    def image(self, images):
+        split = lambda k: [None if x is None else x[k] for x in images]
+        return self._stacks(split(0), keys=split(1), blur=self.blur)
+
+    occ_mask = image
+
+    def flow(self, flows):
+        return self._stacks(flows, blur=self.blur)
+
+    def depth(self, depths):
+        hw1 = lambda a: a.unsqueeze(-1) if torch.is_tensor(a) else np.asarray(a, dtype=np.float32)[..., None]
+        return self._stacks([hw1(a) for a in depths], mul=1.0, add=self.depth_offset)
+
+    def move_mask(self, masks):
+        return self._stacks(masks, as_mask=True)
+
+    def occ_counts(self, masks):
+        """what upload_clip counts on the host, one frame at a time: here one read-back for the clip"""
+        sums = [(m[..., 0] > 0).sum() for m in masks if m is not None]
+        counts = iter(torch.stack(sums).cpu().tolist() if sums else [])
+        return [None if m is None else int(next(counts)) for m in masks]
+
+
+# ---- 3. assemble: the per-frame rules, here and only here
+def _assemble(clip, prep):
+    n = len(clip.names)
+    image, depth = prep.image(clip.images), prep.depth(clip.depth)
+    flow = prep.flow([clip.fwd[i] if i < len(clip.fwd) else None for i in range(n)])
+    move = prep.move_mask(clip.move)
+    occ = prep.occ_mask([clip.occ[i - 1] if 1 <= i <= len(clip.occ) else None for i in range(n)])     # frame i: pair i - 1
+    counts = prep.occ_counts(occ)
     frames = []
-    for i, ip in enumerate(p["img"]):
-        fr = dict(image=image[i], focal=focal, pp=pp, name=_frame_name(ip), depth=depth[i])
+    for i in range(n):
+        fr = dict(image=image[i], focal=clip.focal, pp=clip.pp, name=clip.names[i], depth=depth[i])
         H, W = fr["image"].shape[:2]
-        fr["move_mask"] = move[i] if move[i] is not None else torch.zeros(H, W, dtype=torch.bool, device=device)
-        if i < len(flow_src):
-            fr["flow"] = flow[i]                   # (None for a file with a bad magic number, as read_flow gives)
-        else:
-            fr["flow"] = torch.zeros(H, W, 2, device=device)
+        fr["move_mask"] = move[i] if move[i] is not None else fr["image"].new_zeros((H, W), dtype=torch.bool)   # (no file)
+        # a pair without a flow: zeros; a file with a bad magic number: None, as read_flow gives
+        fr["flow"] = flow[i] if i < len(clip.fwd) else fr["image"].new_zeros((H, W, 2))
         if occ[i] is not None:
             fr["occ_mask"] = occ[i]
-        if i < len(poses):
-            fr["extr"] = torch.tensor(poses[i], dtype=torch.float32)
+        if i < len(clip.poses):
+            fr["extr"] = torch.tensor(clip.poses[i], dtype=torch.float32)                           # (stays on the host)
+        if counts[i] is not None:
+            fr["occ_count"] = counts[i]
         frames.append(fr)
-    # what upload_clip counts on the host, one frame at a time: here one read-back for the clip
-    with_occ = [fr for fr in frames if "occ_mask" in fr]
-    if with_occ:
-        counts = torch.stack([(fr["occ_mask"][..., 0] > 0).sum() for fr in with_occ]).cpu()
-        for fr, c in zip(with_occ, counts.tolist()):
-            fr["occ_count"] = int(c)
     return frames
 
 
