@@ -58,13 +58,8 @@ __global__ void __launch_bounds__(1024) bin_scan_kernel(int32_t* __restrict__ da
     for (int base = 0; base < T; base += 1024) {
         const int i = base + tid;
         const int v = (i < T) ? data[i] : 0;
-        // wave inclusive scan
-        int s = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int n = __shfl_up(s, off);
-            if (lane >= off) s += n;
-        }
+        // (the chunk loop's own barriers, around the carry, also guard wsum: block_scan_excl would add two per chunk)
+        const int s = wave_scan_incl(v);
         if (lane == 63) wsum[wid] = s;
         __syncthreads();
         int wprefix = 0;

@@ -136,9 +136,7 @@ __global__ void __launch_bounds__(256) blend_bwd_kernel(const float* __restrict_
     if (tid == 0) s_max_last = 0;
     __syncthreads();
     {
-        int m = last;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) m = max(m, __shfl_xor(m, off));
+        const int m = wave_max(last);
         if (lane == 0) atomicMax(&s_max_last, m);
     }
     __syncthreads();

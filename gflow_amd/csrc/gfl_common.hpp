@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/gflow_hip.h"
 
 namespace gfl {
@@ -219,6 +221,130 @@ __device__ __forceinline__ int reduce_scatter_component(int lane) {
     if constexpr (N == 7) return sel == 0 ? 2 * odd + hi : (sel == 1 ? (odd == 0 ? 4 + hi : (hi == 0 ? 6 : -1)) : -1);
     return sel == 0 ? 2 * odd + hi : ((sel == 1 && odd == 0) ? 4 + hi : -1);
 }
+
+// ---- wave64 scans, integer reductions and lane exchange: the ONE copy every kernel uses ----
+struct OpAdd {
+    template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return a + b; }
+};
+// inclusive scan over the wave: lane l ends with op over lanes 0 .. l (six __shfl_up steps)
+template <typename T, typename Op = OpAdd>
+__device__ __forceinline__ T wave_scan_incl(T v, Op op = Op{}) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const T n = __shfl_up(v, off);
+        if (lane >= off) v = op(v, n);
+    }
+    return v;
+}
+// the value of lane - 1 (lane 0: its own)
+template <typename T>
+__device__ __forceinline__ T wave_prev_lane(T v) { return __shfl_up(v, 1); }
+
+// max / min / sum of one int per lane, to every lane (xor butterfly, off = 32 .. 1)
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = max(v, __shfl_xor(v, off));
+    return v;
+}
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = min(v, __shfl_xor(v, off));
+    return v;
+}
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// Exclusive scan of one value per thread over the workgroup of BLOCK threads: returns the sum of the threads in front of
+// this one; `total` = the sum over all threads, to every thread.  wsum: BLOCK / 64 values of LDS.  Whole workgroup.
+// Barrier contract: barrier, wave totals written, barrier, totals read -- so
+//   1. it may be called back to back on the same wsum (the leading barrier ends the previous call's reads), and
+//   2. LDS (and global) writes the caller made before the call are visible to the whole workgroup when it returns.
+// There is NO barrier behind the last read of wsum: a caller that writes wsum itself puts one first.
+// int: inclusive - v.  double: the inclusive value of the lane before (v subtracted again would not be exact); the fold
+// order -- lanes of a wave by the shuffle ladder, then the waves in wave order -- is part of gfl_scan_f64's bits.
+template <int BLOCK, typename T>
+__device__ __forceinline__ T block_scan_excl(T v, T* wsum, T& total) {
+    static_assert(BLOCK % 64 == 0, "whole waves");
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const T sc = wave_scan_incl(v);
+    __syncthreads();
+    if (lane == 63) wsum[wid] = sc;
+    __syncthreads();
+    T wprefix = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < BLOCK / 64; ++w) {
+        const T x = wsum[w];
+        if (w < wid) wprefix += x;
+        total += x;
+    }
+    if constexpr (std::is_floating_point<T>::value) {
+        const T prev = wave_prev_lane(sc);
+        return wprefix + (lane > 0 ? prev : T(0));
+    } else {
+        return wprefix + sc - v;
+    }
+}
+
+// Value of lane (lane ^ D) for a wave-uniform D in {1, 2, 4, 8, 16, 32}, on the VALU only: DPP
+// quad permutes / row shifts / row rotate inside a 16-lane row, v_permlane16_swap / v_permlane32_swap
+// (gfx950) across rows.  __shfl_xor goes through ds_bpermute (address VGPR + an LDS-pipe round trip
+// per 32 bits); with ~40 dependent exchange steps per tile the sort network cost 14 of the
+// launch's 24 us that way.
+template <int D>
+__device__ __forceinline__ unsigned xor_lane(unsigned v, int lane) {
+    static_assert(D == 1 || D == 2 || D == 4 || D == 8 || D == 16 || D == 32, "a power of two below the wave size");
+    const int x = (int)v;
+    if constexpr (D == 1) return (unsigned)__builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, true);   // quad_perm [1,0,3,2]
+    else if constexpr (D == 2) return (unsigned)__builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, true);   // quad_perm [2,3,0,1]
+    else if constexpr (D == 4) {
+        int t = __builtin_amdgcn_update_dpp(x, x, 0x104, 0xF, 0x5, false);               // row_shl:4 -> banks 0, 2
+        t = __builtin_amdgcn_update_dpp(t, x, 0x114, 0xF, 0xA, false);                   // row_shr:4 -> banks 1, 3
+        return (unsigned)t;
+    } else if constexpr (D == 8) return (unsigned)__builtin_amdgcn_update_dpp(0, x, 0x128, 0xF, 0xF, true);   // row_ror:8
+    else if constexpr (D == 16) {
+        float a = __builtin_bit_cast(float, v), b = a;
+        permlane16_swap(a, b);               // a = rows {0,0,2,2} of v, b = rows {1,1,3,3}
+        return __builtin_bit_cast(unsigned, (lane & 16) ? a : b);
+    } else {
+        float a = __builtin_bit_cast(float, v), b = a;
+        permlane32_swap(a, b);               // a = {lo, lo}, b = {hi, hi}
+        return __builtin_bit_cast(unsigned, (lane & 32) ? a : b);
+    }
+}
+
+// floats as unsigned keys of the same order (atomicMin / atomicMax on floats of either sign), and back
+__device__ __forceinline__ unsigned f2ord(float f) {
+    const unsigned b = __float_as_uint(f);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float ord2f(unsigned k) {
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+// min of lo and max of hi over the wave, to every lane
+__device__ __forceinline__ void wave_range_ord(unsigned& lo, unsigned& hi) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        lo = min(lo, (unsigned)__shfl_xor((int)lo, off));
+        hi = max(hi, (unsigned)__shfl_xor((int)hi, off));
+    }
+}
+// The range of apply_float_colormap(non_zero=True) (color.py:28-31) as keys: lo = the smallest key of a non-zero value, hi
+// = the largest key of any.  Start from RangeOrd{}, add() every value of the lane, then wave(): the range over the wave, to
+// every lane; lane 0 of every wave folds it into global memory with the caller's own atomics.
+struct RangeOrd {
+    unsigned lo = 0xffffffffu, hi = 0u;
+    __device__ __forceinline__ void add(float x) {
+        const unsigned k = f2ord(x);
+        if (x != 0.f) lo = min(lo, k);
+        hi = max(hi, k);
+    }
+    __device__ __forceinline__ void wave() { wave_range_ord(lo, hi); }
+};
 
 
 // Deterministic block-level reduction of NV values -> one partial row per block.

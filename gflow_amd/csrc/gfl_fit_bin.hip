@@ -373,12 +373,8 @@ __global__ void __launch_bounds__(BIN_BLOCK) fused_scatter_kernel(const float* _
             for (int k = 0; k < per; ++k)
                 if (t0 + k < T) local += tile_counts[t0 + k];
         }
-        int sc = local;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int n = __shfl_up(sc, off);
-            if (lane >= off) sc += n;
-        }
+        // (one barrier, not block_scan_excl's two: nothing has touched wsum before)
+        const int sc = wave_scan_incl(local);
         if (lane == 63) wsum[wid] = sc;
         GFL_PHASE(2, 1);
         __syncthreads();

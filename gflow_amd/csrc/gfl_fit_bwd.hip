@@ -163,9 +163,7 @@ __global__ void __launch_bounds__(256, 8) fused_blend_bwd_kernel(const float* __
     __syncthreads();
     const unsigned long long alive0 = __ballot(inside);
     const int px0w = tx * GFL_TILE + (blk & 1) * 8, py0w = ty * GFL_TILE + (blk >> 1) * 8;
-    int wave_last = last;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) wave_last = max(wave_last, __shfl_xor(wave_last, off));
+    const int wave_last = wave_max(last);
     if (lane == 0) atomicMax(&s_max_last, wave_last);
     __syncthreads();
     const int depth_n = min(total, (int)s_max_last);

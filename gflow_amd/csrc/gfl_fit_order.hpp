@@ -62,17 +62,12 @@ __device__ void build_sort_order(const int32_t* __restrict__ tile_counts, int T,
         for (int k = 0; k < PER_MAX; ++k)
             if (k < per && t0 + k < T) ro.fill[t0 + k] = 0;
         // (mean list length for the heavy-tile threshold: from the counts, not from the regions)
-        int cs = local_c;
-#pragma unroll
-        for (int off = 32; off; off >>= 1) cs += __shfl_xor(cs, off);
+        const int cs = wave_sum_int(local_c);
         if (lane == 0) csum[wid] = cs;
     }
-    int sc = local;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int n = __shfl_up(sc, off);
-        if (lane >= off) sc += n;
-    }
+    // (the two scans below keep their own wave totals and ONE barrier each, not block_scan_excl's two: wsum and hsum are
+    //  each written once per call here)
+    const int sc = wave_scan_incl(local);
     if (lane == 63) wsum[wid] = sc;
     __syncthreads();
     int run = sc - local, total = 0;
@@ -93,12 +88,7 @@ __device__ void build_sort_order(const int32_t* __restrict__ tile_counts, int T,
     int lh = 0;
 #pragma unroll
     for (int k = 0; k < PER_MAX; ++k) lh += cnt[k] > thr ? 1 : 0;
-    int hs = lh;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int n = __shfl_up(hs, off);
-        if (lane >= off) hs += n;
-    }
+    const int hs = wave_scan_incl(lh);
     if (lane == 63) hsum[wid] = hs;
     __syncthreads();
     int H = hs - lh;                                     // heavy tiles before this lane's first tile

@@ -43,25 +43,15 @@ __global__ void __launch_bounds__(256) center_blend_kernel(const float* __restri
 }
 
 // min over the non-zero / max over all depths of the records, as ordered-uint keys (the range of
-// apply_float_colormap(non_zero=True), color.py:28-31; the encoding of cmap_range_kernel of gfl_loss.hip, the minimum
+// apply_float_colormap(non_zero=True), color.py:28-31; RangeOrd, as cmap_range_kernel of gfl_loss.hip, the minimum
 // COMPLEMENTED so that both words are initialised by the one memset that also clears the snapshot's pull counters)
 __global__ void __launch_bounds__(256) rec_depth_range_kernel(const float* __restrict__ rec, int N, unsigned* __restrict__ mm) {
-    unsigned lo = 0xffffffffu, hi = 0u;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x) {
-        const float x = rec[(size_t)i * REC + 9];
-        const unsigned b = __float_as_uint(x);
-        const unsigned k = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-        if (x != 0.f) lo = min(lo, k);
-        hi = max(hi, k);
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        lo = min(lo, (unsigned)__shfl_xor((int)lo, off));
-        hi = max(hi, (unsigned)__shfl_xor((int)hi, off));
-    }
+    RangeOrd r;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x) r.add(rec[(size_t)i * REC + 9]);
+    r.wave();
     if ((threadIdx.x & 63) == 0) {
-        atomicMax(&mm[0], ~lo);
-        atomicMax(&mm[1], hi);
+        atomicMax(&mm[0], ~r.lo);
+        atomicMax(&mm[1], r.hi);
     }
 }
 

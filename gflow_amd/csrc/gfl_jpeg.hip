@@ -138,28 +138,6 @@ __device__ void jpeg_block_symbols(const int16_t* zz, int dc_diff, const uint32_
     if (run) jpeg_put(s, ac_tab[0x00], 0, 0);                                // EOB
 }
 
-// exclusive prefix of v over the workgroup, `total` to everyone; tot: JPEG_BLOCK / WAVE ints of LDS
-__device__ __forceinline__ int jpeg_block_scan(int v, int* tot, int& total) {
-    const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        const int o = __shfl_up(inc, d);
-        if (lane >= d) inc += o;
-    }
-    if (lane == WAVE - 1) tot[wid] = inc;
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < JPEG_BLOCK / WAVE; ++w) {
-        if (w < wid) base += tot[w];
-        total += tot[w];
-    }
-    __syncthreads();
-    return base + inc - v;
-}
-
 // ---- the LDS of a workgroup, by component count
 template <int C>
 struct JpegLds {
@@ -258,7 +236,7 @@ __device__ JpegCoded jpeg_interval(JpegLds<C>& L, const uint8_t* __restrict__ im
         jpeg_block_symbols(zz, dc_diff, dc_tab, ac_tab, cnt);
     }
     int total_bits;
-    const int at = jpeg_block_scan(cnt.bits, L.tot, total_bits);            // (its barriers also cover the zeroing)
+    const int at = block_scan_excl<JPEG_BLOCK>(cnt.bits, L.tot, total_bits);            // (its barriers also cover the zeroing)
     if (tid < nb) {
         BitWriter wr(L.bits, at);
         jpeg_block_symbols(zz, dc_diff, dc_tab, ac_tab, wr);
@@ -284,7 +262,7 @@ __device__ JpegCoded jpeg_interval(JpegLds<C>& L, const uint8_t* __restrict__ im
     }
     __syncthreads();
     const int a = 2 * tid < nseg ? L.seg[2 * tid] : 0, b2 = 2 * tid + 1 < nseg ? L.seg[2 * tid + 1] : 0;
-    const int ex = jpeg_block_scan(a + b2, L.tot, out.nff);
+    const int ex = block_scan_excl<JPEG_BLOCK>(a + b2, L.tot, out.nff);
     L.seg[2 * tid] = ex;
     L.seg[2 * tid + 1] = ex + a;
     __syncthreads();
@@ -336,7 +314,7 @@ __global__ void __launch_bounds__(JPEG_BLOCK)
     for (int base = 0; base < n; base += JPEG_BLOCK) {
         const int i = base + threadIdx.x;
         int total;
-        const int ex = jpeg_block_scan(i < n ? sizes[i] : 0, tot, total);
+        const int ex = block_scan_excl<JPEG_BLOCK>(i < n ? sizes[i] : 0, tot, total);
         if (i < n) {
             offsets[i] = carry + ex;
             if (i % ni == 0) frame_offsets[i / ni] = carry + ex;

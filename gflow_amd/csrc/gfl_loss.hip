@@ -5,30 +5,13 @@
 namespace gfl {
 
 // ------------------------------------------------------------------ colour map
-__device__ __forceinline__ unsigned f2ord(float f) {
-    const unsigned b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(unsigned k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
 __global__ void __launch_bounds__(256) cmap_range_kernel(const float* __restrict__ v, int N, unsigned* __restrict__ mm) {
-    unsigned lo = 0xffffffffu, hi = 0u;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x) {
-        const float x = v[i];
-        const unsigned k = f2ord(x);
-        if (x != 0.f) lo = min(lo, k);
-        hi = max(hi, k);
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        lo = min(lo, (unsigned)__shfl_xor((int)lo, off));
-        hi = max(hi, (unsigned)__shfl_xor((int)hi, off));
-    }
+    RangeOrd r;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x) r.add(v[i]);
+    r.wave();
     if ((threadIdx.x & 63) == 0) {
-        atomicMin(&mm[0], lo);
-        atomicMax(&mm[1], hi);
+        atomicMin(&mm[0], r.lo);
+        atomicMax(&mm[1], r.hi);
     }
 }
 

@@ -151,17 +151,13 @@ __global__ void __launch_bounds__(RB_SCAN) rb_scan_kernel(int32_t* __restrict__ 
     if (tid == 0) s_cut = 0;
     int local = 0;
     for (int i = i0; i < i1; ++i) local = rb_sat_add(local, vt_count[i]);
-    int sc = local;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int n = __shfl_up(sc, off);
-        if (lane >= off) sc = rb_sat_add(sc, n);
-    }
+    // (saturating: the ladder of wave_scan_incl with rb_sat_add; the wave totals are folded with it too, so not block_scan_excl)
+    const int sc = wave_scan_incl(local, [](int a, int b) { return rb_sat_add(a, b); });
     if (lane == 63) s_wave[wid] = sc;
     __syncthreads();
     int wprefix = 0;
     for (int w = 0; w < wid; ++w) wprefix = rb_sat_add(wprefix, s_wave[w]);
-    const int prev = __shfl_up(sc, 1);
+    const int prev = wave_prev_lane(sc);
     const int start = lane == 0 ? wprefix : rb_sat_add(wprefix, prev);
     // the cut: the largest list end that is still <= K_cap (ends do not decrease: this lane's last such end)
     {

@@ -17,31 +17,6 @@ constexpr int SCAN_BLOCK = 256;
 constexpr int SCAN_PER = GFL_SCAN_CHUNK / SCAN_BLOCK;
 static_assert(SCAN_PER * SCAN_BLOCK == GFL_SCAN_CHUNK, "a chunk is SCAN_PER values per lane");
 
-// scan of one double per lane over the workgroup; wsum: SCAN_BLOCK / 64 doubles of LDS.  Returns the sum of the lanes in
-// front of this one; `total` = the workgroup's sum.  Whole workgroup.
-__device__ __forceinline__ double scan_block_excl(double v, double* wsum, double& total) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    double sc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const double n = __shfl_up(sc, off);
-        if (lane >= off) sc += n;
-    }
-    if (lane == 63) wsum[wid] = sc;
-    __syncthreads();
-    double before = 0.0;
-    total = 0.0;
-#pragma unroll
-    for (int w = 0; w < SCAN_BLOCK / 64; ++w) {
-        const double x = wsum[w];
-        if (w < wid) before += x;
-        total += x;
-    }
-    __syncthreads();                 // (wsum is reused by the caller)
-    const double prev = __shfl_up(sc, 1);
-    return before + (lane > 0 ? prev : 0.0);
-}
-
 // this lane's SCAN_PER values of chunk blockIdx.x (zeros behind n) and their running sums
 __device__ __forceinline__ void scan_lane_values(const double* __restrict__ in, int n, double (&v)[SCAN_PER]) {
     const long long base = (long long)blockIdx.x * GFL_SCAN_CHUNK + (long long)threadIdx.x * SCAN_PER;
@@ -57,7 +32,7 @@ __global__ void __launch_bounds__(SCAN_BLOCK) scan_chunk_sums_kernel(const doubl
     double v[SCAN_PER];
     scan_lane_values(in, n, v);
     double total;
-    scan_block_excl(v[SCAN_PER - 1], wsum, total);
+    block_scan_excl<SCAN_BLOCK>(v[SCAN_PER - 1], wsum, total);
     if (threadIdx.x == 0) chunk_sum[blockIdx.x] = total;
 }
 
@@ -68,11 +43,11 @@ __global__ void __launch_bounds__(SCAN_BLOCK) scan_apply_kernel(const double* __
     double front = 0.0;
     for (int c = threadIdx.x; c < (int)blockIdx.x; c += SCAN_BLOCK) front += chunk_sum[c];
     double offset;
-    scan_block_excl(front, wsum, offset);
+    block_scan_excl<SCAN_BLOCK>(front, wsum, offset);
     double v[SCAN_PER];
     scan_lane_values(in, n, v);
     double dummy;
-    const double lane_front = offset + scan_block_excl(v[SCAN_PER - 1], wsum, dummy);
+    const double lane_front = offset + block_scan_excl<SCAN_BLOCK>(v[SCAN_PER - 1], wsum, dummy);
     const long long base = (long long)blockIdx.x * GFL_SCAN_CHUNK + (long long)threadIdx.x * SCAN_PER;
 #pragma unroll
     for (int k = 0; k < SCAN_PER; ++k)

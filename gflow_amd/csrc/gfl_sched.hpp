@@ -113,30 +113,6 @@ __device__ __forceinline__ unsigned plan_blocks(const int (&bw)[4], int (&key)[4
     return plan;
 }
 
-// exclusive scan of one int per thread over the workgroup of BLOCK threads; `total` = sum over all threads
-template <int BLOCK>
-__device__ __forceinline__ int sched_block_scan(int v, int32_t* wsum, int& total) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int sc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int n = __shfl_up(sc, off);
-        if (lane >= off) sc += n;
-    }
-    __syncthreads();
-    if (lane == 63) wsum[wid] = sc;
-    __syncthreads();
-    int wprefix = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < BLOCK / 64; ++w) {
-        const int x = wsum[w];
-        if (w < wid) wprefix += x;
-        total += x;
-    }
-    return wprefix + sc - v;
-}
-
 // exclusive scan over the SCHED_BINS bins in place (BLOCK threads, SCHED_BINS / BLOCK consecutive bins each); returns the total
 template <int BLOCK>
 __device__ __forceinline__ int sched_scan_bins(int32_t* bins, int32_t* wsum) {
@@ -146,7 +122,7 @@ __device__ __forceinline__ int sched_scan_bins(int32_t* bins, int32_t* wsum) {
 #pragma unroll
     for (int k = 0; k < PER; ++k) { v[k] = bins[PER * tid + k]; sum += v[k]; }
     int tot;
-    int run = sched_block_scan<BLOCK>(sum, wsum, tot);
+    int run = block_scan_excl<BLOCK>(sum, wsum, tot);
 #pragma unroll
     for (int k = 0; k < PER; ++k) { bins[PER * tid + k] = run; run += v[k]; }
     return tot;
@@ -191,6 +167,56 @@ struct SchedLds {
     int32_t rank[SCHED_BLOCK];
 };
 
+// ---- the steps both schedulers share (the loops differ: schedule_tiles strides over the tiles, schedule_tiles_xcd gives
+// every thread a contiguous run)
+// first step of a scheduling workgroup of BLOCK threads: empty bins, s_max = 1, pull counters zero, no tile a queue's first.
+// Ends with a barrier.
+template <int BLOCK>
+__device__ __forceinline__ void sched_clear(const Sched& sc, int T, SchedLds& sl) {
+    const int tid = threadIdx.x;
+    if (tid == 0) sl.s_max = 1;
+    for (int b = tid; b < SCHED_BINS; b += BLOCK) sl.bins[b] = 0;
+    for (int c = tid; c < 2 * sc.nq; c += BLOCK) sc.counters[c] = 0;
+    if (sc.first_slot)
+        for (int t = tid; t < T; t += BLOCK) sc.first_slot[t] = -1;
+    __syncthreads();
+}
+// weight of tile t (returned, and left in w16[t]): the units the blend kernel counted on its four blocks in the last
+// iteration, the list length where there is no history; at most SCHED_MAX_WEIGHT.  frac4[t] = the blocks' shares of it,
+// 4 x 8 bits.  The feedback is zeroed: the blend kernel adds this iteration's units.
+__device__ __forceinline__ int sched_tile_weight(int t, const int32_t* __restrict__ tile_counts, const Sched& sc,
+                                                 unsigned short* w16, uint32_t* frac4) {
+    int4* w4 = reinterpret_cast<int4*>(sc.work) + t;
+    const int4 b = *w4;
+    int x = b.x + b.y + b.z + b.w;
+    uint32_t fr = 0x40404040u;       // no history: four equal blocks
+    if (x > 0) {
+        const float inv = 255.f / (float)x;
+        fr = (uint32_t)((float)b.x * inv) | (uint32_t)((float)b.y * inv) << 8 | (uint32_t)((float)b.z * inv) << 16 |
+             (uint32_t)((float)b.w * inv) << 24;
+    } else {
+        x = max(tile_counts[t], 1);
+    }
+    x = min(x, SCHED_MAX_WEIGHT);
+    *w4 = make_int4(0, 0, 0, 0);
+    w16[t] = (unsigned short)x;
+    if (frac4 && t < SCHED_PLAN_TILES) frac4[t] = fr;
+    return x;
+}
+// the queue item of `tile` (weight wt): its priority -- only for the tile a queue takes in round 0, its first, by that
+// tile's share of the mean queue load `target` -- and its block plan against the four SIMD loads of the queue's CU (updated)
+__device__ __forceinline__ int sched_item(int tile, int wt, int round, int target, const uint32_t* frac4, int (&simd_load)[4]) {
+    const int prio = round > 0 ? 0 : (wt * 5 >= target * 2 ? 3 : (wt * 4 >= target ? 2 : 1));
+    unsigned plan = ITEM_PLAN_IDENTITY;
+    if (frac4 && tile < SCHED_PLAN_TILES) {
+        const uint32_t fr = frac4[tile];
+        const int bw[4] = {(int)(fr & 255u) * wt, (int)((fr >> 8) & 255u) * wt, (int)((fr >> 16) & 255u) * wt,
+                           (int)(fr >> 24) * wt};
+        plan = plan_blocks(bw, simd_load);
+    }
+    return tile | (int)(plan << ITEM_PLAN_SHIFT) | (prio << 28);
+}
+
 // lds: scratch of T ints (used as two 16-bit arrays); wsum: LDS scratch of SCHED_BLOCK / 64 ints.  SCHED_BLOCK threads.
 // Whole workgroup.
 // frac4: SCHED_PLAN_TILES words of LDS for the block plans (share of each block in its tile's weight, 4 x 8 bits), or null:
@@ -206,37 +232,17 @@ __device__ void schedule_tiles(const int32_t* __restrict__ tile_counts, int T, c
     const int tid = threadIdx.x;
     const int NQ = sc.nq;
     // ---- 1. weights
-    if (tid == 0) s_max = 1;
-    for (int b = tid; b < SCHED_BINS; b += SCHED_BLOCK) bins[b] = 0;
-    for (int c = tid; c < 2 * NQ; c += SCHED_BLOCK) sc.counters[c] = 0;
-    if (sc.first_slot)
-        for (int t = tid; t < T; t += SCHED_BLOCK) sc.first_slot[t] = -1;
-    __syncthreads();
+    sched_clear<SCHED_BLOCK>(sc, T, sl);
     int local = 0, lmax = 1;
     for (int t = tid; t < T; t += SCHED_BLOCK) {
-        int4* w4 = reinterpret_cast<int4*>(sc.work) + t;
-        const int4 b = *w4;
-        int x = b.x + b.y + b.z + b.w;
-        uint32_t fr = 0x40404040u;       // no history: four equal blocks
-        if (x > 0) {
-            const float inv = 255.f / (float)x;
-            fr = (uint32_t)((float)b.x * inv) | (uint32_t)((float)b.y * inv) << 8 | (uint32_t)((float)b.z * inv) << 16 |
-                 (uint32_t)((float)b.w * inv) << 24;
-        } else {
-            x = max(tile_counts[t], 1);
-        }
-        x = min(x, SCHED_MAX_WEIGHT);
-        *w4 = make_int4(0, 0, 0, 0);     // the blend kernel adds this iteration's units
-        w16[t] = (unsigned short)x;
-        if (frac4 && t < SCHED_PLAN_TILES) frac4[t] = fr;
+        const int x = sched_tile_weight(t, tile_counts, sc, w16, frac4);
         local += x;
         lmax = max(lmax, x);
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) lmax = max(lmax, __shfl_xor(lmax, off));
+    lmax = wave_max(lmax);
     if ((tid & 63) == 0) atomicMax(&s_max, lmax);
     int W_total;
-    sched_block_scan<SCHED_BLOCK>(local, wsum, W_total);          // (contains the barriers that publish s_max, w16)
+    block_scan_excl<SCHED_BLOCK>(local, wsum, W_total);          // (contains the barriers that publish s_max, w16)
     int shift = 0;
     while ((s_max >> shift) >= SCHED_BINS) ++shift;
     // ---- 2. tiles by descending weight (counting sort on the quantised weight; order within a
@@ -246,7 +252,7 @@ __device__ void schedule_tiles(const int32_t* __restrict__ tile_counts, int T, c
     {
         const int a = bins[2 * tid], b = bins[2 * tid + 1];
         int tot;
-        const int excl = sched_block_scan<SCHED_BLOCK>(a + b, wsum, tot);
+        const int excl = block_scan_excl<SCHED_BLOCK>(a + b, wsum, tot);
         bins[2 * tid] = excl;
         bins[2 * tid + 1] = excl + a;
     }
@@ -288,9 +294,7 @@ __device__ void schedule_tiles(const int32_t* __restrict__ tile_counts, int T, c
             __syncthreads();
             {
                 // (256 LDS atomics on one word cost ~4 us: reduce in the wave first)
-                int mn = (tid < NQ && my_cnt < sc.cap_q) ? my_load : 0x7fffffff;
-#pragma unroll
-                for (int off = 32; off >= 1; off >>= 1) mn = min(mn, __shfl_xor(mn, off));
+                const int mn = wave_min((tid < NQ && my_cnt < sc.cap_q) ? my_load : 0x7fffffff);
                 if ((tid & 63) == 0) atomicMin(&s_lo, mn);
             }
             __syncthreads();
@@ -303,7 +307,7 @@ __device__ void schedule_tiles(const int32_t* __restrict__ tile_counts, int T, c
             __syncthreads();
             {
                 const int x = bins[2 * tid], y = bins[2 * tid + 1];
-                const int excl = sched_block_scan<SCHED_BLOCK>(x + y, wsum, m);
+                const int excl = block_scan_excl<SCHED_BLOCK>(x + y, wsum, m);
                 bins[2 * tid] = excl;
                 bins[2 * tid + 1] = excl + x;
             }
@@ -315,17 +319,9 @@ __device__ void schedule_tiles(const int32_t* __restrict__ tile_counts, int T, c
         if (rank < avail && rank < m) {
             const int tile = ord16[next + rank];
             const int wt = w16[tile];
-            const int prio = next > 0 ? 0 : (wt * 5 >= target * 2 ? 3 : (wt * 4 >= target ? 2 : 1));
-            unsigned plan = ITEM_PLAN_IDENTITY;
-            if (frac4 && tile < SCHED_PLAN_TILES) {
-                const uint32_t fr = frac4[tile];
-                const int bw[4] = {(int)(fr & 255u) * wt, (int)((fr >> 8) & 255u) * wt, (int)((fr >> 16) & 255u) * wt,
-                                   (int)(fr >> 24) * wt};
-                plan = plan_blocks(bw, simd_load);
-            }
-            my_list[my_cnt++] = tile | (int)(plan << ITEM_PLAN_SHIFT) | (prio << 28);
+            my_list[my_cnt++] = sched_item(tile, wt, next, target, frac4, simd_load);      // (next = 0: the first round)
             my_load += wt;
-            if (next == 0 && sc.first_slot) sc.first_slot[tile] = tid;       // (the barrier after the clearing loop has passed)
+            if (next == 0 && sc.first_slot) sc.first_slot[tile] = tid;       // (sched_clear's barrier has passed)
         }
         if (next == 0 && tid < NQ && sc.split_min > 0) {
             // forward schedule: a long first tile costs its own CU a quarter, the other three quarters go to the queues
@@ -343,26 +339,9 @@ __device__ void schedule_tiles(const int32_t* __restrict__ tile_counts, int T, c
     if (tid < NQ) sc.count[tid] = my_cnt;
 }
 
-// value of lane (lane ^ D), D in {1, 2, 4, 8, 16}, on the VALU only (DPP / v_permlane16_swap; see gfl_tile_sort.hpp)
-template <int D>
-__device__ __forceinline__ unsigned sched_xor_lane(unsigned v, int lane) {
-    const int x = (int)v;
-    if constexpr (D == 1) return (unsigned)__builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, true);
-    else if constexpr (D == 2) return (unsigned)__builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, true);
-    else if constexpr (D == 4) {
-        int t = __builtin_amdgcn_update_dpp(x, x, 0x104, 0xF, 0x5, false);
-        t = __builtin_amdgcn_update_dpp(t, x, 0x114, 0xF, 0xA, false);
-        return (unsigned)t;
-    } else if constexpr (D == 8) return (unsigned)__builtin_amdgcn_update_dpp(0, x, 0x128, 0xF, 0xF, true);
-    else {
-        float a = __builtin_bit_cast(float, v), b = a;
-        permlane16_swap(a, b);
-        return __builtin_bit_cast(unsigned, (lane & 16) ? a : b);
-    }
-}
 template <int D>
 __device__ __forceinline__ void sched_cx(unsigned& key, int k, int lane) {
-    const unsigned other = sched_xor_lane<D>(key, lane);
+    const unsigned other = xor_lane<D>(key, lane);
     const bool take_min = ((lane & D) == 0) == ((lane & 31 & k) == 0);
     key = ((key < other) == take_min) ? key : other;
 }
@@ -397,40 +376,20 @@ __device__ void schedule_tiles_xcd(const int32_t* __restrict__ tile_counts, int 
     unsigned short* ord16 = w16 + T;                                     // tiles by (band, descending weight)
     const int tid = threadIdx.x;
     const int NQ = sc.nq, NQG = NQ / 8;
-    if (tid == 0) s_max = 1;
-    for (int b = tid; b < SCHED_BINS; b += BLOCK) bins[b] = 0;
-    for (int c = tid; c < 2 * NQ; c += BLOCK) sc.counters[c] = 0;
-    if (sc.first_slot)
-        for (int t = tid; t < T; t += BLOCK) sc.first_slot[t] = -1;
-    __syncthreads();
+    sched_clear<BLOCK>(sc, T, sl);
     // ---- weights; thread tid owns the CONTIGUOUS tiles [tid * per, (tid + 1) * per) (row-major order = bands)
     const int per = (T + BLOCK - 1) / BLOCK;
     const int t_lo = tid * per, t_hi = min(T, t_lo + per);
     int local = 0, lmax = 1;
     for (int t = t_lo; t < t_hi; ++t) {
-        int4* w4 = reinterpret_cast<int4*>(sc.work) + t;
-        const int4 b = *w4;
-        int x = b.x + b.y + b.z + b.w;
-        uint32_t fr = 0x40404040u;
-        if (x > 0) {
-            const float inv = 255.f / (float)x;
-            fr = (uint32_t)((float)b.x * inv) | (uint32_t)((float)b.y * inv) << 8 | (uint32_t)((float)b.z * inv) << 16 |
-                 (uint32_t)((float)b.w * inv) << 24;
-        } else {
-            x = max(tile_counts[t], 1);
-        }
-        x = min(x, SCHED_MAX_WEIGHT);
-        *w4 = make_int4(0, 0, 0, 0);
-        w16[t] = (unsigned short)x;
-        if (frac4 && t < SCHED_PLAN_TILES) frac4[t] = fr;
+        const int x = sched_tile_weight(t, tile_counts, sc, w16, frac4);
         local += x;
         lmax = max(lmax, x);
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) lmax = max(lmax, __shfl_xor(lmax, off));
+    lmax = wave_max(lmax);
     if ((tid & 63) == 0) atomicMax(&s_max, lmax);
     int W_total;
-    int run = sched_block_scan<BLOCK>(local, wsum, W_total);      // weight in front of this thread's tiles (+ the barriers)
+    int run = block_scan_excl<BLOCK>(local, wsum, W_total);      // weight in front of this thread's tiles (+ the barriers)
     int shift = 0;
     while ((s_max >> shift) >= 128) ++shift;
     // ---- counting sort by (band, descending weight); the band of a tile = where its prefix weight falls
@@ -524,15 +483,7 @@ __device__ void schedule_tiles_xcd(const int32_t* __restrict__ tile_counts, int 
             if (rank < m && p < cnt && room) {
                 const int tile = ord16[b0 + p];
                 const int wt = w16[tile];
-                const int prio = k > 0 ? 0 : (wt * 5 >= target * 2 ? 3 : (wt * 4 >= target ? 2 : 1));
-                unsigned plan = ITEM_PLAN_IDENTITY;
-                if (frac4 && tile < SCHED_PLAN_TILES) {
-                    const uint32_t fr = frac4[tile];
-                    const int bw[4] = {(int)(fr & 255u) * wt, (int)((fr >> 8) & 255u) * wt, (int)((fr >> 16) & 255u) * wt,
-                                       (int)(fr >> 24) * wt};
-                    plan = plan_blocks(bw, key);
-                }
-                my_list[n_items] = tile | (int)(plan << ITEM_PLAN_SHIFT) | (prio << 28);
+                my_list[n_items] = sched_item(tile, wt, k, target, frac4, key);
                 if (n_items == 0 && sc.first_slot) sc.first_slot[tile] = q;
                 ++n_items;
                 load += wt;

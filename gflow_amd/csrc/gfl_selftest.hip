@@ -21,6 +21,21 @@ __global__ void __launch_bounds__(64) selftest_reduce10_kernel(const float* __re
     }
 }
 
+// one workgroup of BLOCK threads: block_scan_excl over in[0 .. BLOCK) and then over in[BLOCK .. 2 BLOCK), back to back on the
+// same wsum with no barrier of the kernel's own in between
+template <int BLOCK>
+__global__ void __launch_bounds__(BLOCK) selftest_block_scan_kernel(const int32_t* __restrict__ in, int32_t* __restrict__ out_excl,
+                                                                    int32_t* __restrict__ out_total) {
+    __shared__ int32_t wsum[BLOCK / 64];
+    const int tid = threadIdx.x;
+    int total0, total1;
+    const int excl0 = block_scan_excl<BLOCK>(in[tid], wsum, total0);
+    const int excl1 = block_scan_excl<BLOCK>(in[BLOCK + tid], wsum, total1);
+    out_excl[tid] = excl0;
+    out_excl[BLOCK + tid] = excl1;
+    if (tid == BLOCK - 1) { out_total[0] = total0; out_total[1] = total1; }
+}
+
 // Sigma2 = M Sigma M^T of n splats both ways: m [n][6] = rows m0 | m1 of M, cov [n][6]; out_* [n][3] = a b c
 __global__ void __launch_bounds__(256) selftest_cov2d_kernel(const float* __restrict__ m, const float* __restrict__ cov, int n,
                                                              float* __restrict__ out_valu, float* __restrict__ out_mfma) {
@@ -80,6 +95,16 @@ extern "C" int gfl_selftest_cov2d(const float* m, const float* cov, int n, float
     if (!m || !cov || !out_valu || !out_mfma || n < 0) return GFL_ERR_INVALID;
     if (n == 0) return GFL_OK;
     gfl::selftest_cov2d_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(m, cov, n, out_valu, out_mfma);
+    return gfl::check_launch();
+}
+
+extern "C" int gfl_selftest_block_scan(const int32_t* in, int block, int32_t* out_excl, int32_t* out_total, gfl_stream_t stream) {
+    if (!in || !out_excl || !out_total) return GFL_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    if (block == 256) gfl::selftest_block_scan_kernel<256><<<1, 256, 0, s>>>(in, out_excl, out_total);
+    else if (block == 512) gfl::selftest_block_scan_kernel<512><<<1, 512, 0, s>>>(in, out_excl, out_total);
+    else if (block == 1024) gfl::selftest_block_scan_kernel<1024><<<1, 1024, 0, s>>>(in, out_excl, out_total);
+    else return GFL_ERR_INVALID;
     return gfl::check_launch();
 }
 

@@ -8,7 +8,7 @@
 // (sixteen waves: 21 and 17 us -- every tile then pays for the wider workgroup).
 // Bitonic network; a compare-exchange partner is
 //   - in the same lane            when the stride is below E        (register swap),
-//   - in the same wave            when it is below 64 E             (DPP / permlane swap, no LDS),
+//   - in the same wave            when it is below 64 E             (xor_lane: DPP / permlane swap, no LDS),
 //   - in another wave otherwise   (a few steps per sort)            (16 KB LDS exchange buffer, four keys per barrier pair).
 // A first version sorted in LDS with a barrier per pass: a single 300-key tile then cost ~25 us
 // of barrier latency and set the duration of the whole launch.
@@ -23,39 +23,13 @@ __device__ long long g_sort_trace[16384 * 4];   // analysis build: start / keys 
 #define SORT_TRACE(slot)
 #endif
 
-// Value of lane (lane ^ D) for a wave-uniform D in {1, 2, 4, 8, 16, 32}, on the VALU only: DPP
-// quad permutes / row shifts / row rotate inside a 16-lane row, v_permlane16_swap / v_permlane32_swap
-// (gfx950) across rows.  __shfl_xor goes through ds_bpermute (address VGPR + an LDS-pipe round trip
-// per 32 bits); with ~40 dependent exchange steps per tile the sort network cost 14 of the
-// launch's 24 us that way.
-template <int D>
-__device__ __forceinline__ unsigned xor_lane_u32(unsigned v, int lane) {
-    const int x = (int)v;
-    if constexpr (D == 1) return (unsigned)__builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, true);   // quad_perm [1,0,3,2]
-    else if constexpr (D == 2) return (unsigned)__builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, true);   // quad_perm [2,3,0,1]
-    else if constexpr (D == 4) {
-        int t = __builtin_amdgcn_update_dpp(x, x, 0x104, 0xF, 0x5, false);               // row_shl:4 -> banks 0, 2
-        t = __builtin_amdgcn_update_dpp(t, x, 0x114, 0xF, 0xA, false);                   // row_shr:4 -> banks 1, 3
-        return (unsigned)t;
-    } else if constexpr (D == 8) return (unsigned)__builtin_amdgcn_update_dpp(0, x, 0x128, 0xF, 0xF, true);   // row_ror:8
-    else if constexpr (D == 16) {
-        float a = __builtin_bit_cast(float, v), b = a;
-        permlane16_swap(a, b);               // a = rows {0,0,2,2} of v, b = rows {1,1,3,3}
-        return __builtin_bit_cast(unsigned, (lane & 16) ? a : b);
-    } else {
-        float a = __builtin_bit_cast(float, v), b = a;
-        permlane32_swap(a, b);               // a = {lo, lo}, b = {hi, hi}
-        return __builtin_bit_cast(unsigned, (lane & 32) ? a : b);
-    }
-}
-
 // one compare-exchange step of the network with the partner D lanes away, all E keys of the lane
 template <int E, int D>
 __device__ __forceinline__ void exchange_in_wave(unsigned long long (&key)[E], int k, int tid) {
     const bool lower = (tid & D) == 0;
 #pragma unroll
     for (int e = 0; e < E; ++e) {
-        const unsigned lo = xor_lane_u32<D>((unsigned)key[e], tid), hi = xor_lane_u32<D>((unsigned)(key[e] >> 32), tid);
+        const unsigned lo = xor_lane<D>((unsigned)key[e], tid), hi = xor_lane<D>((unsigned)(key[e] >> 32), tid);
         const unsigned long long other = ((unsigned long long)hi << 32) | lo;
         const bool up = ((tid * E + e) & k) == 0;
         const bool take_min = lower == up;

@@ -116,7 +116,7 @@ typedef enum gfl_status {
  * number stays; a binding that needs it looks the symbol up).  gfl_track_history, gfl_track_backward and
  * gfl_track_backward_workspace_bytes were added WITHIN 312 in the same way, and so were gfl_track_vis and gfl_prep_frames with
  * their workspace queries, the four gfl_jpeg_* entries, and gfl_optflow, gfl_optflow_level, gfl_optflow_workspace_bytes,
- * and the seven gfl_sfm_* entries.  A binding checks gfl_version() >= GFL_VERSION of the header it was written for. */
+ * the seven gfl_sfm_* entries and gfl_selftest_block_scan.  A binding checks gfl_version() >= GFL_VERSION of the header it was written for. */
 #define GFL_VERSION 312
 int gfl_version(void);
 /* out[10] = TILE, NEAREST, EXTENT, FOV_CLAMP, LOWPASS, EIG_FLOOR, RADIUS_SIGMA, ALPHA_MIN, ALPHA_MAX, T_MIN of this build */
@@ -558,6 +558,10 @@ int gfl_tile_sort_reserved(const int32_t* order, const int32_t* fill, int32_t* t
 /* device self-test of the wave64 reduce-scatter used by the blend backward: in[64][10] ->
  * out_scatter[10] (permlane-swap reduce-scatter) and out_dpp[10] (plain DPP sums) */
 int gfl_selftest_reduce10(const float* in, float* out_scatter, float* out_dpp, gfl_stream_t stream);
+/* device self-test of the workgroup exclusive scan every kernel uses (block_scan_excl, gfl_common.hpp): ONE workgroup of
+ * `block` threads (256, 512 or 1024; anything else: GFL_ERR_INVALID) scans in[0 .. block) and then in[block .. 2 block),
+ * back to back on the same LDS scratch -> out_excl[2 block], and the two totals -> out_total[2] */
+int gfl_selftest_block_scan(const int32_t* in, int block, int32_t* out_excl, int32_t* out_total, gfl_stream_t stream);
 /* device self-test of the EWA contraction Sigma2 = M Sigma M^T (gfl_math.hpp) both ways: m[n][6] = the two rows of
  * M = J W, cov[n][6] = xx xy xz yy yz zz -> out_valu[n][3], out_mfma[n][3] = (a, b, c) before the low-pass.  The
  * MFMA form (v_mfma_f32_4x4x1_16b_f32, sixteen splats per instruction) is what GFL_EWA_MFMA=1 puts into the fused

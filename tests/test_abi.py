@@ -122,3 +122,13 @@ def test_reserved_entry_points_reject_bad_arguments_without_a_gpu():
     null = ctypes.c_void_p(0)
     assert lib.gfl_tile_sort_reserved(null, null, null, null, 64, 64, 16, null, null, null, null) != 0
     assert lib.gfl_fit_reserved_supported(null, null) == 0
+
+
+def test_block_scan_selftest_rejects_other_block_sizes_without_a_gpu():
+    """gfl_selftest_block_scan runs workgroups of 256, 512 or 1024 threads only, and says so before anything is launched."""
+    from gflow_amd import _lib
+    lib = _lib.load()
+    buf = (ctypes.c_int32 * 8)()
+    for block in (0, 64, 128, 384, 2048, -256):
+        assert lib.gfl_selftest_block_scan(buf, block, buf, buf, None) == -1
+    assert lib.gfl_selftest_block_scan(None, 256, buf, buf, None) == -1

@@ -68,6 +68,26 @@ def test_oracle_parity_holds_with_the_matrix_core_contraction():
     assert " passed" in r.stdout and "skipped" not in r.stdout.splitlines()[-1], tail
 
 
+@pytest.mark.parametrize("block", [256, 512, 1024])
+def test_block_scan_twice_on_the_same_scratch(block):
+    """block_scan_excl, the one workgroup scan of the library: two scans back to back on the same LDS scratch, with no
+    barrier between them but the scan's own, for every workgroup size in use.  Values 1 + (i * 7919) % 13: a lane or wave
+    mix-up cannot cancel.  Exact against numpy.cumsum."""
+    import numpy as np
+    from gflow_amd import _lib as L
+    lib = L.load()
+    x = (1 + (np.arange(2 * block, dtype=np.int64) * 7919) % 13).astype(np.int32)
+    xd = torch.from_numpy(x).to(DEV)
+    excl = torch.full((2 * block,), -7, dtype=torch.int32, device=DEV)
+    total = torch.full((2,), -7, dtype=torch.int32, device=DEV)
+    L.check(lib.gfl_selftest_block_scan(L.ptr(xd), block, L.ptr(excl), L.ptr(total), L.stream()), "selftest")
+    torch.cuda.synchronize()
+    halves = x.reshape(2, block)
+    ref = np.cumsum(halves, axis=1) - halves                       # exclusive
+    assert np.array_equal(excl.cpu().numpy().reshape(2, block), ref)
+    assert np.array_equal(total.cpu().numpy(), halves.sum(axis=1))
+
+
 @pytest.mark.parametrize("box", [8, 4])
 def test_block_culling_never_drops_a_visible_pixel(box):
     """The blend kernels skip a (splat, pixel box) unit when `block_mask` says the splat cannot reach the box with
