@@ -104,6 +104,8 @@ SIGNATURES = {
     "gfl_flow_workspace_bytes": (c_size_t, [c_int, c_int]),
     "gfl_flow_pair": (c_int, [_P, c_int, _P, _P, _P, c_int, _P, c_int, c_int, _P, _P, c_int, c_int, c_float, c_int, c_int, _P,
                               _P, _P, _P, c_size_t, _P]),
+    "gfl_label_frame": (c_int, [_P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_int, _P, _P, _P]),
+    "gfl_label_assign": (c_int, [_P, c_int, _P, c_int, c_int, _P, _P]),
     "gfl_epi_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "gfl_epi_fundamental": (c_int, [_P, c_int, c_int, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
     "gfl_epi_mask": (c_int, [_P, c_int, c_int, _P, ctypes.c_double, _P, _P, _P, _P, _P, _P, c_size_t, _P]),

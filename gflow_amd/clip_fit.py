@@ -17,6 +17,7 @@ import torch
 from . import camera as CM
 from . import flow as FL
 from . import msplat
+from . import propagation as PG
 from . import quality as QL
 from . import render as render_mod
 from . import segmentation as SG
@@ -46,7 +47,8 @@ DEFAULTS = dict(num_points=60000, lr=4e-3, lr_camera=0.0, iterations_first=500, 
 
 # the keys of fit_clip's dict that are per-clip numbers (sums over clips make sense); "traj" is the trajectory output,
 # "tracks" the tracker's, "segmentation" the moving-region masks and their score, "recon" and "camera" the per-frame
-# reconstruction sums and the camera path with its score, "flow" the per-pair flow sums (and maps)
+# reconstruction sums and the camera path with its score, "flow" the per-pair flow sums (and maps), "propagation" the object
+# id maps and their score
 NUMERIC_KEYS = ("psnr_sum", "frames", "iterations", "rasterisations", "clips", "splats_final", "void_iterations")
 
 _FIT_STREAMS = {}
@@ -168,7 +170,7 @@ class ClipFit:
 
     def __init__(self, frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, log=None, load_extr=True, chunk=None,
                  async_snapshots=True, keep=None, cu_count=0, deterministic=None, track_queries=None, segment=False,
-                 recon=False, camera=False, flow=False, track_backward=False, track_vis=False):
+                 recon=False, camera=False, flow=False, track_backward=False, track_vis=False, propagate=None):
         if track_backward and track_queries is None:
             raise ValueError("fit_clip(track_backward=True) needs track_queries")
         if track_vis and track_queries is None and not int((cfg or {}).get("traj_num", DEFAULTS["traj_num"])) > 0:
@@ -205,6 +207,8 @@ class ClipFit:
             self.flow_rec = FL.FlowRecorder(len(frames), tr.H, tr.W, tr.device, keep_maps=flow == "maps")
             if keep is not None and keep.get("record_flow_inputs"):
                 self.flow_rec.inputs = keep.setdefault("flow_inputs", [])
+        # (ValueError for a prompt the recorder refuses: nothing has been fitted yet)
+        self.object_rec = None if propagate is None else PG.ObjectRecorder(len(frames), tr.H, tr.W, tr.device, propagate)
         tr.load_camera(focal=f0["focal"], pp=f0["pp"])
         if load_extr and f0.get("extr") is not None:
             tr.load_camera(extr=f0["extr"])
@@ -287,6 +291,19 @@ class ClipFit:
             prev = self.frames[i - 1] if i else None
             self.flow_rec.frame(i, rec, n, ids, tile_range, prev["flow"] if prev else None, prev["move_mask"] if prev else None)
 
+    def record_objects(self, i):
+        # frame i's final records and sorted tile lists go to the object recorder, as they go to the flow recorder: the id map
+        # of the frame from one gfl_label_frame, ids for the rows that have none; nothing is read back
+        tr = self.tr
+        with torch.no_grad():
+            if tr.engine_current:
+                aux, _ = self.final_forward()
+                rec, n, ids, tile_range = aux.rec, aux.N, aux.ids, aux.tile_range
+            else:
+                rec, n, ids, tile_range = FL.operator_state(tr._input_group(detach=True))
+                tr.rasterisations_done += 1
+            self.object_rec.frame(i, rec, n, ids, tile_range)
+
     def record_scores(self, i):
         # benchmark.py:191-230 and :323-329 for frame i, on what the frame's PSNR is taken from and what save_checkpoint
         # stores: two small launches that write one row of the clip's sums, and a clone of the pose; nothing is read back
@@ -310,6 +327,8 @@ class ClipFit:
             self.record_tracks(i)
         if self.flow_rec is not None:
             self.record_flow(i)
+        if self.object_rec is not None:
+            self.record_objects(i)
         # (PSNR stays on the device and is read ONCE at the end of the clip: a float() per frame drained the queue between
         #  two frames; with a log callback the caller asked for the numbers as they come)
         p = tr.psnr()
@@ -430,6 +449,9 @@ class ClipFit:
             out["camera"] = dict(extr=extr, **CM.evaluate(extr, gt))
         if self.flow_rec is not None:
             out["flow"] = self.flow_rec.result()          # (one copy of the (T-1, 3, 6) sums; with "maps" the maps behind it)
+        if self.object_rec is not None:
+            # one copy of the id maps; the frames that carry an "object_mask" are scored with one launch
+            out["propagation"] = self.object_rec.result([fr.get("object_mask") for fr in frames])
         if self.track_vis:
             out["track_vis"] = self.overlays(out)
         return out
@@ -437,7 +459,7 @@ class ClipFit:
 
 def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, log=None, load_extr=True, chunk=None,
                    async_snapshots=True, keep=None, cu_count=0, deterministic=None, track_queries=None, segment=False,
-                   recon=False, camera=False, flow=False, track_backward=False, track_vis=False):
+                   recon=False, camera=False, flow=False, track_backward=False, track_vis=False, propagate=None):
     """fit_clip as a generator: yields after every ``chunk`` iterations of a stage (None: never) and returns the metrics
     dict of the clip (PSNR summed over its frames; with ``cfg["traj_num"]`` > 0 also ``"traj"``: the per-frame trajectory
     images and seed projections, host arrays -- what the reference's frame loop collects in
@@ -490,11 +512,17 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
     ``seeds_still`` and, when there are moving seeds, ``seeds_move`` (fit_video.py:386-392).  ``keep`` then also receives
     ``keep["track_vis_inputs"]`` = dict(video (T, H, W, 3) uint8, masks (T, H, W) uint8 with ``traj_num``), host arrays.
     ``track_vis`` may also be a dict name -> (tracks (T, N, 2), occluded (T, N)) of further tracks to paint over the same
-    renders, one more array each (the command line's ``gt``: benchmark.py:165)."""
+    renders, one more array each (the command line's ``gt``: benchmark.py:165).
+    ``propagate``: None, or the object ids of frame 0 -- (H, W) integers, 0 = background, at most 15 -- to propagate through
+    the clip (gflow_amd.propagation.ObjectRecorder; INTEGRATION.md, "Object propagation"; a prompt it refuses is a ValueError
+    before anything is fitted): every frame ends with one gfl_label_frame on the forward the other recorders read, and the
+    dict then has ``"propagation"`` = dict(maps (T, H, W) uint8 -- 255 = unknown --, labels (N,) uint8, rows (T,), n_objects; counts
+    (T, K - 1, 6), J, F, JF (T, K - 1), scored (T,), flat), scored against the frames' ``"object_mask"`` (frames 1 .. T - 1
+    that carry one).  Off by default; nothing about a fit changes with it off."""
     cf = ClipFit(frames, device, cfg, seed=seed, snapshot_interval=snapshot_interval, fused=fused, log=log, load_extr=load_extr,
                  chunk=chunk, async_snapshots=async_snapshots, keep=keep, cu_count=cu_count, deterministic=deterministic,
                  track_queries=track_queries, segment=segment, recon=recon, camera=camera, flow=flow,
-                 track_backward=track_backward, track_vis=track_vis)
+                 track_backward=track_backward, track_vis=track_vis, propagate=propagate)
     yield from cf.steps()
     return cf.result()
 
@@ -527,7 +555,7 @@ def fit_clip(frames, device, cfg=None, fused=True, deterministic=None, **options
 
 
 def fit_clips_concurrent(clips, device, cfg=None, seeds=None, chunk=32, partition=False, deterministic=None,
-                         track_queries=None, track_backward=False, track_vis=False, **options):
+                         track_queries=None, track_backward=False, track_vis=False, propagate=None, **options):
     """Fit several clips AT THE SAME TIME on ONE device, in one host thread: every clip has its own trainer, engine and
     STREAM, and the clips take turns enqueueing ``chunk`` iterations each (fit_clip_steps), so their graph launches
     interleave on the device.  One fit leaves the chip partly idle -- its kernels are a chain of dependent launches,
@@ -546,13 +574,16 @@ def fit_clips_concurrent(clips, device, cfg=None, seeds=None, chunk=32, partitio
     with the same seed -- without ``partition``, which changes the number of tile queues (include/gflow_hip.h).
     ``track_queries``: None, or one entry (fit_clip_steps' ``track_queries``, or None) per clip; ``track_backward``:
     fit_clip_steps' for every clip that has queries (ValueError without ``track_queries``).  ``track_vis``: fit_clip_steps',
-    for all clips, or a list with one entry per clip.  ``options``: fit_clip_steps'
+    for all clips, or a list with one entry per clip.  ``propagate``: None, or one prompt (fit_clip_steps' ``propagate``, or
+    None) per clip.  ``options``: fit_clip_steps'
     other ones, for all clips (``async_snapshots`` and ``cu_count`` are set here)."""
     n = len(clips)
     if track_queries is not None and len(track_queries) != n:
         raise ValueError("fit_clips_concurrent: track_queries needs one entry per clip")
     if track_backward and track_queries is None:
         raise ValueError("fit_clips_concurrent(track_backward=True) needs track_queries")
+    if propagate is not None and len(propagate) != n:
+        raise ValueError("fit_clips_concurrent: propagate needs one entry per clip")
     if isinstance(track_vis, (list, tuple)) and len(track_vis) != n:
         raise ValueError("fit_clips_concurrent: a list of track_vis needs one entry per clip")
     seeds = list(range(n)) if seeds is None else seeds
@@ -575,7 +606,8 @@ def fit_clips_concurrent(clips, device, cfg=None, seeds=None, chunk=32, partitio
                            cu_count=shares[i][1] if shares else 0, deterministic=deterministic,
                            track_queries=None if track_queries is None else track_queries[i],
                            track_backward=bool(track_backward) and track_queries[i] is not None,
-                           track_vis=track_vis[i] if isinstance(track_vis, (list, tuple)) else track_vis, **options)
+                           track_vis=track_vis[i] if isinstance(track_vis, (list, tuple)) else track_vis,
+                           propagate=None if propagate is None else propagate[i], **options)
             for i in range(n)]
     results = [None] * n
     live = list(range(n))

@@ -26,6 +26,7 @@ import torch
 
 from . import flow as FL
 from . import io as gio
+from . import propagation as PG
 from . import quality as QL
 from . import synthetic as S
 from . import track_vis as TV
@@ -105,6 +106,13 @@ def _parser():
     ap.add_argument("--flow-out", default=None,
                     help="with --flow: write each clip's flow maps to DIR/clip_<i>/flow_<frame>.flo (frame -> frame + 1 on "
                          "the frame's grid; pixels without a flow are 1e10, Middlebury's mark)")
+    ap.add_argument("--propagate", action="store_true",
+                    help="propagate the object ids of the first frame's annotation (<seq>_mask/*.png; a synthetic clip's first "
+                         "move mask) through the clip and score every later frame that has one with DAVIS J, F and J&F per "
+                         "object (a \"davis_semi\" block in the line)")
+    ap.add_argument("--propagate-out", default=None,
+                    help="with --propagate: write each clip's id maps to DIR/clip_<i>/<frame name>.png (with the prompt "
+                         "file's palette if it has one, else grey ids; unknown pixels are 0)")
     ap.add_argument("--no-load-extr", action="store_true",
                     help="do not load the frames' camera poses (extr): the camera-only stages estimate them, as the "
                          "reference's scripts/fit_video.sh runs")
@@ -146,6 +154,8 @@ def _check_args(ap, args):
         ap.error("--track-backward needs --track")
     if args.track_vis and not (args.track or args.traj_num > 0):
         ap.error("--track-vis needs --track or --traj-num")
+    if args.propagate_out and not args.propagate:
+        ap.error("--propagate-out needs --propagate")
     if args.video and not args.track_vis:
         ap.error("--video needs --track-vis")
     if args.track and args.track_queries == "strided" and not args.track_backward:
@@ -200,9 +210,15 @@ def _load_clips(args, mine, lengths, dev):
                                                          or gio.is_video(args.sequence[ci])) else None,
                                           decode=args.decode,
                                           flows="estimate" if args.make_flows else "files",
-                                          depth_camera="estimate" if args.make_depth_camera else "files", focal=args.focal)
+                                          depth_camera="estimate" if args.make_depth_camera else "files", focal=args.focal,
+                                          object_masks="files" if args.propagate else "none")
         else:
             clips[ci] = upload_clip(S.make_clip(lengths[ci], args.height, args.width, seed=ci, device=dev), dev)
+            if args.propagate:                   # (a synthetic clip's one object is its moving disc)
+                for fr in clips[ci]:
+                    fr["object_mask"] = fr["move_mask"].to(torch.uint8)
+        if args.propagate and (not clips[ci] or clips[ci][0].get("object_mask") is None):
+            raise SystemExit(f"--propagate: clip {ci} has no annotation of its first frame (<seq>_mask/*.png)")
     return clips
 
 
@@ -251,18 +267,20 @@ def _fit_groups(args, clips, lengths, dev, cfg, gts, queries, rank):
     options = dict(track_backward=args.track_backward, deterministic=True if args.deterministic else None, segment=args.seg,
                    recon=args.recon, camera=args.camera, flow=("maps" if args.flow_out else True) if args.flow else False,
                    load_extr=not args.no_load_extr)
+    prompt = lambda ci: clips[ci][0]["object_mask"] if args.propagate else None
     results = {}
     for g0 in range(0, len(order), c):
         group = order[g0:g0 + c]
         if len(group) == 1:
             ci = group[0]
             res = [fit_clip(clips[ci], dev, cfg, seed=ci, track_queries=queries.get(ci),
-                            track_vis=_vis_option(args, gts, clips, ci), **options,
+                            track_vis=_vis_option(args, gts, clips, ci), propagate=prompt(ci), **options,
                             log=(lambda s, ci=ci: print(f"[rank {rank} clip {ci}] {s}")) if args.verbose else None)]
         else:
             res = fit_clips_concurrent([clips[ci] for ci in group], dev, cfg, seeds=group,
                                        track_queries=[queries.get(ci) for ci in group] if args.track else None,
-                                       track_vis=[_vis_option(args, gts, clips, ci) for ci in group], **options)
+                                       track_vis=[_vis_option(args, gts, clips, ci) for ci in group],
+                                       propagate=[prompt(ci) for ci in group] if args.propagate else None, **options)
         results.update(zip(group, res))
     return results
 
@@ -306,6 +324,17 @@ def _report(args, results, wall, clips, gts, queries, dropped, rank, world, over
         if args.flow_out:
             for ci, fl in of("flow").items():
                 FL.write_flo_maps(os.path.join(args.flow_out, f"clip_{ci}"), fl)
+    if args.propagate:
+        out["davis_semi"] = reduce_davis({ci: p["flat"] for ci, p in of("propagation").items()}, *over_ranks)
+        if args.propagate_out:
+            for ci, p in of("propagation").items():
+                palette = None
+                if args.sequence:
+                    from PIL import Image
+                    first = Image.open(gio.sequence_paths(args.sequence[ci])["objects"][0])
+                    palette = first.getpalette() if first.mode == "P" else None
+                PG.write_id_maps(os.path.join(args.propagate_out, f"clip_{ci}"), p["maps"],
+                                 [fr.get("name", f"{t:05d}") for t, fr in enumerate(clips[ci])], palette)
     if rank == 0 and args.metrics_csv:
         QL.write_metrics_csv(args.metrics_csv, csv_metrics(out))
     return out

@@ -10,6 +10,7 @@ Mirrors ``gflow/utils/read.py`` and ``gflow/utils/conversion.py`` and the direct
                                      (both kinds of .flo can be made from the images: gflow_amd.optflow)
     <seq>_epipolar/*_open.png        move mask                           (fit_video.py:96-97)
     <seq>_camera_mast3r_s2/*.json    {"focal", "pp", "pose"}              (read.py:72-89)
+    <seq>_mask/*.png                 object ids per pixel (DAVIS annotations; fit_video.py's mask prompt; optional)
 
 A clip can also be ONE video file: a ``sequence_path`` that is a file ending in ``.avi`` (Motion-JPEG, as gflow_amd.video
 writes it) stands for the folder of its frames, named ``frame_00000``, ``frame_00001``, ...; the sibling folders are then
@@ -32,15 +33,17 @@ import torch.nn.functional as F
 FLO_MAGIC = 202021.25
 
 
+def _resize_target(h, w, resize):
+    """the size torchvision.transforms.Resize(int) gives an (h, w) image: the shorter side becomes ``resize``"""
+    if resize is None:
+        return h, w
+    return (resize, int(resize * w / h)) if h <= w else (int(resize * h / w), resize)
+
+
 def _resize_chw(t, resize):
     """torchvision.transforms.Resize(int, antialias=True) on a (C,H,W) float tensor."""
-    if resize is None:
-        return t
     _, h, w = t.shape
-    if h <= w:
-        nh, nw = resize, int(resize * w / h)
-    else:
-        nh, nw = int(resize * h / w), resize
+    nh, nw = _resize_target(h, w, resize)
     if (nh, nw) == (h, w):
         return t
     return F.interpolate(t.unsqueeze(0), size=(nh, nw), mode="bilinear", antialias=True, align_corners=False).squeeze(0)
@@ -125,6 +128,30 @@ def read_mask(mask_path, resize=None):
     return t.squeeze() > 0
 
 
+def _resize_ids(ids, resize):
+    """_resize_chw's target size, nearest neighbour: an id is never interpolated"""
+    nh, nw = _resize_target(*ids.shape, resize)
+    if (nh, nw) == tuple(ids.shape):
+        return ids
+    return F.interpolate(ids[None, None].float(), size=(nh, nw), mode="nearest")[0, 0].to(torch.uint8)
+
+
+def _object_ids(img):
+    """(H, W) uint8 ids of an opened PIL image: a palette image's indices; any other mode 1 where read_mask's rule says
+    set (a non-zero channel)"""
+    a = np.asarray(img)
+    if img.mode != "P":
+        a = (a.reshape(a.shape[0], a.shape[1], -1) != 0).any(axis=-1)
+    return torch.from_numpy(np.ascontiguousarray(a.astype(np.uint8)))
+
+
+def read_object_mask(mask_path, resize=None):
+    """An object annotation -> (H, W) uint8 ids, 0 = background: the indices of a palette PNG (DAVIS-2017), else 1 where
+    ``read_mask`` says set.  ``resize``: the loader's target size, nearest neighbour."""
+    from PIL import Image
+    return _resize_ids(_object_ids(Image.open(mask_path)), resize)
+
+
 def read_depth(depth_path, resize=None, depth_scale=1.0, depth_offset=0.0):
     """read.py:60-70 -> (H,W) float."""
     t = torch.tensor(np.load(depth_path), dtype=torch.float32).unsqueeze(0)
@@ -184,6 +211,7 @@ def _every_path(sequence_path):
         flow_bwd=sorted(flow_dir.glob("*pred_bwd.flo")),
         move=sorted(Path(sp + "_epipolar").glob("*_open.png")),
         camera=sorted(Path(sp + "_camera_mast3r_s2").glob("*.json")),
+        objects=sorted(Path(sp + "_mask").glob("*.png")),
     )
 
 
@@ -208,7 +236,7 @@ _OPTIONS = dict(decode=("host", "device"), occ_masks=("files", "flow"), move_mas
 
 def load_sequence(sequence_path, resize=None, frame_start=0, frame_range=-1, skip_interval=1, depth_offset=0.0,
                   move_masks="files", occ_masks="files", blur=False, device=None, flows="files", depth_camera="files",
-                  focal=None, decode="host"):
+                  focal=None, decode="host", object_masks="none"):
     """Frames in the dict form ``gflow_amd.fit_video.fit_clip`` takes.  Frame i carries the flow
     i -> i+1 (fit_video.py:249: frame i+1 is fitted with flow_paths[i]) and the occlusion mask that
     fit_video.py:248 reads for it (img_occ_paths[i-1]).
@@ -241,11 +269,16 @@ def load_sequence(sequence_path, resize=None, frame_start=0, frame_range=-1, ski
     ``decode``: "host" opens every image file with PIL; "device" (needs ``device``) decodes the JPEG files that
     gflow_amd.video.parse_jpeg accepts in one gflow_amd.video.decode_jpeg call per shape -- the same bits, so the frames are
     the same tensors -- and leaves PNGs and refused JPEGs to PIL, with one warning per clip that says how many.  A video
-    file's frames (``sequence_path`` a ``.avi`` file) are always decoded on the device: without ``device`` it raises."""
+    file's frames (``sequence_path`` a ``.avi`` file) are always decoded on the device: without ``device`` it raises.
+    ``object_masks``: "none" (the default) leaves the frames as they are; "files" reads ``<seq>_mask/*.png``, sliced like
+    the other per-frame files, into ``frames[i]["object_mask"]`` -- (H, W) uint8 ids (``read_object_mask``: resized nearest
+    neighbour, never blurred; on ``device`` if there is one) -- which is None for a frame without a file."""
     given = dict(decode=decode, occ_masks=occ_masks, move_masks=move_masks, flows=flows, depth_camera=depth_camera)
     for name, (a, b) in _OPTIONS.items():
         if given[name] not in (a, b):
             raise ValueError(f"load_sequence: {name} must be \"{a}\" or \"{b}\", got {given[name]!r}")
+    if object_masks not in ("none", "files"):
+        raise ValueError(f"load_sequence: object_masks must be \"none\" or \"files\", got {object_masks!r}")
     if decode == "device" and device is None:
         raise ValueError("load_sequence: decode=\"device\" needs device=")
     if is_video(sequence_path) and device is None:
@@ -266,6 +299,10 @@ def load_sequence(sequence_path, resize=None, frame_start=0, frame_range=-1, ski
                     decode, dev)
     prep = _HostPrep(resize, blur, depth_offset) if device is None else _DevicePrep(dev, resize, blur, depth_offset)
     frames = _assemble(clip, prep)
+    if object_masks == "files":
+        for fr, path in zip(frames, clip.objects + [None] * len(frames)):
+            ids = None if path is None else read_object_mask(path, resize)
+            fr["object_mask"] = ids if ids is None or device is None else ids.to(dev)
     if move_masks == "epipolar":
         from .move_seg import clip_move_masks
         clip_move_masks(frames, n_flows=len(clip.fwd))
@@ -286,6 +323,7 @@ class _Clip:
     focal: float
     pp: list
     poses: np.ndarray
+    objects: list = None                           # the slice's <seq>_mask files (paths; read only when asked for)
 
 
 def _resolve(sequence_path, frame_start, frame_range, skip_interval, move_masks, occ_masks, flows, depth_camera, focal, decode,
@@ -350,7 +388,8 @@ def _resolve(sequence_path, frame_start, frame_range, skip_interval, move_masks,
     else:
         depth = [np.load(p["depth"][i]) for i in range(n)]
         focal, pp, poses = read_camera(p["camera"])
-    return _Clip([_frame_name(ip) for ip in p["img"]], [decoded[i] for i in mine], fwd, bwd, depth, move, occ, focal, pp, poses)
+    return _Clip([_frame_name(ip) for ip in p["img"]], [decoded[i] for i in mine], fwd, bwd, depth, move, occ, focal, pp, poses,
+                 list(p["objects"][:n]))
 
 
 def _exclusions(fwd, move, occ, checked, epipolar):

@@ -116,7 +116,8 @@ typedef enum gfl_status {
  * number stays; a binding that needs it looks the symbol up).  gfl_track_history, gfl_track_backward and
  * gfl_track_backward_workspace_bytes were added WITHIN 312 in the same way, and so were gfl_track_vis and gfl_prep_frames with
  * their workspace queries, the four gfl_jpeg_* entries, and gfl_optflow, gfl_optflow_level, gfl_optflow_workspace_bytes,
- * the seven gfl_sfm_* entries and gfl_selftest_block_scan.  A binding checks gfl_version() >= GFL_VERSION of the header it was written for. */
+ * the seven gfl_sfm_* entries, gfl_selftest_block_scan and gfl_label_frame, gfl_label_assign.  A binding checks
+ * gfl_version() >= GFL_VERSION of the header it was written for. */
 #define GFL_VERSION 312
 int gfl_version(void);
 /* out[10] = TILE, NEAREST, EXTENT, FOV_CLAMP, LOWPASS, EIG_FLOOR, RADIUS_SIGMA, ALPHA_MIN, ALPHA_MAX, T_MIN of this build */
@@ -709,6 +710,38 @@ int gfl_flow_pair(const float* rec_a, int n_a, const int32_t* ids, const int32_t
                   int uv_b_stride, const float* depth_b, int depth_b_stride, int n_b, const float* gt_flow,
                   const uint8_t* move_mask, int W, int H, float min_weight, int pair, int n_pairs, double* sums,
                   float* flow_out, uint8_t* valid_out, void* workspace, size_t workspace_bytes, gfl_stream_t stream);
+
+/* ---- object labels through a clip fit (additive within 312; gflow_amd/propagation.py, INTEGRATION.md "Object propagation") ---------------
+ * gfl_label_frame: the label map the labelled splats of one frame imply.  rec, n, ids, tile_range: what gfl_flow_pair takes
+ * for frame A -- the fit records [n][12] float32, 16-byte aligned (only columns 0..5 are read), and the depth-sorted tile
+ * lists, tile_range [T][2] = start / end into ids, T = ceil(W / 16) * ceil(H / 16) (the lists may lie anywhere in ids, with
+ * anything between them).  labels: uint8 [n_labels], 0 <= n_labels <= n; row j is LABELLED iff j < n_labels and
+ * labels[j] < K; 255 is the canonical "unlabelled", any value >= K counts the same.  K: the number of classes, background
+ * class 0 included, 2 <= K <= 16.
+ * Every pixel (x, y), sampled at (x + GFL_PIXEL_CENTER, y + GFL_PIXEL_CENTER), walks its tile's list front to back under
+ * the rule of gfl_blend_fwd: power > 0 skips; alpha = min(GFL_ALPHA_MAX, o G); alpha < GFL_ALPHA_MIN skips; the walk stops
+ * BEFORE adding when T (1 - alpha) < GFL_T_MIN.  With w = alpha T a labelled row adds acc[label] += w (one float32 add);
+ * an unlabelled row adds nothing, but occludes like any other: T *= 1 - alpha always.
+ *   den = ((acc[0] + acc[1]) + ...) + acc[K - 1].  If den >= min_weight the pixel's label is the smallest k with the largest
+ *   acc[k] and conf = acc[k] / den (float32); else the label is `unknown` (0 .. 255) and conf = 0.
+ * label_out [H][W] uint8: written for every pixel.  conf_out [H][W] float32: written for every pixel, or NULL.
+ * GFL_ERR_INVALID, before anything is launched: K outside [2, 16], min_weight outside (0, 1], W or H < 1, more than 16384
+ * tiles, n < 0, n_labels outside [0, n], unknown outside [0, 255], a null or misaligned pointer that is needed (label_out
+ * always; rec, ids, tile_range for n > 0; labels for n_labels > 0).  n == 0 is GFL_OK: every pixel is `unknown`, the lists
+ * are not read.
+ * One launch (a workgroup per tile), no atomics and no sums across lanes: the same bits on every call, in every mode.  No
+ * allocation, no host synchronisation; callable on the fit's stream between graph replays.
+ *
+ * gfl_label_assign: unlabelled rows take the label of the pixel they sit on.  labels_inout: uint8 [n].  For every row
+ * j < n with labels_inout[j] == 255: u = rec[j][0], v = rec[j][1], depth = rec[j][9]; if depth != 0 and 0 < u < W - 1 and
+ * 0 < v < H - 1 (false for a NaN), m = map[(int)v][(int)u] (truncation), and if m != 255, labels_inout[j] = m.  Everything
+ * else is left as it is.  map: [H][W] uint8 -- the first frame's annotation (the mask prompt), or a later frame's
+ * label_out (inheritance: appended rows and rows that have just come into view).  rec needs 4-byte alignment only.
+ * GFL_ERR_INVALID: W or H < 1, n < 0, a null pointer for n > 0.  n == 0 is GFL_OK.  One launch, a lane per row. */
+int gfl_label_frame(const float* rec, int n, const int32_t* ids, const int32_t* tile_range, const uint8_t* labels,
+                    int n_labels, int K, int W, int H, float min_weight, int unknown, uint8_t* label_out, float* conf_out,
+                    gfl_stream_t stream);
+int gfl_label_assign(const float* rec, int n, const uint8_t* map, int W, int H, uint8_t* labels_inout, gfl_stream_t stream);
 
 /* ---- move masks from the flow (312; gflow_amd/move_seg.py, INTEGRATION.md "Move masks from the flow") ------------------
  * What the reference's utility/move_seg.py makes of a forward flow: a fundamental matrix by least median of squares, the
