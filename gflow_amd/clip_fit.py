@@ -277,32 +277,30 @@ class ClipFit:
             if keep is not None and keep.get("record_track_inputs"):
                 keep.setdefault("track_inputs", []).append((uv.clone(), depth.clone(), dm.clone()))
 
-    def record_flow(self, i):
-        # frame i's final records and sorted tile lists go to the flow recorder (on the operator path the five operators'
-        # outputs, packed).  From frame 1 on one gfl_flow_pair for the pair (i - 1, i); nothing is read back
+    def final_state(self):
+        # (rec, n, ids, tile_range) of THIS frame's final state, the fit records and sorted tile lists: the second engine's
+        # after final_forward (shared), on the operator path the five operators' outputs, packed -- one more rasterisation
+        # for every reader that asks (nothing is kept between them)
         tr = self.tr
+        if tr.engine_current:
+            aux, _ = self.final_forward()
+            return aux.rec, aux.N, aux.ids, aux.tile_range
+        state = FL.operator_state(tr._input_group(detach=True))
+        tr.rasterisations_done += 1
+        return state
+
+    def record_flow(self, i):
+        # frame i's final state goes to the flow recorder.  From frame 1 on one gfl_flow_pair for the pair (i - 1, i);
+        # nothing is read back
         with torch.no_grad():
-            if tr.engine_current:
-                aux, _ = self.final_forward()
-                rec, n, ids, tile_range = aux.rec, aux.N, aux.ids, aux.tile_range
-            else:
-                rec, n, ids, tile_range = FL.operator_state(tr._input_group(detach=True))
-                tr.rasterisations_done += 1
             prev = self.frames[i - 1] if i else None
-            self.flow_rec.frame(i, rec, n, ids, tile_range, prev["flow"] if prev else None, prev["move_mask"] if prev else None)
+            self.flow_rec.frame(i, *self.final_state(), prev["flow"] if prev else None, prev["move_mask"] if prev else None)
 
     def record_objects(self, i):
-        # frame i's final records and sorted tile lists go to the object recorder, as they go to the flow recorder: the id map
-        # of the frame from one gfl_label_frame, ids for the rows that have none; nothing is read back
-        tr = self.tr
+        # frame i's final state goes to the object recorder, as it goes to the flow recorder: the id map of the frame from
+        # one gfl_label_frame, ids for the rows that have none; nothing is read back
         with torch.no_grad():
-            if tr.engine_current:
-                aux, _ = self.final_forward()
-                rec, n, ids, tile_range = aux.rec, aux.N, aux.ids, aux.tile_range
-            else:
-                rec, n, ids, tile_range = FL.operator_state(tr._input_group(detach=True))
-                tr.rasterisations_done += 1
-            self.object_rec.frame(i, rec, n, ids, tile_range)
+            self.object_rec.frame(i, *self.final_state())
 
     def record_scores(self, i):
         # benchmark.py:191-230 and :323-329 for frame i, on what the frame's PSNR is taken from and what save_checkpoint

@@ -6,11 +6,9 @@
 // The tile's depth-sorted splat list is staged through LDS 256 records at a time
 // (three wide LDS reads per splat, all lanes the same address = broadcast).
 #include "gfl_common.hpp"
-#include "gfl_splat_alpha.hpp"   // splat_alpha: the blend rule, shared with gfl_flow.hip
+#include "gfl_splat_alpha.hpp"   // splat_alpha, WALK_BATCH: the blend rule, shared with gfl_flow.hip and gfl_label.hip
 
 namespace gfl {
-
-constexpr int BLEND_BATCH = 256;
 
 struct SplatRec {            // 40 bytes + pad: what a pixel needs from one splat
     float4 p0;               // u, v, conic a, conic b
@@ -40,7 +38,7 @@ __global__ void __launch_bounds__(256) blend_fwd_kernel(const float* __restrict_
                                                         const int32_t* __restrict__ tile_range, float bg, int W, int H,
                                                         int gx, float* __restrict__ out, float* __restrict__ final_T,
                                                         int32_t* __restrict__ n_contrib) {
-    __shared__ SplatRec recs[BLEND_BATCH];
+    __shared__ SplatRec recs[WALK_BATCH];
     const int tile = blockIdx.x;
     const int tx = tile % gx, ty = tile / gx;
     const int tid = threadIdx.x;
@@ -55,12 +53,16 @@ __global__ void __launch_bounds__(256) blend_fwd_kernel(const float* __restrict_
     int last = 0;
     bool done = !inside;
 
-    for (int base = start; base < end; base += BLEND_BATCH) {
+    // operator_tile_walk (gfl_splat_alpha.hpp) written out: with the sums added inside a callable the compiler lays this
+    // loop out differently, 0.4 - 0.8 % slower at one, three and four channels (480 x 854, 60 000 splats).  A change
+    // to the stop rule or to the arithmetic of a pixel is made in both; tests/test_gpu_operator_walk.py holds the flow
+    // and label kernels, which run the shared walk, to this loop bit for bit.
+    for (int base = start; base < end; base += WALK_BATCH) {
         if (__syncthreads_and(done)) break;
         const int idx = base + tid;
         if (idx < end) stage_splat<C>(&recs[tid], ids[idx], uv, conic, opacity, feature, C_total, c0);
         __syncthreads();
-        const int cnt = min(BLEND_BATCH, end - base);
+        const int cnt = min(WALK_BATCH, end - base);
         if (!done) {
             for (int j = 0; j < cnt; ++j) {
                 const float4 p0 = recs[j].p0;
@@ -103,8 +105,8 @@ __global__ void __launch_bounds__(256) blend_bwd_kernel(const float* __restrict_
                                                         const float* __restrict__ d_out, float* __restrict__ d_uv,
                                                         float* __restrict__ d_conic, float* __restrict__ d_opacity,
                                                         float* __restrict__ d_feature) {
-    __shared__ SplatRec recs[BLEND_BATCH];
-    __shared__ int32_t rec_id[BLEND_BATCH];
+    __shared__ SplatRec recs[WALK_BATCH];
+    __shared__ int32_t rec_id[WALK_BATCH];
     const int tile = blockIdx.x;
     const int tx = tile % gx, ty = tile / gx;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -142,7 +144,7 @@ __global__ void __launch_bounds__(256) blend_bwd_kernel(const float* __restrict_
     __syncthreads();
     const int depth_n = min(total, (int)s_max_last);
 
-    for (int r0 = 0; r0 < depth_n; r0 += BLEND_BATCH) {
+    for (int r0 = 0; r0 < depth_n; r0 += WALK_BATCH) {
         // stage list positions depth_n-1-r0 ... downwards; slot j <-> position depth_n-1-r0-j
         const int pos_t = depth_n - 1 - r0 - tid;
         __syncthreads();
@@ -152,7 +154,7 @@ __global__ void __launch_bounds__(256) blend_bwd_kernel(const float* __restrict_
             stage_splat<C>(&recs[tid], gid, uv, conic, opacity, feature, C_total, c0);
         }
         __syncthreads();
-        const int cnt = min(BLEND_BATCH, depth_n - r0);
+        const int cnt = min(WALK_BATCH, depth_n - r0);
         for (int j = 0; j < cnt; ++j) {
             const int pos = depth_n - 1 - r0 - j;  // 0-based list position
             const float4 p0 = recs[j].p0;

@@ -28,6 +28,7 @@ inline int check(hipError_t e) {
 }
 
 constexpr int WAVE = 64;
+constexpr int REC = 12;   // floats per rec row (the fit's layout: gfl_fit.hpp)
 
 // where pixel p is sampled (include/gflow_hip.h: GFL_PIXEL_CENTER).  With the default 0 this is (float)p and the kernels are
 // instruction for instruction what they were without the constant.
@@ -253,6 +254,11 @@ __device__ __forceinline__ int wave_min(int v) {
     return v;
 }
 __device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {       // fixed shape: every lane ends with the same bits
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
     return v;

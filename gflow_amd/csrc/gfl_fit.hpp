@@ -39,8 +39,7 @@ static_assert(RBIN_BLOCK == 256 || RBIN_BLOCK == 512, "two scale-row partials pe
 #define GFL_WIDE_TILES 16
 #endif
 constexpr int WIDE_TILES = GFL_WIDE_TILES;   // splats covering more tiles are binned by a whole wave
-constexpr int ROW = 16;   // floats per params row
-constexpr int REC = 12;   // floats per rec row
+constexpr int ROW = 16;   // floats per params row (REC, floats per rec row: gfl_common.hpp)
 #ifndef GFL_PG_STRIDE
 #define GFL_PG_STRIDE 12
 #endif

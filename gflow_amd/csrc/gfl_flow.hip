@@ -1,14 +1,14 @@
 // Dense optical flow of a frame pair and its end-point error (gfl_flow_pair; include/gflow_hip.h, gflow_amd/flow.py).
 //
 // The motion field the fitted splats imply from frame A to frame B, on A's pixel grid: every pixel walks A's sorted tile
-// list front to back under exactly the operator blend's rule (splat_alpha of gfl_splat_alpha.hpp, the T_MIN stop before
-// adding, pixf()) with the splat's own motion d = uv_B - uv_A as the feature,
+// list front to back under exactly the operator blend's rule (operator_tile_walk of gfl_splat_alpha.hpp, the blend's own
+// loop) with the splat's own motion d = uv_B - uv_A as the feature,
 //   w = alpha T;   num += w d, den += w   for rows that still exist in B (row < n_b, depth_b != 0);   T *= 1 - alpha always
 // and F = num / den where den >= min_weight.  Against gt_flow the end-point error in float64, summed per class of
 // move_mask.
 //
 // Launch 1: one workgroup (4 wave64) per 16x16 tile, A WAVE OWNS AN 8x8 BLOCK as in blend_fwd_kernel; the tile's list is
-// staged through LDS FLOW_BATCH records at a time (two wide LDS reads and a narrow one per splat, all lanes the same address
+// staged through LDS WALK_BATCH records at a time (two wide LDS reads and a narrow one per splat, all lanes the same address
 // = broadcast).  The counts of a wave are popcounts of ballots, its epe sum a fixed xor tree over the lanes; the four waves'
 // 18 numbers are added in wave order and stored as the tile's row of the workspace.  Launch 2: one workgroup, thread t
 // adds the rows t, t + 256, ... in that order, thread k < 18 then adds the 256 partial sums of number k in thread order.
@@ -19,50 +19,34 @@
 
 namespace gfl {
 
-constexpr int FLOW_BATCH = 256;
-constexpr int FLOW_REC = 12;                        // floats per fit record (gfl_fit.hpp REC)
 constexpr int FLOW_NV = 18;                         // 3 classes x {n_pixels, n_valid, epe_sum, n<1, n<3, n<5}
-constexpr int FLOW_MAX_TILES = 16384;
-
-__device__ __forceinline__ double wave_sum_f64(double v) {       // fixed shape: every lane ends with the same bits
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 __global__ void __launch_bounds__(256) flow_pair_kernel(
         const float* __restrict__ rec_a, int n_a, const int32_t* __restrict__ ids, const int32_t* __restrict__ tile_range,
         const float* __restrict__ uv_b, int uv_b_stride, const float* __restrict__ depth_b, int depth_b_stride, int n_b,
         const float* __restrict__ gt_flow, const uint8_t* __restrict__ move_mask, int W, int H, int gx, float min_weight,
         double* __restrict__ partial, float* __restrict__ flow_out, uint8_t* __restrict__ valid_out) {
-    __shared__ float4 s_p0[FLOW_BATCH];             // u, v, conic a, conic b
-    __shared__ float4 s_p1[FLOW_BATCH];             // conic c, opacity, dx, dy
-    __shared__ float s_has[FLOW_BATCH];             // 1: the row has a future, 0: it only occludes
+    __shared__ float4 s_p0[WALK_BATCH];             // u, v, conic a, conic b
+    __shared__ float4 s_p1[WALK_BATCH];             // conic c, opacity, dx, dy
+    __shared__ float s_has[WALK_BATCH];             // 1: the row has a future, 0: it only occludes
     __shared__ double s_red[4][FLOW_NV];
     const int tile = blockIdx.x;
     const int tx = tile % gx, ty = tile / gx;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const auto [lx, ly, px, py, inside] = tile_pixel(tx, ty, W, H);
     const float fx = pixf(px), fy = pixf(py);
-    int start = 0, end = 0;
-    if (n_a > 0) {
-        start = tile_range[2 * tile];
-        end = tile_range[2 * tile + 1];
-    }
+    const auto [start, end] = list_range(tile_range, tile, n_a);
 
     float T = 1.f, nx = 0.f, ny = 0.f, den = 0.f;
-    bool done = !inside;
-    for (int base = start; base < end; base += FLOW_BATCH) {
-        if (__syncthreads_and(done)) break;
-        const int idx = base + tid;
-        if (idx < end) {
+    operator_tile_walk(
+        start, end, inside, fx, fy, T,
+        [&](int idx, int slot) {
             const int g = ids[idx];
             float4 p0 = make_float4(0.f, 0.f, 0.f, 0.f), p1 = make_float4(0.f, 0.f, 0.f, 0.f);      // (opacity 0: skipped)
             float has = 0.f;
             if ((unsigned)g < (unsigned)n_a) {
-                const float* r = rec_a + (size_t)g * FLOW_REC;
-                p0 = *reinterpret_cast<const float4*>(r);
-                const float2 co = *reinterpret_cast<const float2*>(r + 4);
+                float2 co;
+                fit_record_head(rec_a, g, p0, co);
                 float dx = 0.f, dy = 0.f;
                 if (g < n_b && depth_b[(size_t)g * depth_b_stride] != 0.f) {
                     const float* q = uv_b + (size_t)g * uv_b_stride;
@@ -72,30 +56,18 @@ __global__ void __launch_bounds__(256) flow_pair_kernel(
                 }
                 p1 = make_float4(co.x, co.y, dx, dy);
             }
-            s_p0[tid] = p0;
-            s_p1[tid] = p1;
-            s_has[tid] = has;
-        }
-        __syncthreads();
-        const int cnt = min(FLOW_BATCH, end - base);
-        if (!done) {
-            for (int j = 0; j < cnt; ++j) {
-                const float4 p0 = s_p0[j];
-                const float4 p1 = s_p1[j];
-                float alpha, G;
-                if (!splat_alpha(p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, fx, fy, alpha, G)) continue;
-                const float test_T = T * (1.f - alpha);
-                if (test_T < GFL_T_MIN) { done = true; break; }
-                const float w = alpha * T;
-                if (s_has[j] != 0.f) {              // (the same for every lane)
-                    nx = fmaf(w, p1.z, nx);
-                    ny = fmaf(w, p1.w, ny);
-                    den += w;
-                }
-                T = test_T;
+            s_p0[slot] = p0;
+            s_p1[slot] = p1;
+            s_has[slot] = has;
+        },
+        [&](int j, float4& p0, float4& p1) { p0 = s_p0[j]; p1 = s_p1[j]; },
+        [&](int j, float w, const float4& p1, int) {
+            if (s_has[j] != 0.f) {                  // (the same for every lane)
+                nx = fmaf(w, p1.z, nx);
+                ny = fmaf(w, p1.w, ny);
+                den += w;
             }
-        }
-    }
+        });
 
     // the pixel's flow, its error and its class
     const size_t pix = inside ? (size_t)py * W + px : 0;
@@ -169,7 +141,7 @@ extern "C" {
 size_t gfl_flow_workspace_bytes(int W, int H) {
     if (W < 1 || H < 1) return 0;
     const size_t tiles = tile_grid(W, H).tiles();
-    if (tiles > (size_t)FLOW_MAX_TILES) return 0;
+    if (tiles > (size_t)LIST_MAX_TILES) return 0;
     return tiles * FLOW_NV * sizeof(double);
 }
 
@@ -183,10 +155,9 @@ int gfl_flow_pair(const float* rec_a, int n_a, const int32_t* ids, const int32_t
     const size_t need = gfl_flow_workspace_bytes(W, H);
     if (need == 0) return GFL_ERR_INVALID;                                                // more than 16384 tiles
     if (!gt_flow || !sums || !workspace || workspace_bytes < need) return GFL_ERR_INVALID;
-    if (n_a > 0 && (!rec_a || !ids || !tile_range)) return GFL_ERR_INVALID;
+    if (!list_state_ok(rec_a, n_a, ids, tile_range)) return GFL_ERR_INVALID;
     if (n_a > 0 && n_b > 0 && (!uv_b || !depth_b)) return GFL_ERR_INVALID;
-    if (((uintptr_t)rec_a & 15) || ((uintptr_t)gt_flow & 7) || ((uintptr_t)flow_out & 7) || ((uintptr_t)workspace & 7))
-        return GFL_ERR_INVALID;                                                           // (rows are read as float4 + float2)
+    if (((uintptr_t)gt_flow & 7) || ((uintptr_t)flow_out & 7) || ((uintptr_t)workspace & 7)) return GFL_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const auto [gx, gy, tiles] = tile_grid(W, H);
     double* partial = (double*)workspace;

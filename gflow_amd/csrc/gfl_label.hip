@@ -1,12 +1,12 @@
 // Object labels through a clip fit (gfl_label_frame, gfl_label_assign; include/gflow_hip.h, gflow_amd/propagation.py).
 //
 // gfl_label_frame: the label map the labelled splats of one frame imply.  Every pixel walks its tile's sorted list front to
-// back under exactly the operator blend's rule (splat_alpha of gfl_splat_alpha.hpp, the T_MIN stop before adding, pixf()),
-// as flow_pair_kernel does, with the splat's class as the feature:
+// back under exactly the operator blend's rule (operator_tile_walk of gfl_splat_alpha.hpp, the blend's own loop), as
+// flow_pair_kernel does, with the splat's class as the feature:
 //   w = alpha T;   acc[label] += w   for rows that carry a label;   T *= 1 - alpha always
 // and the pixel's label is the class of the largest sum where the sums together reach min_weight.
 //
-// One workgroup (4 wave64) per 16x16 tile, A WAVE OWNS AN 8x8 BLOCK; the tile's list is staged through LDS LABEL_BATCH
+// One workgroup (4 wave64) per 16x16 tile, A WAVE OWNS AN 8x8 BLOCK; the tile's list is staged through LDS WALK_BATCH
 // records at a time: two wide LDS reads per splat (all lanes the same address = broadcast), the label -- already resolved
 // to "a class below K, or 255" -- rides in the second one.  Within a step of the walk the label is the same for every
 // lane: it is moved to a scalar register and the accumulator is chosen by a UNIFORM branch over unrolled cases, so the
@@ -20,9 +20,6 @@
 
 namespace gfl {
 
-constexpr int LABEL_BATCH = 256;
-constexpr int LABEL_REC = 12;                       // floats per fit record (gfl_fit.hpp REC)
-constexpr int LABEL_MAX_TILES = 16384;
 constexpr int LABEL_NONE = 255;                     // the canonical "unlabelled"
 constexpr int LABEL_MAX_K = 16;
 
@@ -45,58 +42,38 @@ __global__ void __launch_bounds__(256) label_frame_kernel(
         const float* __restrict__ rec, int n, const int32_t* __restrict__ ids, const int32_t* __restrict__ tile_range,
         const uint8_t* __restrict__ labels, int n_labels, int K, int W, int H, int gx, float min_weight, int unknown,
         uint8_t* __restrict__ label_out, float* __restrict__ conf_out) {
-    __shared__ float4 s_p0[LABEL_BATCH];            // u, v, conic a, conic b
-    __shared__ float4 s_p1[LABEL_BATCH];            // conic c, opacity, the label (an int's bits), -
+    __shared__ float4 s_p0[WALK_BATCH];             // u, v, conic a, conic b
+    __shared__ float4 s_p1[WALK_BATCH];             // conic c, opacity, the label (an int's bits), -
     const int tile = blockIdx.x;
     const int tx = tile % gx, ty = tile / gx;
-    const int tid = threadIdx.x;
     const auto [lx, ly, px, py, inside] = tile_pixel(tx, ty, W, H);
     const float fx = pixf(px), fy = pixf(py);
-    int start = 0, end = 0;
-    if (n > 0) {
-        start = tile_range[2 * tile];
-        end = tile_range[2 * tile + 1];
-    }
+    const auto [start, end] = list_range(tile_range, tile, n);
 
     float T = 1.f;
     float acc[KMAX];
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) acc[k] = 0.f;
-    bool done = !inside;
-    for (int base = start; base < end; base += LABEL_BATCH) {
-        if (__syncthreads_and(done)) break;
-        const int idx = base + tid;
-        if (idx < end) {
+    operator_tile_walk(
+        start, end, inside, fx, fy, T,
+        [&](int idx, int slot) {
             const int g = ids[idx];
             float4 p0 = make_float4(0.f, 0.f, 0.f, 0.f);                                             // (opacity 0: skipped)
             float4 p1 = make_float4(0.f, 0.f, __int_as_float(LABEL_NONE), 0.f);
             if ((unsigned)g < (unsigned)n) {
-                const float* r = rec + (size_t)g * LABEL_REC;
-                p0 = *reinterpret_cast<const float4*>(r);
-                const float2 co = *reinterpret_cast<const float2*>(r + 4);
+                float2 co;
+                fit_record_head(rec, g, p0, co);
                 int lab = g < n_labels ? (int)labels[g] : LABEL_NONE;
                 if (lab >= K) lab = LABEL_NONE;
                 p1 = make_float4(co.x, co.y, __int_as_float(lab), 0.f);
             }
-            s_p0[tid] = p0;
-            s_p1[tid] = p1;
-        }
-        __syncthreads();
-        const int cnt = min(LABEL_BATCH, end - base);
-        if (!done) {
-            for (int j = 0; j < cnt; ++j) {
-                const float4 p0 = s_p0[j];
-                const float4 p1 = s_p1[j];
-                float alpha, G;
-                if (!splat_alpha(p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, fx, fy, alpha, G)) continue;
-                const float test_T = T * (1.f - alpha);
-                if (test_T < GFL_T_MIN) { done = true; break; }
-                const float w = alpha * T;
-                add_to_class<KMAX>(acc, __builtin_amdgcn_readfirstlane(__float_as_int(p1.z)), w);     // (the same for every lane)
-                T = test_T;
-            }
-        }
-    }
+            s_p0[slot] = p0;
+            s_p1[slot] = p1;
+        },
+        [&](int j, float4& p0, float4& p1) { p0 = s_p0[j]; p1 = s_p1[j]; },
+        [&](int, float w, const float4& p1, int) {
+            add_to_class<KMAX>(acc, __builtin_amdgcn_readfirstlane(__float_as_int(p1.z)), w);         // (the same for every lane)
+        });
 
     if (!inside) return;
     float den = 0.f, best = 0.f;
@@ -119,7 +96,7 @@ __global__ void __launch_bounds__(256) label_assign_kernel(const float* __restri
                                                            uint8_t* __restrict__ labels) {
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= n || labels[j] != LABEL_NONE) return;
-    const float* r = rec + (size_t)j * LABEL_REC;
+    const float* r = rec + (size_t)j * REC;
     const float u = r[0], v = r[1], depth = r[9];
     // geometry.within: strict on both sides, false for NaN
     if (depth != 0.f && u > 0.f && u < (float)(W - 1) && v > 0.f && v < (float)(H - 1)) {
@@ -141,12 +118,11 @@ int gfl_label_frame(const float* rec, int n, const int32_t* ids, const int32_t* 
     if (!(min_weight > 0.f && min_weight <= 1.f)) return GFL_ERR_INVALID;                 // (a NaN is refused too)
     if (unknown < 0 || unknown > 255) return GFL_ERR_INVALID;
     const TileGrid grid = tile_grid(W, H);
-    if (grid.tiles() > (size_t)LABEL_MAX_TILES) return GFL_ERR_INVALID;
+    if (grid.tiles() > (size_t)LIST_MAX_TILES) return GFL_ERR_INVALID;
     if (!label_out) return GFL_ERR_INVALID;
-    if (n > 0 && (!rec || !ids || !tile_range)) return GFL_ERR_INVALID;
+    if (!list_state_ok(rec, n, ids, tile_range)) return GFL_ERR_INVALID;
     if (n_labels > 0 && !labels) return GFL_ERR_INVALID;
-    if (((uintptr_t)rec & 15) || ((uintptr_t)ids & 3) || ((uintptr_t)tile_range & 3) || ((uintptr_t)conf_out & 3))
-        return GFL_ERR_INVALID;                                                           // (rows are read as float4 + float2)
+    if ((uintptr_t)conf_out & 3) return GFL_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
 #define GFL_LABEL_LAUNCH(KMAX)                                                                                   \
     label_frame_kernel<KMAX><<<grid.T, 256, 0, s>>>(rec, n, ids, tile_range, labels, n_labels, K, W, H, grid.gx, \

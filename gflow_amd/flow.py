@@ -16,11 +16,11 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .fused import REC, check_list_state, tile_count
 
 CLASSES = ("all", "still", "moving")
 SUM_NAMES = ("n_pixels", "n_valid", "epe_sum", "n_1px", "n_3px", "n_5px")
 UNKNOWN_FLOW = 1e10               # Middlebury's mark of a pixel without a flow (both components), as written to .flo
-REC = 12                          # floats per fit record (fused.REC)
 
 
 def pack_records(uv, conic, opacity, depth):
@@ -74,7 +74,7 @@ class FlowRecorder:
         self.min_weight = float(min_weight)
         self.device = torch.device(device)
         self.P = self.T - 1
-        self.tiles = ((self.W + 15) // 16) * ((self.H + 15) // 16)
+        self.tiles = tile_count(self.W, self.H)
         self.sums = torch.zeros((max(self.P, 1), 3, 6), dtype=torch.float64, device=self.device)
         L.need_device(self.sums)
         need = L.load().gfl_flow_workspace_bytes(self.W, self.H)
@@ -108,11 +108,7 @@ class FlowRecorder:
         i, n = int(i), int(n)
         if i != self._last + 1 or i >= self.T:
             raise ValueError(f"FlowRecorder.frame: frame {i} after frame {self._last} of {self.T}")
-        L.need_device(rec, ids, tile_range)
-        if rec.dtype != torch.float32 or rec.dim() != 2 or rec.shape[1] != REC or rec.shape[0] < n or not rec.is_contiguous():
-            raise ValueError("FlowRecorder.frame: rec must be a contiguous (>= n, 12) float32 tensor")
-        if ids.dtype != torch.int32 or tile_range.dtype != torch.int32 or tuple(tile_range.shape) != (self.tiles, 2):
-            raise ValueError(f"FlowRecorder.frame: ids and tile_range must be int32, tile_range ({self.tiles}, 2)")
+        check_list_state("FlowRecorder.frame", rec, n, ids, tile_range, self.tiles)      # (ids, tile_range: copied below, any strides)
         if i >= 1:
             if gt_flow is None or tuple(gt_flow.shape) != (self.H, self.W, 2):
                 raise ValueError(f"FlowRecorder.frame: gt_flow must be ({self.H}, {self.W}, 2)")

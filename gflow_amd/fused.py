@@ -12,11 +12,28 @@ import ctypes
 import torch
 
 from . import _lib as L
+from .msplat import tile_grid
 from .pinned import DeferredRead
 
 ROW = 16
-REC = 12
+REC = 12                                   # floats per fit record
 COLS = {"xyz": (0, 3), "scale": (3, 6), "rotate": (6, 10), "opacity": (10, 11), "rgb": (11, 14)}
+
+
+def tile_count(W, H):
+    """the 16 x 16 tiles of a W x H image: the rows of a ``tile_range``"""
+    gx, gy = tile_grid(int(W), int(H))
+    return gx * gy
+
+
+def check_list_state(who, rec, n, ids, tile_range, tiles):
+    """What every taker of a frame's final state asks of it -- ``rec`` (>= n rows of 12 float32: the fit records), ``ids`` /
+    ``tile_range`` (its sorted tile lists, int32, ``tile_range`` (tiles, 2)), all on the device; ``who`` names the caller."""
+    L.need_device(rec, ids, tile_range)
+    if rec.dtype != torch.float32 or rec.dim() != 2 or rec.shape[1] != REC or rec.shape[0] < n or not rec.is_contiguous():
+        raise ValueError(f"{who}: rec must be a contiguous (>= n, 12) float32 tensor")
+    if ids.dtype != torch.int32 or tile_range.dtype != torch.int32 or tuple(tile_range.shape) != (tiles, 2):
+        raise ValueError(f"{who}: ids and tile_range must be int32, tile_range ({tiles}, 2)")
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int32
@@ -182,7 +199,7 @@ class FitEngine:
         if self.dev.type != "cuda":
             raise RuntimeError("FitEngine needs a HIP device (there is no CPU path)")
         self.W, self.H = int(W), int(H)
-        self.gx, self.gy = (self.W + 15) // 16, (self.H + 15) // 16
+        self.gx, self.gy = tile_grid(self.W, self.H)
         self.T = self.gx * self.gy
         self.N = 0
         self.hp = FitHyper(bg=bg, nearest=0.2, extent=1.3, lambda_rgb=1.0, lambda_depth=0.0, lambda_var=0.0,

@@ -25,10 +25,10 @@ import torch
 
 from . import _lib as L
 from . import segmentation as SG
+from .fused import check_list_state, tile_count
 
 UNKNOWN = 255                     # a map pixel without a label; a splat without one
 MAX_ID = 15                       # gfl_label_frame composites at most 16 classes
-REC = 12                          # floats per fit record (fused.REC)
 
 
 def _id_map(a, H, W, what):
@@ -62,7 +62,7 @@ class ObjectRecorder:
             raise ValueError("ObjectRecorder: the prompt has no object (no non-zero id)")
         self.K = top + 1
         self.min_weight = float(min_weight)
-        self.tiles = ((self.W + 15) // 16) * ((self.H + 15) // 16)
+        self.tiles = tile_count(self.W, self.H)
         if self.tiles > 16384:
             raise ValueError(f"ObjectRecorder: {self.W} x {self.H} has more than 16384 tiles")
         self.radius = SG.bound_pix(self.H, self.W)
@@ -94,11 +94,7 @@ class ObjectRecorder:
             raise ValueError(f"ObjectRecorder.frame: frame {i} after frame {self._last} of {self.T}")
         if n < self._n:
             raise ValueError(f"ObjectRecorder.frame: {n} rows after {self._n} (rows are only ever appended)")
-        L.need_device(rec, ids, tile_range)
-        if rec.dtype != torch.float32 or rec.dim() != 2 or rec.shape[1] != REC or rec.shape[0] < n or not rec.is_contiguous():
-            raise ValueError("ObjectRecorder.frame: rec must be a contiguous (>= n, 12) float32 tensor")
-        if ids.dtype != torch.int32 or tile_range.dtype != torch.int32 or tuple(tile_range.shape) != (self.tiles, 2):
-            raise ValueError(f"ObjectRecorder.frame: ids and tile_range must be int32, tile_range ({self.tiles}, 2)")
+        check_list_state("ObjectRecorder.frame", rec, n, ids, tile_range, self.tiles)
         if not ids.is_contiguous() or not tile_range.is_contiguous():
             raise ValueError("ObjectRecorder.frame: ids and tile_range must be contiguous")
         lib = L.load()

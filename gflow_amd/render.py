@@ -12,6 +12,7 @@ import torch
 from . import _lib as L
 from . import msplat
 from .color import apply_float_colormap
+from .fused import tile_count
 from .pinned import DeferredRead
 
 FUSED_TYPES = frozenset(("rgb", "uv", "depth", "depth_map"))
@@ -380,7 +381,7 @@ def render_block(block, ranges, intr, extr, bg, W, H, uint8=False, records=False
                 host = torch.tensor([[a, c] for a, c in zip(firsts, counts)], dtype=torch.int32).pin_memory()
                 rows_dev = host.to(dev, non_blocking=True)
         ovf = torch.empty(J, dtype=torch.int32, device=dev)
-        T = ((W + 15) // 16) * ((H + 15) // 16)
+        T = tile_count(W, H)
         k_job = batch_k_cap(max(per_job))
         step = max(1, min(int(BATCH_MAX_JOBS), int(BATCH_MAX_TILES) // T, int(BATCH_MAX_PAIRS) // k_job))
         k_used = 0
@@ -468,7 +469,7 @@ def render_composed(block, labels, job_src, job_s, job_edit, intr, extr, bg, W, 
                                      L.ptr(out_rows), L.ptr(job_rows), L.ptr(flags), L.ptr(buf), buf.numel(), L.stream()),
                 "compose_rows")
         # the composer's rows are the rasteriser's block: R = J * rows_max, job j's range is out_job_rows[j]
-        T = ((W + 15) // 16) * ((H + 15) // 16)
+        T = tile_count(W, H)
         k_job = batch_k_cap(rows_max)
         step = max(1, min(int(BATCH_MAX_JOBS), int(BATCH_MAX_TILES) // T, int(BATCH_MAX_PAIRS) // k_job))
         k_used = 0

@@ -16,6 +16,7 @@ import torch
 
 from . import _lib as L
 from . import color
+from .fused import tile_count
 from .pinned import DeferredRead
 
 STAGE = 256                        # candidates the paint kernel stages at a time (gfl_track_vis.hip: TV_STAGE)
@@ -27,8 +28,7 @@ def default_k_cap(T, N, W, H):
     few pixels touches one to four 16 x 16 tiles; one that jumps across the image touches its whole bounding box), at least
     65536 pairs, never more than every segment in every tile."""
     segs = max(int(T) - 1, 0) * int(N)
-    tiles = ((int(W) + 15) // 16) * ((int(H) + 15) // 16)
-    return max(1, min(segs * tiles, max(65536, 8 * segs)))
+    return max(1, min(segs * tile_count(W, H), max(65536, 8 * segs)))
 
 
 def _as_video(video, dev):
