@@ -49,7 +49,9 @@ def _vis(visible, n):
         raise RuntimeError("msplat: visible must have N elements")
     L.need_device(visible)
     v = visible.reshape(-1)
-    return v.view(torch.uint8) if v.dtype == torch.bool else (v != 0).view(torch.uint8)
+    # (contiguous first: the reshape of a strided view, wide[:, :1] or m[::2], is itself strided, and the kernels read
+    #  N consecutive bytes from the pointer)
+    return (v if v.dtype == torch.bool else v != 0).contiguous().view(torch.uint8)
 
 
 def tile_grid(W, H):

@@ -527,3 +527,56 @@ def test_compute_sh_matches_oracle(K):
     # no mask, empty input
     assert msplat.compute_sh(b_shs.detach(), b_d.detach()).shape == (n, 3)
     assert msplat.compute_sh(torch.zeros(0, K, 3, device="cuda"), torch.zeros(0, 3, device="cuda")).shape == (0, 3)
+
+
+# ------------------------------------------------------------------ visibility masks that are views
+def test_masks_that_are_strided_views():
+    """compute_cov3d, ewa_project and compute_sh take ``visible`` as bytes read with stride 1 from a raw pointer.  A mask that
+    is a strided view -- column 0 of an (N, 2) bool tensor, every second entry of a (2N,) one -- keeps its stride through
+    reshape(-1); read from its base pointer with stride 1 it is another mask (here: mask and complement interleaved).
+    N = 300: one full workgroup and a part; about half the rows invisible.  Outputs and gradients of the three operators
+    with either view are bit-equal to those with ``mask.contiguous()``, and differ from those with the complement."""
+    ms = _ms()
+    n, K = 300, 4
+    s = random_scene(n, 200, 136, seed=17, sigma_px=2.5, behind=0.0)
+    d = to_dev(s)
+    g = torch.Generator().manual_seed(17)
+    uv, depth = ms.project_point(d["xyz"], d["intr"], d["extr"], s["W"], s["H"])
+    seen = (depth != 0).cpu()
+    mask = (torch.rand(n, 1, generator=g) > 0.5) & seen
+    other = ~mask & seen
+    assert 0.3 * n < int(mask.sum()) < 0.7 * n and int(other.sum()) > 0.3 * n
+    wide = torch.cat([mask, ~mask], dim=1).to(DEV)                   # (N, 2): column 0 is the mask
+    long = wide.reshape(-1).clone()                                  # (2N,): the even entries are the mask
+    views = {"wide[:, :1]": wide[:, :1], "long[::2]": long[::2]}
+    for v in views.values():
+        assert not v.is_contiguous() and torch.equal(v.reshape(n, 1).cpu(), mask)
+    cov = ms.compute_cov3d(d["scale"], d["rotate"], depth != 0).detach()
+    shs = torch.randn(n, K, 3, generator=g).to(DEV)
+    dirs = torch.nn.functional.normalize(torch.randn(n, 3, generator=g), dim=1).to(DEV)
+    w_cov, w_con, w_sh = (torch.randn(n, c, generator=g).to(DEV) for c in (6, 3, 3))
+
+    def run(vis):
+        out = []
+        leaves = [t.clone().requires_grad_(True) for t in (d["scale"], d["rotate"])]
+        y = ms.compute_cov3d(*leaves, vis)
+        (y * w_cov).sum().backward()
+        out += [y.detach()] + [t.grad for t in leaves]
+        leaves = [t.clone().requires_grad_(True) for t in (d["xyz"], cov, d["extr"])]
+        conic, radius, tiles = ms.ewa_project(leaves[0], leaves[1], d["intr"], leaves[2], uv, s["W"], s["H"], vis)
+        (conic * w_con).sum().backward()
+        out += [conic.detach(), radius, tiles] + [t.grad for t in leaves]
+        leaves = [t.clone().requires_grad_(True) for t in (shs, dirs)]
+        y = ms.compute_sh(*leaves, vis)
+        (y * w_sh).sum().backward()
+        out += [y.detach()] + [t.grad for t in leaves]
+        return out
+
+    names = ("cov3d", "d_scale", "d_rotate", "conic", "radius", "tiles", "d_xyz", "d_cov3d", "d_extr", "sh", "d_shs", "d_dirs")
+    want = run(mask.to(DEV).contiguous())
+    complement = run(other.to(DEV).contiguous())
+    for name, a, b in zip(names, want, complement):
+        assert not torch.equal(a, b), f"{name}: the mask does not matter"
+    for how, v in views.items():
+        for name, a, b in zip(names, run(v), want):
+            assert torch.equal(a, b), f"{name}: the mask passed as {how} gives another result than its contiguous copy"
