@@ -294,7 +294,11 @@ __global__ void __launch_bounds__(REDUCE_BLOCK) fused_preprocess_bwd_adam_kernel
             const float var = 0.5f * ((s.s[0] - mean) * (s.s[0] - mean) + (s.s[1] - mean) * (s.s[1] - mean) +
                                       (s.s[2] - mean) * (s.s[2] - mean));
             const float sd = sqrtf(var);
-            if (sd != 0.f) {                                // torch masks the 0/0 of std's backward to 0
+            // three equal scales (every splat starts that way, trainer.py:223): the deviation is 0, but (s + s + s) / 3 rounds
+            // to a neighbour of s for four values in ten, and the division by sd blew that residue up to 0.4-0.7 lambda_var / N
+            // per component.  (Every other row keeps the arithmetic, and the bits, it had.)
+            const bool equal = s.s[0] == s.s[1] && s.s[1] == s.s[2];
+            if (sd != 0.f && !equal) {                      // torch masks the 0/0 of std's backward to 0
 #pragma unroll
                 for (int k = 0; k < 3; ++k) g[3 + k] += rc.lambda_var * (s.s[k] - mean) / (2.f * sd);
             }

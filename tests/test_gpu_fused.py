@@ -201,11 +201,14 @@ def test_fused_gradients_under_camera(cam):
         _check_fused_gradients(*only, tag=f"[{cam}, clamped splats only] fused: ")
 
 
-def test_fused_adam_update_matches_torch_adam(setup):
+@pytest.mark.parametrize("lr_camera", [1e-3, 0.0])
+def test_fused_adam_update_matches_torch_adam(setup, lr_camera):
     """Given the fused path's own gradients, the parameter update equals torch.optim.Adam
-    + LinearLR (trainer.py:153,384) over several steps."""
+    + LinearLR (trainer.py:153,384) over several steps -- on both launch orders: with a camera launch behind the per-splat
+    one (lr_camera > 0: it advances the step counter), and without (lr_camera = 0, the first frame and every joint stage:
+    the backward blend's LossTail has advanced the counter already and the per-splat launch reads ``*d_step - 1``)."""
     s, raw, img, dep = setup
-    eng = _engine(raw, s, img, dep, pose=POSE, lr=4e-3, lr_camera=1e-3, total_iters=4, lambda_rgb=1.0,
+    eng = _engine(raw, s, img, dep, pose=POSE, lr=4e-3, lr_camera=lr_camera, total_iters=4, lambda_rgb=1.0,
                   lambda_depth=0.1, lambda_var=10.0)
     n = raw["xyz"].shape[0]
     p = eng.params[:n, :14].clone().cpu().requires_grad_(True)
@@ -219,6 +222,7 @@ def test_fused_adam_update_matches_torch_adam(setup):
         ref.step(); sch.step()
     err = (eng.params[:n, :14].cpu() - p.detach()).abs().max().item()
     assert err < 5e-5, f"Adam trajectories diverge by {err:.2e}"
+    assert int(eng.step.item()) == 6
 
 
 def test_fused_three_steps_track_the_oracle(setup):
@@ -244,7 +248,11 @@ def test_fused_three_steps_track_the_oracle(setup):
 
 
 def test_fused_regularisers_and_masks(setup):
-    """flow / still terms and the gradient-control flags (trainer.py:505-551)."""
+    """The SUM of the render's gradient and the flow term, and the gradient-control flags (trainer.py:505-551), by relative
+    L2 over all rows.  The still term is set but reaches no assertion here: its weights are built from the mask that is also
+    ``row_flags`` bit 0, so the xyz gradient of every row it acts on is zeroed right after it is added (and ``ref_xyz[still]``
+    is zeroed too); the flow term runs with lr_camera = 0, so it forms no pose gradient.  Each term ALONE, its pose
+    gradient, and still weights that differ from the frozen rows: tests/test_gpu_regularisers.py."""
     s, raw, img, dep = setup
     n = raw["xyz"].shape[0]
     g = torch.Generator().manual_seed(9)
