@@ -122,6 +122,10 @@ SIGNATURES = {
     "gfl_jpeg_decode_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int64]),
     "gfl_jpeg_decode": (c_int, [_P, c_int64, _P, c_int64, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "gfl_jpeg_decode_struct_bytes": (c_int, [_P, _P]),
+    "gfl_png_strip_rows": (c_int, [c_int, c_int]),
+    "gfl_png_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "gfl_png_sizes": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "gfl_png_emit": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int64, _P, c_size_t, _P]),
     "gfl_optflow_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "gfl_optflow": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "gfl_optflow_level": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, c_int, c_int, c_int, _P, c_size_t, _P]),

@@ -5,7 +5,8 @@
 (``iterations_camera``, ``lr_camera_after``) followed by the full fit (``iterations_after``,
 ``lr_after``, occlusion-mask densification at iteration 0).  Inputs are in-memory frames (dicts
 as produced by ``gflow_amd.synthetic.make_clip``: image, depth, flow, move_mask, occ_mask, focal,
-pp); the reference's file readers and video writers are out of scope.
+pp); the reference's file readers are ``gflow_amd.io``, its log folder -- checkpoints, images, videos -- is what ``save`` writes
+(``gflow_amd.log_folder``).
 
 ``ClipFit`` is one clip's fit as an object: ``__init__`` refuses what can be refused and builds the trainer and the
 recorders that were asked for, ``steps()`` is the frame loop as a generator, ``result()`` the clip's dict.
@@ -16,6 +17,7 @@ import torch
 
 from . import camera as CM
 from . import flow as FL
+from . import log_folder as LF
 from . import msplat
 from . import propagation as PG
 from . import quality as QL
@@ -170,9 +172,11 @@ class ClipFit:
 
     def __init__(self, frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, log=None, load_extr=True, chunk=None,
                  async_snapshots=True, keep=None, cu_count=0, deterministic=None, track_queries=None, segment=False,
-                 recon=False, camera=False, flow=False, track_backward=False, track_vis=False, propagate=None):
+                 recon=False, camera=False, flow=False, track_backward=False, track_vis=False, propagate=None, save=None):
         if track_backward and track_queries is None:
             raise ValueError("fit_clip(track_backward=True) needs track_queries")
+        # (ValueError before anything is fitted: the operator path, names that are no file names)
+        self.clip_log = None if save is None else LF.ClipLog(save, frames, fused=fused)
         if track_vis and track_queries is None and not int((cfg or {}).get("traj_num", DEFAULTS["traj_num"])) > 0:
             raise ValueError("fit_clip(track_vis=True) needs track_queries or cfg['traj_num'] > 0")
         self.tracker = None
@@ -197,7 +201,7 @@ class ClipFit:
                             device=device, seed=seed, fused=fused, deterministic=deterministic)
         tr.async_snapshots = bool(async_snapshots)       # (trainer.py: snapshots composed beside the next iterations, or behind theirs)
         tr.cu_count = int(cu_count)                      # (the caller's stream is CU-masked: fit_clips_concurrent(partition=True))
-        if segment or (track_vis and self.traj):
+        if segment or (track_vis and self.traj) or self.clip_log is not None:
             tr.seg_recorder = SG.MoveSegRecorder(len(frames), tr.H, tr.W, tr.device)
         self.tr = tr
         self.vis_frames = [] if track_vis else None      # track_vis: every frame's final render, (H, W, 3) uint8 on the device
@@ -222,23 +226,24 @@ class ClipFit:
         # the trajectory seeds (select_traj_seeds, after the first frame's fit): their rows, those on the device, the split
         self.traj_index = self.traj_index_t = self.split_interval = None
         self.final = None                                # the engine of this frame's final_forward, once it has run (end_of_frame forgets it)
+        self.final_images = None                         # and the scene's images, if the reader that ran it asked for them
         self.psnr_sum = None
 
     def final_forward(self, scene=False):
         # The forward of THIS frame's final state on the second engine (fused path): run when the first of the frame's
         # recorders asks for it, shared by those after it -- the frame is rasterised once more, not once per recorder.
         # Returns (that engine, None); the reader that runs it may ask for the scene's images too (``scene=True``, the
-        # trajectory recorder, which asks first): (the engine, (3, H, W, 3) uint8) -- the forward, the snapshot of its images,
-        # then the overflow watch.
-        tr, images = self.tr, None
+        # log recorder and the trajectory recorder, which ask first): (the engine, (3, H, W, 3) uint8) -- the forward, the
+        # snapshot of its images, then the overflow watch; the images are kept for a later reader that asks for them too.
+        tr = self.tr
         if self.final is None:
             if scene:
-                images = tr.second.scene_u8(tr.engine, tr.bg)
+                self.final_images = tr.second.scene_u8(tr.engine, tr.bg)
             else:
                 tr.second.forward(tr.engine, tr.bg).watch_overflow()
             self.final = tr.second.engine
             tr.rasterisations_done += 1
-        return self.final, images
+        return self.final, (self.final_images if scene else None)
 
     def record_trajectories(self):
         # fit_video.py:226-238 / 335-349 call trainer.eval + project_points here, after every frame.  What they need of THIS
@@ -318,7 +323,9 @@ class ClipFit:
         # what every frame ends with, once its stages are fitted: the recorders that read the frame's final state (which share
         # final_forward's forward), its PSNR, the scores taken where the PSNR is
         tr = self.tr
-        self.final = None
+        self.final = self.final_images = None
+        if self.clip_log is not None:
+            self.clip_log.frame(self, i)                 # (first: its layer forwards use the second engine before the shared one)
         if self.traj:
             self.record_trajectories()
         if self.tracker is not None:
@@ -452,12 +459,17 @@ class ClipFit:
             out["propagation"] = self.object_rec.result([fr.get("object_mask") for fr in frames])
         if self.track_vis:
             out["track_vis"] = self.overlays(out)
+        if self.clip_log is not None:
+            # the hull masks as for ``segment`` (host work, once), then the folder: checkpoints, PNG and AVI files
+            rec = tr.seg_recorder
+            masks, valid = (out["segmentation"]["masks"], out["segmentation"]["valid"]) if self.segment else rec.masks(rec.fetch())
+            out["saved"] = self.clip_log.write(masks, valid, traj_out)
         return out
 
 
 def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=True, log=None, load_extr=True, chunk=None,
                    async_snapshots=True, keep=None, cu_count=0, deterministic=None, track_queries=None, segment=False,
-                   recon=False, camera=False, flow=False, track_backward=False, track_vis=False, propagate=None):
+                   recon=False, camera=False, flow=False, track_backward=False, track_vis=False, propagate=None, save=None):
     """fit_clip as a generator: yields after every ``chunk`` iterations of a stage (None: never) and returns the metrics
     dict of the clip (PSNR summed over its frames; with ``cfg["traj_num"]`` > 0 also ``"traj"``: the per-frame trajectory
     images and seed projections, host arrays -- what the reference's frame loop collects in
@@ -516,11 +528,20 @@ def fit_clip_steps(frames, device, cfg=None, seed=0, snapshot_interval=0, fused=
     before anything is fitted): every frame ends with one gfl_label_frame on the forward the other recorders read, and the
     dict then has ``"propagation"`` = dict(maps (T, H, W) uint8 -- 255 = unknown --, labels (N,) uint8, rows (T,), n_objects; counts
     (T, K - 1, 6), J, F, JF (T, K - 1), scored (T,), flat), scored against the frames' ``"object_mask"`` (frames 1 .. T - 1
-    that carry one).  Off by default; nothing about a fit changes with it off."""
+    that carry one).  Off by default; nothing about a fit changes with it off.
+    ``save``: None, or a folder that becomes the reference's log folder of this clip (gflow_amd.log_folder.ClipLog;
+    INTEGRATION.md, "Saving a fit"; needs ``fused=True``, else ValueError): every frame ends with clones of what
+    save_checkpoint stores, the scene's three images from the frame's shared final forward and the four layer images (two
+    more forwards), all kept on the device; once the clip is fitted ``ckpt/<name>.tar``, the seven ``images/img*_<name>.png``
+    and ``images_seg/move_mask_<name>.png`` per frame (PNG coded on the device, gflow_amd.png) and the ``sequence*.avi``
+    files at 5 fps are written, with ``traj_num`` also ``sequence_traj.avi``, ``sequence_traj_upon.avi`` and
+    ``sequence_traj.pkl``; ``<name>`` is the frame's ``"name"``, else its five-digit index.  The dict then has ``"saved"``, the
+    folder.  Saving reads the fit, it never steps it: the splats, the camera and the PSNR are what they are without it
+    (``rasterisations`` counts its forwards)."""
     cf = ClipFit(frames, device, cfg, seed=seed, snapshot_interval=snapshot_interval, fused=fused, log=log, load_extr=load_extr,
                  chunk=chunk, async_snapshots=async_snapshots, keep=keep, cu_count=cu_count, deterministic=deterministic,
                  track_queries=track_queries, segment=segment, recon=recon, camera=camera, flow=flow,
-                 track_backward=track_backward, track_vis=track_vis, propagate=propagate)
+                 track_backward=track_backward, track_vis=track_vis, propagate=propagate, save=save)
     yield from cf.steps()
     return cf.result()
 
@@ -553,7 +574,7 @@ def fit_clip(frames, device, cfg=None, fused=True, deterministic=None, **options
 
 
 def fit_clips_concurrent(clips, device, cfg=None, seeds=None, chunk=32, partition=False, deterministic=None,
-                         track_queries=None, track_backward=False, track_vis=False, propagate=None, **options):
+                         track_queries=None, track_backward=False, track_vis=False, propagate=None, save=None, **options):
     """Fit several clips AT THE SAME TIME on ONE device, in one host thread: every clip has its own trainer, engine and
     STREAM, and the clips take turns enqueueing ``chunk`` iterations each (fit_clip_steps), so their graph launches
     interleave on the device.  One fit leaves the chip partly idle -- its kernels are a chain of dependent launches,
@@ -573,7 +594,7 @@ def fit_clips_concurrent(clips, device, cfg=None, seeds=None, chunk=32, partitio
     ``track_queries``: None, or one entry (fit_clip_steps' ``track_queries``, or None) per clip; ``track_backward``:
     fit_clip_steps' for every clip that has queries (ValueError without ``track_queries``).  ``track_vis``: fit_clip_steps',
     for all clips, or a list with one entry per clip.  ``propagate``: None, or one prompt (fit_clip_steps' ``propagate``, or
-    None) per clip.  ``options``: fit_clip_steps'
+    None) per clip.  ``save``: None, or one folder (fit_clip_steps' ``save``, or None) per clip.  ``options``: fit_clip_steps'
     other ones, for all clips (``async_snapshots`` and ``cu_count`` are set here)."""
     n = len(clips)
     if track_queries is not None and len(track_queries) != n:
@@ -582,6 +603,8 @@ def fit_clips_concurrent(clips, device, cfg=None, seeds=None, chunk=32, partitio
         raise ValueError("fit_clips_concurrent(track_backward=True) needs track_queries")
     if propagate is not None and len(propagate) != n:
         raise ValueError("fit_clips_concurrent: propagate needs one entry per clip")
+    if save is not None and (isinstance(save, (str, bytes)) or len(save) != n):
+        raise ValueError("fit_clips_concurrent: save needs one folder per clip")
     if isinstance(track_vis, (list, tuple)) and len(track_vis) != n:
         raise ValueError("fit_clips_concurrent: a list of track_vis needs one entry per clip")
     seeds = list(range(n)) if seeds is None else seeds
@@ -605,7 +628,8 @@ def fit_clips_concurrent(clips, device, cfg=None, seeds=None, chunk=32, partitio
                            track_queries=None if track_queries is None else track_queries[i],
                            track_backward=bool(track_backward) and track_queries[i] is not None,
                            track_vis=track_vis[i] if isinstance(track_vis, (list, tuple)) else track_vis,
-                           propagate=None if propagate is None else propagate[i], **options)
+                           propagate=None if propagate is None else propagate[i],
+                           save=None if save is None else save[i], **options)
             for i in range(n)]
     results = [None] * n
     live = list(range(n))

@@ -137,6 +137,9 @@ def _parser():
     ap.add_argument("--focal", type=float, default=None,
                     help="with --make-depth-camera: the focal length in pixels of the native images (default: max(W, H), an "
                          "assumption)")
+    ap.add_argument("--out", default=None,
+                    help="save every clip's fit as the reference's log folder DIR/clip_<i>/ (ckpt/, images/, images_seg/, the "
+                         "sequence*.avi files; gflow_amd.log_folder): `python -m gflow_amd.viewer --folder DIR/clip_0` opens it")
     ap.add_argument("--metrics-csv", default=None,
                     help="rank 0 writes the blocks that were asked for as key,value lines under the reference's "
                          "metrics.csv keys")
@@ -268,19 +271,21 @@ def _fit_groups(args, clips, lengths, dev, cfg, gts, queries, rank):
                    recon=args.recon, camera=args.camera, flow=("maps" if args.flow_out else True) if args.flow else False,
                    load_extr=not args.no_load_extr)
     prompt = lambda ci: clips[ci][0]["object_mask"] if args.propagate else None
+    folder = lambda ci: os.path.join(args.out, f"clip_{ci}") if args.out else None
     results = {}
     for g0 in range(0, len(order), c):
         group = order[g0:g0 + c]
         if len(group) == 1:
             ci = group[0]
             res = [fit_clip(clips[ci], dev, cfg, seed=ci, track_queries=queries.get(ci),
-                            track_vis=_vis_option(args, gts, clips, ci), propagate=prompt(ci), **options,
+                            track_vis=_vis_option(args, gts, clips, ci), propagate=prompt(ci), save=folder(ci), **options,
                             log=(lambda s, ci=ci: print(f"[rank {rank} clip {ci}] {s}")) if args.verbose else None)]
         else:
             res = fit_clips_concurrent([clips[ci] for ci in group], dev, cfg, seeds=group,
                                        track_queries=[queries.get(ci) for ci in group] if args.track else None,
                                        track_vis=[_vis_option(args, gts, clips, ci) for ci in group],
-                                       propagate=[prompt(ci) for ci in group] if args.propagate else None, **options)
+                                       propagate=[prompt(ci) for ci in group] if args.propagate else None,
+                                       save=[folder(ci) for ci in group] if args.out else None, **options)
         results.update(zip(group, res))
     return results
 

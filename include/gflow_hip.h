@@ -116,7 +116,8 @@ typedef enum gfl_status {
  * number stays; a binding that needs it looks the symbol up).  gfl_track_history, gfl_track_backward and
  * gfl_track_backward_workspace_bytes were added WITHIN 312 in the same way, and so were gfl_track_vis and gfl_prep_frames with
  * their workspace queries, the four gfl_jpeg_* entries, and gfl_optflow, gfl_optflow_level, gfl_optflow_workspace_bytes,
- * the seven gfl_sfm_* entries, gfl_selftest_block_scan and gfl_label_frame, gfl_label_assign.  A binding checks
+ * the seven gfl_sfm_* entries, gfl_selftest_block_scan and gfl_label_frame, gfl_label_assign, and the four gfl_png_* entries
+ * (gfl_png_strip_rows, gfl_png_workspace_bytes, gfl_png_sizes, gfl_png_emit).  A binding checks
  * gfl_version() >= GFL_VERSION of the header it was written for. */
 #define GFL_VERSION 312
 int gfl_version(void);
@@ -965,6 +966,40 @@ int gfl_jpeg_decode(const uint8_t* bytes, int64_t n_bytes, const gfl_jpeg_unit* 
                     const gfl_jpeg_frame_tables* tables, int T, int C, int W, int H, int hs, int vs, uint8_t* images,
                     int32_t* unit_status, void* workspace, size_t workspace_bytes, gfl_stream_t stream);
 int gfl_jpeg_decode_struct_bytes(int* sizeof_unit, int* sizeof_frame_tables);
+
+/* ---- PNG files (additive within 312; gflow_amd/png.py, INTEGRATION.md "PNG files") -----------------------------------------
+ * The zlib stream (RFC 1950 / 1951) of T PNG images of one shape in two calls: what an IDAT chunk holds.  The host puts the
+ * chunks around it (gflow_amd.png.png_chunks).
+ *   images [T][H][W][C] uint8, contiguous, C = 1 (grey, or indices of a palette) or C = 3 (R, G, B).
+ * Filtered bytes: every row is the filter-type byte 2 (Up) and its W C bytes minus the RAW row above, mod 256; the row above
+ *   row 0 is zeros.  An image is cut into strips of gfl_png_strip_rows(C, W) = clamp(32768 / (1 + W C), 1, 64) rows (its last
+ *   strip is shorter), so that a strip's filtered bytes fit in 32 KiB of LDS; 0: one filtered row does not fit, the shape is
+ *   refused.  The row above a strip's first row is the previous strip's last row.  One workgroup codes one (image, strip).
+ * Tokens: a literal, or a match of length 3 .. 258 at distance 1.  Matches are runs of one byte value inside the strip's filtered
+ *   bytes: the run's first byte is a literal, then matches of 258 while 258 bytes are left, then one match of 3 .. 257, or the
+ *   1 or 2 bytes left as literals.
+ * A strip is one non-final block of dynamic Huffman codes (BTYPE = 10) followed by an empty stored block (000, zero bits to
+ *   the byte, 00 00 FF FF), so that every strip ends on a byte -- or, where that would be longer, one stored block (5 + n bytes
+ *   for n filtered bytes): a strip never takes more than n + 5 bytes.  The literal / length code is built from the strip's own
+ *   histogram (EOB always present, lengths <= 15), the distance alphabet is always one symbol (distance 1) of length 1, the
+ *   code-length sequence uses the symbols 16 / 17 / 18 and its own code has lengths <= 7; both codes are complete (Kraft sum 1).
+ * An image's stream: 78 01, its strips, 03 00 (a final block that holds EOB alone), the big-endian Adler-32 of all its filtered
+ *   bytes -- taken per strip and combined in order: A = A1 + A2 - 1, B = B1 + B2 + n2 (A1 - 1), both mod 65521.
+ * gfl_png_sizes codes every strip, keeps its length and Adler-32, scans the lengths and combines the sums: the strip offsets
+ *   stay in the workspace, frame_offsets [T + 1] int64 on the device = where image t's stream starts in `out`, [T] = the total.
+ *   gfl_png_emit (same images, shape and workspace, after gfl_png_sizes on the same stream) codes again through the same
+ *   routine and writes every strip at its offset: exactly frame_offsets[T] bytes.  A strip that would end behind out_bytes is
+ *   not written at all -- nothing is ever stored outside [out, out + out_bytes).  The bytes depend on the inputs alone.
+ * GFL_ERR_INVALID, before any launch: a NULL pointer, C not 1 or 3, T, W or H < 1, gfl_png_strip_rows(C, W) = 0, more than 2^30
+ *   (image, strip) pairs, out_bytes < 1, a workspace or frame_offsets that is not 8-byte aligned.  GFL_ERR_WORKSPACE:
+ *   workspace_bytes < gfl_png_workspace_bytes (0 for arguments it rejects).  No allocation, no host synchronisation;
+ *   gfl_png_strip_rows and gfl_png_workspace_bytes need no device. */
+int gfl_png_strip_rows(int C, int W);
+size_t gfl_png_workspace_bytes(int T, int C, int W, int H);
+int gfl_png_sizes(const uint8_t* images, int T, int C, int W, int H, int64_t* frame_offsets, void* workspace,
+                  size_t workspace_bytes, gfl_stream_t stream);
+int gfl_png_emit(const uint8_t* images, int T, int C, int W, int H, uint8_t* out, int64_t out_bytes, void* workspace,
+                 size_t workspace_bytes, gfl_stream_t stream);
 
 /* ---- optical flow (additive within 312; gflow_amd/optflow.py, INTEGRATION.md "Flows from the images") --------------------
  * The flow a -> b on a's grid, in pixels, of P pairs of images: a classical coarse-to-fine variational estimate (robust data
