@@ -126,6 +126,8 @@ SIGNATURES = {
     "gfl_png_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "gfl_png_sizes": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "gfl_png_emit": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int64, _P, c_size_t, _P]),
+    "gfl_png_decode_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "gfl_png_decode": (c_int, [_P, c_int64, _P, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "gfl_optflow_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "gfl_optflow": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "gfl_optflow_level": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, c_int, c_int, c_int, _P, c_size_t, _P]),

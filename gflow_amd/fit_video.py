@@ -64,9 +64,10 @@ def _parser():
     ap.add_argument("--prep", choices=("host", "device"), default="host",
                     help="with --sequence: where the decoded files are converted, resized and blurred -- on the host with "
                          "torch, one file at a time, or as whole stacks on this rank's device (gflow_amd.prep)")
-    ap.add_argument("--decode", choices=("host", "device"), default="host",
+    ap.add_argument("--decode", choices=("host", "device", "device-all"), default="host",
                     help="with --sequence: where the image files are decoded -- PIL on the host, or the JPEG files as one stack "
-                         "on this rank's device (gflow_amd.video.decode_jpeg: the same bits; implies --prep device).  A "
+                         "on this rank's device (gflow_amd.video.decode_jpeg: the same bits; implies --prep device); "
+                         "device-all decodes the PNG images and masks there too (gflow_amd.png.decode_png).  A "
                          "--sequence that is a .avi file is always decoded and prepared on the device")
     ap.add_argument("--deterministic", action="store_true",
                     help="bit-identical results for identical inputs (the library's deterministic mode, INTEGRATION.md)")
@@ -209,7 +210,7 @@ def _load_clips(args, mine, lengths, dev):
             clips[ci] = gio.load_sequence(args.sequence[ci], resize=args.resize,
                                           move_masks="epipolar" if args.make_move_masks else "files",
                                           occ_masks="flow" if args.make_occ_masks else "files", blur=args.blur,
-                                          device=dev if (args.prep == "device" or args.decode == "device"
+                                          device=dev if (args.prep == "device" or args.decode != "host"
                                                          or gio.is_video(args.sequence[ci])) else None,
                                           decode=args.decode,
                                           flows="estimate" if args.make_flows else "files",

@@ -64,6 +64,8 @@ def _blur_chw(t, blur, kernel_size=7, sigma=5.0):
 
 
 def _image_div(dtype):
+    if isinstance(dtype, torch.dtype):             # (decoded on the device: uint8)
+        return 255.0 if dtype == torch.uint8 else 1.0
     return 255.0 if dtype == np.uint8 else 65535.0 if dtype == np.uint16 else 1.0
 
 
@@ -230,7 +232,7 @@ def sequence_paths(sequence_path, frame_start=0, frame_range=-1, skip_interval=1
     return {k: cut(v, k == "occ") for k, v in every.items()}
 
 
-_OPTIONS = dict(decode=("host", "device"), occ_masks=("files", "flow"), move_masks=("files", "epipolar"),
+_OPTIONS = dict(decode=("host", "device", "device-all"), occ_masks=("files", "flow"), move_masks=("files", "epipolar"),
                 flows=("files", "estimate"), depth_camera=("files", "estimate"))
 
 
@@ -268,19 +270,24 @@ def load_sequence(sequence_path, resize=None, frame_start=0, frame_range=-1, ski
     weights ("Frame preparation"): without ``resize`` and ``blur`` both paths give the same bits.
     ``decode``: "host" opens every image file with PIL; "device" (needs ``device``) decodes the JPEG files that
     gflow_amd.video.parse_jpeg accepts in one gflow_amd.video.decode_jpeg call per shape -- the same bits, so the frames are
-    the same tensors -- and leaves PNGs and refused JPEGs to PIL, with one warning per clip that says how many.  A video
+    the same tensors -- and leaves PNGs and refused JPEGs to PIL, with one warning per clip that says how many.
+    "device-all" (needs ``device`` too) does that and also decodes the PNG files gflow_amd.png.parse_png accepts -- images,
+    move masks, occlusion masks and object masks -- with gflow_amd.png.decode_png, one call per kind and shape, again the
+    same bits; whatever is left (16-bit or interlaced PNGs, other formats) is opened by PIL, with one warning per clip that
+    counts those files.  A video
     file's frames (``sequence_path`` a ``.avi`` file) are always decoded on the device: without ``device`` it raises.
     ``object_masks``: "none" (the default) leaves the frames as they are; "files" reads ``<seq>_mask/*.png``, sliced like
     the other per-frame files, into ``frames[i]["object_mask"]`` -- (H, W) uint8 ids (``read_object_mask``: resized nearest
     neighbour, never blurred; on ``device`` if there is one) -- which is None for a frame without a file."""
     given = dict(decode=decode, occ_masks=occ_masks, move_masks=move_masks, flows=flows, depth_camera=depth_camera)
-    for name, (a, b) in _OPTIONS.items():
-        if given[name] not in (a, b):
-            raise ValueError(f"load_sequence: {name} must be \"{a}\" or \"{b}\", got {given[name]!r}")
+    for name, allowed in _OPTIONS.items():
+        if given[name] not in allowed:
+            (a, b), more = allowed[:2], "".join(f" or \"{c}\"" for c in allowed[2:])
+            raise ValueError(f"load_sequence: {name} must be \"{a}\" or \"{b}\"{more}, got {given[name]!r}")
     if object_masks not in ("none", "files"):
         raise ValueError(f"load_sequence: object_masks must be \"none\" or \"files\", got {object_masks!r}")
-    if decode == "device" and device is None:
-        raise ValueError("load_sequence: decode=\"device\" needs device=")
+    if decode != "host" and device is None:
+        raise ValueError(f"load_sequence: decode=\"{decode}\" needs device=")
     if is_video(sequence_path) and device is None:
         raise RuntimeError(f"gflow_amd.io: {sequence_path}: a video file is decoded on a HIP (cuda) device, pass device=; there "
                            "is no CPU fallback")
@@ -295,17 +302,31 @@ def load_sequence(sequence_path, resize=None, frame_start=0, frame_range=-1, ski
             raise RuntimeError("gflow_amd.io: load_sequence with device=, flows=\"estimate\" or depth_camera=\"estimate\" needs a "
                                "HIP (cuda) device; there is no CPU fallback")
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    tally = [0, 0]                                 # decode="device-all": files PIL had to open, files in all
     clip = _resolve(sequence_path, frame_start, frame_range, skip_interval, move_masks, occ_masks, flows, depth_camera, focal,
-                    decode, dev)
+                    decode, dev, tally)
     prep = _HostPrep(resize, blur, depth_offset) if device is None else _DevicePrep(dev, resize, blur, depth_offset)
     frames = _assemble(clip, prep)
     if object_masks == "files":
-        for fr, path in zip(frames, clip.objects + [None] * len(frames)):
+        paths = [path for _, path in zip(frames, clip.objects)]
+        on_device, colour = [None] * len(paths), [None] * len(paths)
+        if decode == "device-all":
+            on_device, colour = _device_pngs(paths, dev)
+            _count(tally, sum(a is None for a in on_device), len(paths))
+        for fr, path, a, c in zip(frames, paths + [None] * len(frames), on_device + [None] * len(frames),
+                                  colour + [None] * len(frames)):
+            if a is not None:                      # _object_ids' rule on the decoded tensor
+                ids = a if c == 3 else (a.reshape(a.shape[0], a.shape[1], -1) != 0).any(dim=-1).to(torch.uint8)
+                fr["object_mask"] = _resize_ids(ids.contiguous(), resize)
+                continue
             ids = None if path is None else read_object_mask(path, resize)
             fr["object_mask"] = ids if ids is None or device is None else ids.to(dev)
     if move_masks == "epipolar":
         from .move_seg import clip_move_masks
         clip_move_masks(frames, n_flows=len(clip.fwd))
+    if decode == "device-all" and tally[0]:
+        warnings.warn(f"load_sequence(decode=\"device-all\"): {tally[0]} of {tally[1]} image and mask files were decoded on the "
+                      "host (files outside the device decoders' scope)")
     return frames
 
 
@@ -327,7 +348,7 @@ class _Clip:
 
 
 def _resolve(sequence_path, frame_start, frame_range, skip_interval, move_masks, occ_masks, flows, depth_camera, focal, decode,
-             dev):
+             dev, tally):
     """In dependency order: images -> flows -> native occlusion -> the geometry's exclusion masks -> depth and camera."""
     every = _every_path(sequence_path)
     cut = _slicer(len(every["img"]), frame_start, frame_range, skip_interval)
@@ -338,7 +359,7 @@ def _resolve(sequence_path, frame_start, frame_range, skip_interval, move_masks,
     pairs = cut(list(range(max(len(every["img"]) - 1, 0)))) if flows == "estimate" else []
     touched = sorted(set(pairs) | {i + 1 for i in pairs})
     used = sorted(set(mine) | set(touched))
-    decoded = dict(zip(used, _decode_images([every["img"][i] for i in used], decode, dev)))
+    decoded = dict(zip(used, _decode_images([every["img"][i] for i in used], decode, dev, tally)))
     # flows: pair k of the list is (image k, image k + 1), as in a folder that holds the flows of EVERY pair
     if flows == "files":
         fwd = [_read_flo(f) for f in p["flow"][:n]]
@@ -346,7 +367,7 @@ def _resolve(sequence_path, frame_start, frame_range, skip_interval, move_masks,
     elif pairs:
         from .optflow import clip_flows
         where = {i: j for j, i in enumerate(touched)}              # (i and i + 1 stay neighbours in the stack)
-        stack = _image_stack([decoded[i] for i in touched], dev, decode == "device" or is_video(sequence_path))
+        stack = _image_stack([decoded[i] for i in touched], dev, decode != "host" or is_video(sequence_path))
         fwd, bwd = (list(f[:n]) for f in clip_flows(stack, pairs=[where[i] for i in pairs]))
     else:
         fwd, bwd = [], []
@@ -372,11 +393,11 @@ def _resolve(sequence_path, frame_start, frame_range, skip_interval, move_masks,
             for j, i in enumerate(idx):
                 occ[i] = (masks[j], 1.0)
     else:
-        occ_files = [_open_image(f) for f in p["occ"][:m if estimate else frames_reach]]
+        occ_files = _open_images(p["occ"][:m if estimate else frames_reach], decode, dev, tally)
         occ = [_image_array(a) for a in occ_files]
     move = [None] * n
     if move_masks == "files":
-        move = [_decode_mask(p["move"][i]) if i < len(p["move"]) else None for i in range(n)]
+        move = [_mask_array(a) for a in _open_images(p["move"][:n], decode, dev, tally)] + [None] * max(n - len(p["move"]), 0)
     if estimate:
         f_dev, b_dev = _stack(fwd, dev), _stack(bwd[:m], dev) if both else None
         ex_f, ex_b = _exclusions(f_dev, move[:m], [_mask_array(a) for a in occ_files], checked if both else None,
@@ -444,18 +465,60 @@ def _open_image(path):
     return np.asarray(Image.open(path))
 
 
+def _device_pngs(paths, device):
+    """([a device tensor with the shape and the bits of np.asarray(Image.open(path)), or None], [the file's colour type, or
+    None]): the PNG files gflow_amd.png.parse_png accepts, decoded by gflow_amd.png.decode_png in one call per shape"""
+    from .png import decode_png, parse_png
+    out, colour, groups = [None] * len(paths), [None] * len(paths), {}
+    for i, ip in enumerate(paths):
+        if isinstance(ip, AviFrame) or not str(ip).lower().endswith(".png"):
+            continue
+        with open(ip, "rb") as f:
+            data = f.read()
+        try:
+            p = parse_png(data, str(ip))
+        except ValueError:
+            continue
+        colour[i] = p["colour_type"]
+        groups.setdefault((p["width"], p["height"], p["bpp"]), []).append((i, p))
+    for members in groups.values():
+        stack = decode_png([p for _, p in members], device, names=[str(paths[i]) for i, _ in members])
+        for j, (i, _) in enumerate(members):
+            out[i] = stack[j, :, :, 0] if stack.shape[-1] == 1 else stack[j]
+    return out, colour
+
+
+def _open_images(paths, decode, device, tally):
+    """_open_image of every path; with decode="device-all" the PNG files the device decoder takes come from it, as device
+    tensors.  ``tally``: [files PIL opened, files in all], counted under "device-all" only."""
+    if decode != "device-all":
+        return [_open_image(ip) for ip in paths]
+    on_device = _device_pngs(paths, device)[0]
+    _count(tally, sum(a is None for a in on_device), len(paths))
+    return [_open_image(ip) if a is None else a for ip, a in zip(paths, on_device)]
+
+
+def _count(tally, on_host, files):
+    """decode="device-all": ``on_host`` of ``files`` more files were left to PIL"""
+    tally[0] += on_host
+    tally[1] += files
+
+
 def _mask_array(mask):
     """(H, W, C) uint8 or float32 as read_mask takes a file's array"""
     if mask.ndim == 2:
         mask = mask[..., None]
     elif mask.ndim != 3:
         raise ValueError("The mask should be 2D or 3D")
+    if torch.is_tensor(mask):                      # (decoded on the device: uint8)
+        return mask.contiguous()
     return np.ascontiguousarray(mask if mask.dtype == np.uint8 else mask.astype(np.float32))
 
 
 def _image_array(img):
     """(array (H, W, C <= 3) uint8 or float32, the divisor that makes it [0, 1]) as image_path_to_tensor takes a file's array"""
-    return np.ascontiguousarray(_mask_array(img)[..., :3]), _image_div(img.dtype)
+    rgb = _mask_array(img)[..., :3]
+    return rgb.contiguous() if torch.is_tensor(rgb) else np.ascontiguousarray(rgb), _image_div(img.dtype)
 
 
 def _decode_image(path):
@@ -468,17 +531,19 @@ def _decode_mask(path):
     return _mask_array(_open_image(path))
 
 
-def _decode_images(paths, decode, device):
+def _decode_images(paths, decode, device, tally=None):
     """[(array or device tensor (H, W, C <= 3), divisor)] of a clip's images, as _decode_image gives them.  A video file's
     frames, and with decode="device" the JPEG files the device decoder takes, come from gflow_amd.video.decode_jpeg as
-    device tensors (one call per shape); every other file from PIL, with one warning that counts them."""
+    device tensors (one call per shape); every other file from PIL, with one warning that counts them.  With
+    decode="device-all" the PNG files gflow_amd.png.parse_png accepts come from gflow_amd.png.decode_png as well, and the
+    files left to PIL are counted into ``tally`` for the clip's one warning."""
     from .video import decode_jpeg, parse_jpeg
     out = [None] * len(paths)
-    groups, on_host = {}, 0
+    groups, rest = {}, []                          # JPEG data by shape; the indices of every other file
     for i, ip in enumerate(paths):
         if isinstance(ip, AviFrame):
             data, name = ip.data, repr(ip)
-        elif decode == "device" and str(ip).lower().endswith((".jpg", ".jpeg")):
+        elif decode != "host" and str(ip).lower().endswith((".jpg", ".jpeg")):
             with open(ip, "rb") as f:
                 data, name = f.read(), str(ip)
         else:
@@ -491,8 +556,16 @@ def _decode_images(paths, decode, device):
             except ValueError:
                 if isinstance(ip, AviFrame):
                     raise
-        out[i] = _decode_image(ip)
-        on_host += decode == "device"
+        rest.append(i)
+    if decode == "device-all":
+        on_device = _device_pngs([paths[i] for i in rest], device)[0]
+        for i, a in zip(rest, on_device):
+            out[i] = _image_array(_open_image(paths[i]) if a is None else a)
+        _count(tally, sum(a is None for a in on_device), len(paths))
+    else:
+        for i in rest:
+            out[i] = _decode_image(paths[i])
+    on_host = len(rest) if decode == "device" else 0
     for members in groups.values():
         stack = decode_jpeg([d for _, d, _ in members], device, names=[n for _, _, n in members])
         for j, (i, _, _) in enumerate(members):
@@ -510,7 +583,7 @@ def _np(a):
 
 def _mask_to_tensor(mask, resize=None):
     """what read_mask makes of a file's (H, W, C) array"""
-    t = _resize_chw(torch.from_numpy(np.array(mask)).float().permute(2, 0, 1), resize)
+    t = _resize_chw(torch.from_numpy(np.array(_np(mask))).float().permute(2, 0, 1), resize)
     if t.shape[-1] > 1:
         t = t.sum(dim=0)
     return t.squeeze() > 0

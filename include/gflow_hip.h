@@ -117,7 +117,8 @@ typedef enum gfl_status {
  * gfl_track_backward_workspace_bytes were added WITHIN 312 in the same way, and so were gfl_track_vis and gfl_prep_frames with
  * their workspace queries, the four gfl_jpeg_* entries, and gfl_optflow, gfl_optflow_level, gfl_optflow_workspace_bytes,
  * the seven gfl_sfm_* entries, gfl_selftest_block_scan and gfl_label_frame, gfl_label_assign, and the four gfl_png_* entries
- * (gfl_png_strip_rows, gfl_png_workspace_bytes, gfl_png_sizes, gfl_png_emit).  A binding checks
+ * (gfl_png_strip_rows, gfl_png_workspace_bytes, gfl_png_sizes, gfl_png_emit), and gfl_png_decode with
+ * gfl_png_decode_workspace_bytes.  A binding checks
  * gfl_version() >= GFL_VERSION of the header it was written for. */
 #define GFL_VERSION 312
 int gfl_version(void);
@@ -1000,6 +1001,41 @@ int gfl_png_sizes(const uint8_t* images, int T, int C, int W, int H, int64_t* fr
                   size_t workspace_bytes, gfl_stream_t stream);
 int gfl_png_emit(const uint8_t* images, int T, int C, int W, int H, uint8_t* out, int64_t out_bytes, void* workspace,
                  size_t workspace_bytes, gfl_stream_t stream);
+
+/* Decoding (additive within 312; gflow_amd.png.decode_png, INTEGRATION.md "Decoding PNG files"; the decoder proper -- bit reader,
+ * block headers, table construction, symbol decode -- lives in csrc/gfl_inflate.hpp, which a host compiler takes too:
+ * tools/png_dec_host.cpp; the device's input staging and output window are csrc/gfl_png_dec.hip's alone).  The zlib streams of T
+ * non-interlaced 8-bit PNG images of one shape -> their pixels, the bits of np.asarray(PIL.Image.open(file)).
+ *   data [n_bytes] uint8; offsets [T + 1] int64 on the device (8-byte aligned): image t's stream -- its IDAT payloads put
+ *     together -- is data[offsets[t], offsets[t + 1]), clipped to [0, n_bytes] whatever the offsets say.
+ *   bpp = bytes per pixel, 1 .. 4 (grey or palette indices, grey + alpha, RGB, RGBA); images [T][H][W][bpp] uint8.
+ * Two launches.  inflate: one 64-lane workgroup per image (a stream is serial) turns the stream into its H (1 + W bpp)
+ *   filtered bytes in the workspace -- stored, fixed and dynamic blocks, distances up to 32768, overlapping copies; window and
+ *   code tables in LDS.  unfilter: filter types 0 .. 4 per row, the row above row 0 zeros, a lane per row.
+ * status [T] int32 (4-byte aligned): 0, or the FIRST error of the image's stream in stream order -- decoding of that image
+ *   stops there, the image is left entirely zero, other images of the call are unaffected.  The filter-type bytes are looked
+ *   at once the stream has passed all other checks.  Bytes behind the checksum are ignored.  Every read of `data` and every
+ *   write is bounds-checked against the image's own extent: malformed input gives a status, never an out-of-range access.
+ * GFL_ERR_INVALID, before any launch: a NULL pointer, T, W or H < 1, bpp outside 1 .. 4, n_bytes < 0, an image of 2^31 or more
+ *   filtered bytes, a workspace that is not 16-byte aligned.  GFL_ERR_WORKSPACE: workspace_bytes <
+ *   gfl_png_decode_workspace_bytes (0 for arguments it rejects; needs no device).  No allocation, no host synchronisation. */
+#define GFL_PNG_OK 0
+#define GFL_PNG_INPUT_END 1        /* the input ends early */
+#define GFL_PNG_BAD_HEADER 2       /* zlib header: CM != 8, window > 32 KiB, FCHECK, FDICT set */
+#define GFL_PNG_BLOCK_TYPE 3       /* reserved block type */
+#define GFL_PNG_STORED_LEN 4       /* a stored block's LEN / NLEN disagree */
+#define GFL_PNG_TOO_MANY_CODES 5   /* HLIT > 286 or HDIST > 30 */
+#define GFL_PNG_BAD_REPEAT 6       /* a repeat code with nothing to repeat, or one running past the end */
+#define GFL_PNG_BAD_CODE 7         /* an over-subscribed code, or an incomplete one (but a single code of length 1) */
+#define GFL_PNG_NO_END_OF_BLOCK 8  /* no end-of-block code */
+#define GFL_PNG_BAD_SYMBOL 9       /* an undefined symbol, or a length or distance symbol out of range */
+#define GFL_PNG_FAR_DISTANCE 10    /* a distance reaching before the start of the output */
+#define GFL_PNG_OUTPUT_SIZE 11     /* more or fewer output bytes than H (1 + W bpp) */
+#define GFL_PNG_BAD_ADLER 12       /* Adler-32 mismatch */
+#define GFL_PNG_BAD_FILTER 13      /* a filter-type byte above 4 */
+size_t gfl_png_decode_workspace_bytes(int T, int bpp, int W, int H);
+int gfl_png_decode(const uint8_t* data, int64_t n_bytes, const int64_t* offsets, int T, int bpp, int W, int H, uint8_t* images,
+                   int32_t* status, void* workspace, size_t workspace_bytes, gfl_stream_t stream);
 
 /* ---- optical flow (additive within 312; gflow_amd/optflow.py, INTEGRATION.md "Flows from the images") --------------------
  * The flow a -> b on a's grid, in pixels, of P pairs of images: a classical coarse-to-fine variational estimate (robust data
